@@ -188,6 +188,7 @@ def bench_teacher(args, device):
             out = net(x)
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        outputs = {"logits": out.cpu()} if args.dump_outputs else None
         lib.profiler = LaunchProfiler()
         net(x)
         net(x)
@@ -224,7 +225,8 @@ def bench_teacher(args, device):
             "config": {"workload": "teacher: {} - {}x3x{}x{}".format(WORKLOADS["teacher"][6], args.batch,
                                                                   args.height, args.width),
                        "logits_shape": list(out.shape)},
-            "roofline": roof, "cpu_baseline": None}
+            "roofline": roof, "cpu_baseline": None,
+            "dumped_outputs": dump_outputs(args.dump_outputs, outputs) if outputs else None}
 
 
 def build_model(device, workload="headline"):
@@ -262,6 +264,46 @@ def synthetic_batch(batch, height, width, rank, device, classes=NUM_CLASSES):
     mask[:, height // 2: height // 2 + 5, :] = 255
     image = image.to(device).contiguous(memory_format=torch.channels_last)
     return image, mask.to(device)
+
+
+DUMP_BUDGET_BYTES = 56 << 20  # --dump-outputs: array data written at most (under 64 MB with the .npy headers)
+
+
+def step_outputs(loss, net):
+    """What a caller of the timed training step holds after its last call, copied to the host before anything
+    else runs (the roofline passes step the model again): the loss, the parameters and BatchNorm buffers the step
+    left behind, and the gradients it computed."""
+    out = {"loss": loss.detach().reshape(1)}
+    for k, v in net.state_dict().items():
+        out["state." + k] = v
+    for k, p in net.named_parameters():
+        if p.grad is not None:
+            out["grad." + k] = p.grad
+    return {k: v.detach().cpu() for k, v in out.items()}
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every array as ``out_dir/<name>.npy``, float64 if it is float64 or an integer type, float32
+    otherwise.  If they hold more than ``budget`` bytes in all, each one is replaced by the same share of its
+    flattened elements at indices drawn (sorted, without repetition) from numpy's default_rng(0): a fixed sample, so
+    that the dumps of two builds still compare element for element.  Returns a summary for the JSON line."""
+    import numpy as np
+
+    host = {}
+    for name, t in arrays.items():
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.is_complex())
+        host[name] = t.to(torch.float64 if wide else torch.float32).numpy()
+    total = sum(a.nbytes for a in host.values())
+    share = min(1.0, budget / total) if total else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, a in host.items():
+        if share < 1.0:
+            keep = max(1, int(a.size * share))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += a.nbytes
+    return {"dir": out_dir, "arrays": len(host), "bytes": written, "sampled": share < 1.0}
 
 
 def cpu_baseline(height, width):
@@ -675,11 +717,17 @@ def main():
                     help="debug: read the loss on the host after every step (the engine's loss.item())")
     ap.add_argument("--launch-selftest", action="store_true",
                     help="only launch the ranks, rendezvous and all-reduce on the CPU (gloo): no GPU needed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy: the "
+                         "loss, the model's parameters and buffers, the parameter gradients (the teacher: its logits); "
+                         "a fixed, seeded sample of each array if they exceed 56 MiB in all")
     args = ap.parse_args()
     args.graph_flag_given = any(a == "--graph" or a.startswith("--graph=") for a in sys.argv[1:])
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started bare: become the launcher of N ranks (one per GPU) and pass rank 0's line through
         if not args.launch_selftest and not args.same_device:
@@ -857,6 +905,9 @@ def main():
             stamps.append(time.perf_counter())
     fence()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, step_outputs(loss, net))
     if args.step_times:
         sys.stderr.write("rank {} step ms (host, {}): {}  | fence +{:.1f}\n".format(
             rank, "synced" if args.sync_each_step else "not synced",
@@ -1021,7 +1072,7 @@ def main():
                        + (", {} lanes, {} line graphs, {} forks per step (line {} ms)".format(
                            graph_layout.get("lanes"), graph_layout.get("parts"), graph_layout.get("forks"),
                            graph_layout.get("line_ms")) if graph_layout and graph_layout.get("parts") else "")},
-            "roofline": roof, "cpu_baseline": cpu, "secondary": secondary,
+            "roofline": roof, "cpu_baseline": cpu, "secondary": secondary, "dumped_outputs": dumped,
         }
         if cpu:
             out["gpu_over_cpu"] = out["value"] / cpu["value"]

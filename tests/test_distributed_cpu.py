@@ -595,3 +595,31 @@ def test_bench_refuses_a_world_that_is_not_what_was_asked():
     out = _run_bench(["--gpus", "2"])
     if not torch.cuda.is_available():
         assert out.returncode != 0 and "HIP device" in (out.stderr + out.stdout)
+
+
+def test_bench_dump_outputs_samples_large_outputs_the_same_way_every_time(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on the host: float32 .npy files (float64 for float64 and integer arrays), whole while
+    they fit the budget, else the same seeded elements of every array in every run; --steps below 1 is refused"""
+    import numpy as np
+
+    # (bench.py sets this at import: the test process keeps its own value)
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    import bench
+
+    g = torch.Generator().manual_seed(0)
+    arrays = {"loss": torch.tensor([0.5]), "state.w": torch.randn(64, 32, generator=g),
+              "state.n": torch.tensor(7), "grad.w": torch.randn(64, 32, generator=g, dtype=torch.float64)}
+    whole = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert whole["arrays"] == 4 and not whole["sampled"]
+    for name, t in arrays.items():
+        a = np.load(tmp_path / "whole" / (name + ".npy"))
+        assert a.dtype == (np.float32 if name in ("loss", "state.w") else np.float64), name
+        assert a.shape == tuple(t.shape) and np.array_equal(a, t.numpy().astype(a.dtype)), name
+    budget = 4096
+    runs = [bench.dump_outputs(str(tmp_path / d), arrays, budget=budget) for d in ("s1", "s2")]
+    assert runs[0]["sampled"] and runs[0]["bytes"] <= budget + 8 * len(arrays)
+    for name, t in arrays.items():
+        a1, a2 = (np.load(tmp_path / d / (name + ".npy")) for d in ("s1", "s2"))
+        assert np.array_equal(a1, a2) and np.isin(a1, t.numpy().astype(a1.dtype).reshape(-1)).all(), name
+    out = _run_bench(["--steps", "0"])
+    assert out.returncode != 0 and "--steps must be >= 1" in (out.stderr + out.stdout)

@@ -667,6 +667,49 @@ def test_bench_prints_the_contract_line():
     assert cpu["kind"] == "port" and cpu["value"] > 0 and cpu["cores"] >= 1
 
 
+def test_bench_dumps_what_its_last_timed_step_computed(tmp_path):
+    """bench.py --dump-outputs at a reduced size: the last timed step's loss (the JSON line's), the parameters and
+    BatchNorm buffers it left and the gradients it computed, as float32 / float64 .npy files.  A second run with the
+    same arguments starts from the same inputs and weights and, the step being bit-reproducible, dumps the same bits."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(d):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1",
+                              "--batch", "2", "--height", "128", "--width", "256", "--no-cpu-baseline", "--no-roofline",
+                              "--pmc", "0", "--secondary", "0", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads(out.stdout.strip().splitlines()[-1])
+
+    rec = run(tmp_path / "a")
+    files = sorted(os.listdir(tmp_path / "a"))
+    got = {f[:-len(".npy")]: np.load(tmp_path / "a" / f) for f in files}
+    assert rec["dumped_outputs"]["arrays"] == len(files) and not rec["dumped_outputs"]["sampled"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10 ** 6
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert float(got["loss"][0]) == rec["config"]["loss"]
+    genotype = [[[3, 0, 1], [4, 1, 1], [3, 1, 1]],
+                [[0, 1, 0, 0, 1], [2, 1, 2, 1, 0], [3, 1, 1, 1, 0], [1, 1, 2, 0, 0],
+                 [3, 0, 2, 0, 0], [5, 3, 2, 1, 0], [0, 5, 0, 1, 0]]]
+    init = build_product_net("template", genotype, 19, dict(agg_size=64, repeats=2), 0)
+    params = dict(init.named_parameters())
+    assert set(got) == ({"loss"} | {"state." + k for k in init.state_dict()} | {"grad." + k for k in params})
+    for k, v in init.state_dict().items():
+        assert got["state." + k].shape == tuple(v.shape), k
+    # the state is the one after the timed steps: the optimisers moved (almost) every parameter from its seeded start
+    moved = sum(not np.array_equal(got["state." + k], v.detach().numpy()) for k, v in params.items())
+    assert moved > 0.9 * len(params), (moved, len(params))
+    run(tmp_path / "b")
+    assert sorted(os.listdir(tmp_path / "b")) == files
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), got[f[:-len(".npy")]]), f
+
+
 def test_task0_with_knowledge_distillation_matches_reference_run(monkeypatch):
     """populate_task0(do_kd=True) caches the teacher's logits (bilinear to the first feature map) and
     train_task0 adds kd_coeff * kd_crit(output, kd_y) (src/engine/trainer.py:53-61,147-149): losses,

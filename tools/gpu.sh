@@ -18,7 +18,7 @@
 #   tools/gpu.sh pmc      OUT SCRIPT "C1 C2"...     rocprofv3 --pmc passes (one per quoted counter set) over a tools/ script
 # The round's final collection stays tools/gpu_check.sh all; tools/gpu_pmc.sh; tools/gpu_pmc_mfma.sh (collect_profiles.sh).
 set -u
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 CMD="${1:-help}"
 if [[ "$CMD" == "help" || $# -lt 2 ]]; then sed -n 2,21p "$0"; exit 0; fi

@@ -3,7 +3,7 @@
 # file so that a faulting kernel cannot take the other files down), smoke(),
 # a short bench and a rocprofv3 kernel-trace summary.  Logs -> gpurun_out/.
 set -u
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=gpurun_out
 mkdir -p $OUT

@@ -2,7 +2,7 @@
 # HBM traffic counters for the bench workload: two separate rocprofv3 --pmc passes
 # (FETCH_SIZE uses 3 of the 4 TCC slots, WRITE_SIZE 2 - they do not fit one pass).
 set -u
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out
 mkdir -p $OUT

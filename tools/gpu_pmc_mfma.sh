@@ -4,7 +4,7 @@
 # separately by tools/gpu_pmc.sh) + a kernel trace for the launch durations, joined per dispatch
 # and summarised per kernel family -> gpurun_out/pmc_mfma_summary.txt
 set -u
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out
 mkdir -p $OUT
