@@ -483,6 +483,17 @@ int nasseg_lane_event_create(void** event);
 int nasseg_lane_destroy(void* stream, void* event);
 int nasseg_graph_run(int n_ops, const int64_t* ops, void* stream);
 
+/* ---- sample augmentation: the training / validation pipelines of data/datasets.py (data/device.py) ------
+ * One launch per batch of B samples, every output Ho x Wo.  src: packed uint8 source windows (HxWx3 images,
+ * HxW masks) of src_bytes bytes; desc int64 [B][8] = {image offset, mask offset, window height, window width,
+ * image row stride, mask row stride (bytes), image fill (3 bytes, channel 0 lowest), mask fill}; taps int32
+ * [B][9 (Ho + Wo)] = rows [Ho][4 indices, 4 coefficients], columns [Wo][4, 4] (OpenCV's 11-bit INTER_CUBIC
+ * coefficients; index -1: a fill pixel), mask rows [Ho], mask columns [Wo] (nearest index, -1: fill), indices
+ * into the window; lut [3][256]: output value of channel c for the uint8 result v.  Writes image [B][Ho][Wo][3]
+ * (NHWC) and mask uint8 [B][Ho][Wo]. */
+int nasseg_augment(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps, const float* lut,
+                   float* image, uint8_t* mask, int B, int Ho, int Wo, void* stream);
+
 /* ---- bfloat16 activation storage --------------------------------------------
  * Every entry point above that reads or writes ACTIVATIONS (feature maps and their gradients)
  * has a twin nasseg_bf16_<op> with the same arguments in which those tensors are stored as
@@ -644,6 +655,10 @@ int nasseg_bf16_conv_wgrad(const nasseg_bf16_t* x, int ldx, const nasseg_bf16_t*
                       const float* in_scale, const float* in_shift, int in_act, int B, int Hs,
                       int Ws, int K, int Ho, int Wo, int N, int kh, int kw, int stride, int pad,
                       int dil, void* stream);
+
+int nasseg_bf16_augment(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
+                        const nasseg_bf16_t* lut, nasseg_bf16_t* image, uint8_t* mask, int B, int Ho, int Wo,
+                        void* stream);
 
 #ifdef __cplusplus
 }

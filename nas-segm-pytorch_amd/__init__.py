@@ -9,7 +9,7 @@ from . import functional  # noqa: F401
 from ._lib import NassegError, lib  # noqa: F401
 
 
-def install_dropin(kd=False, data=False):
+def install_dropin(kd=False, data=False, data_on_device=False):
     """Register this package under the module names the reference's own scripts
     import (``nn.layer_factory``, ``nn.micro_decoders``, ``nn.encoders``,
     ``rl.genotypes``, ``helpers.miou_utils``, ``engine.trainer``,
@@ -19,6 +19,8 @@ def install_dropin(kd=False, data=False):
     src/main_search.py:456) onto ``kd/rf_lw.py``; data=True maps ``data.loaders``
     / ``data.datasets`` (src/main_search.py:30) onto ``data/`` - no OpenCV needed,
     its resizes are restatements whose parity with cv2 is NOT pinned.
+    data_on_device=True maps them too, but ``data.loaders.create_loaders`` then resolves to
+    data/device.py: the same batches, augmented on the GPU (fp32 images already on the device).
     See INTEGRATION.md."""
     import sys
 
@@ -43,6 +45,11 @@ def install_dropin(kd=False, data=False):
         from .data import datasets, loaders
 
         table.update({"data": data_pkg, "data.datasets": datasets, "data.loaders": loaders})
+    if data_on_device:
+        from . import data as data_pkg
+        from .data import datasets, device
+
+        table.update({"data": data_pkg, "data.datasets": datasets, "data.loaders": device})
     for name, mod in table.items():
         sys.modules[name] = mod
     # `rl`, `helpers`, `engine` keep the reference's other submodules importable:

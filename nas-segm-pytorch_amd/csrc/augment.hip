@@ -1,0 +1,111 @@
+// Sample augmentation of the data pipeline (data/datasets.py, planned by data/device.py): OpenCV's fixed-point
+// INTER_CUBIC resize, crops, mirror and constant borders, Normalise and the cast of the engine's image, in one
+// gather per batch.  The host hands over per-axis tables - four source indices and four 11-bit coefficients per
+// output row / column (index -1: a fill pixel), a nearest index per row / column for the mask - already rebased to
+// the uploaded source window, so the kernel only adds integers: the result is exact by construction, whatever the
+// summation order.  The uint8 result v of channel c becomes lut[c][v] (Normalise evaluated by the host in float64
+// and cast to act_t there).
+#include "common.h"
+
+namespace {
+
+// per-sample descriptor: int64 [AUG_DESC]
+enum { AUG_IMG_OFF, AUG_MSK_OFF, AUG_H, AUG_W, AUG_IMG_LD, AUG_MSK_LD, AUG_IMG_FILL, AUG_MSK_FILL, AUG_DESC };
+
+// one thread per output pixel of one sample (blockIdx.y), the pixels of a sample in row-major order: a wave writes
+// 64 consecutive pixels (768 contiguous bytes of fp32 image, 64 of mask), and the few output rows a workgroup
+// covers read the same four source rows, which stay in L1 / L2 between the lanes that share them.
+__global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                      const int64_t* __restrict__ desc,
+                                                      const int* __restrict__ taps,
+                                                      const act_t* __restrict__ lut, act_t* __restrict__ image,
+                                                      uint8_t* __restrict__ mask, int Ho, int Wo) {
+  __shared__ act_t slut[3 * 256];
+  for (int i = threadIdx.x; i < 3 * 256; i += 256) slut[i] = lut[i];
+  __syncthreads();
+
+  const int b = blockIdx.y;
+  const int64_t npix = (int64_t)Ho * Wo;
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= npix) return;
+  const int oy = (int)(p / Wo), ox = (int)(p - (int64_t)oy * Wo);
+
+  const int64_t* d = desc + (int64_t)b * AUG_DESC;
+  const int64_t img_off = d[AUG_IMG_OFF], msk_off = d[AUG_MSK_OFF];
+  const int h = (int)d[AUG_H], w = (int)d[AUG_W];
+  const int64_t img_ld = d[AUG_IMG_LD], msk_ld = d[AUG_MSK_LD];
+  const int img_fill = (int)d[AUG_IMG_FILL], msk_fill = (int)d[AUG_MSK_FILL];
+  // a window that does not lie inside the buffer is read as fill (the host checks before it launches; this
+  // keeps every load in bounds whatever it is handed)
+  const bool img_ok = h > 0 && w > 0 && img_off >= 0 && img_ld >= 3 * (int64_t)w &&
+                      img_off + (h - 1) * img_ld + 3 * (int64_t)w <= src_bytes;
+  const bool msk_ok = h > 0 && w > 0 && msk_off >= 0 && msk_ld >= w &&
+                      msk_off + (h - 1) * msk_ld + w <= src_bytes;
+
+  // tables of the sample: rows [Ho][8], columns [Wo][8] (4 indices, 4 coefficients), mask rows [Ho], columns [Wo]
+  const int* t = taps + (int64_t)b * (9 * (Ho + Wo));
+  const int* ty = t + oy * 8;
+  const int* tx = t + Ho * 8 + ox * 8;
+  const int my = t[8 * (Ho + Wo) + oy], mx = t[8 * (Ho + Wo) + Ho + ox];
+
+  int v[3];
+  if (ty[0] < 0 || tx[0] < 0 || !img_ok) {
+    v[0] = img_fill & 255;
+    v[1] = (img_fill >> 8) & 255;
+    v[2] = (img_fill >> 16) & 255;
+  } else {
+    int xo[4], ax[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      xo[j] = 3 * min(max(tx[j], 0), w - 1);
+      ax[j] = tx[4 + j];
+    }
+    // horizontal sums: |sum| <= 255 * sum|ax| (< 2^13 * 255), int32; vertical products and sum in int64 (up to
+    // ~255 * 2816^2 = 2.0e9 for Keys' A = -0.75, within 7 % of 2^31: exact in int64 for any coefficients)
+    int64_t acc[3] = {0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint8_t* row = src + img_off + (int64_t)min(max(ty[k], 0), h - 1) * img_ld;
+      int hs[3] = {0, 0, 0};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) hs[c] += ax[j] * (int)row[xo[j] + c];
+      }
+      const int64_t ay = ty[4 + k];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[c] += ay * hs[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int64_t r = (acc[c] + (1 << 21)) >> 22;  // arithmetic shift, as numpy's >> on int64
+      v[c] = (int)(r < 0 ? 0 : (r > 255 ? 255 : r));
+    }
+  }
+  act_t* o = image + ((int64_t)b * npix + p) * 3;
+  o[0] = slut[v[0]];
+  o[1] = slut[256 + v[1]];
+  o[2] = slut[512 + v[2]];
+
+  int m = msk_fill & 255;
+  if (my >= 0 && mx >= 0 && msk_ok) m = src[msk_off + (int64_t)min(my, h - 1) * msk_ld + min(mx, w - 1)];
+  mask[(int64_t)b * npix + p] = (uint8_t)m;
+}
+
+}  // namespace
+
+extern "C" {
+
+int NASSEG_FN(augment)(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
+                       const act_t* lut, act_t* image, uint8_t* mask, int B, int Ho, int Wo, void* stream) {
+  NASSEG_REQUIRE(B > 0 && B <= 65535 && Ho > 0 && Wo > 0 && src_bytes > 0, "augment: bad shape");
+  NASSEG_REQUIRE((int64_t)9 * (Ho + Wo) < ((int64_t)1 << 31), "augment: output too large");
+  const int64_t npix = (int64_t)Ho * Wo;
+  NASSEG_REQUIRE(cdiv64(npix, 256) < ((int64_t)1 << 31), "augment: output too large");
+  hipLaunchKernelGGL(augment_kernel, dim3((unsigned)cdiv64(npix, 256), B), dim3(256), 0, (hipStream_t)stream, src,
+                     src_bytes, desc, taps, lut, image, mask, Ho, Wo);
+  NASSEG_LAUNCH_CHECK("augment");
+  return NASSEG_OK;
+}
+
+}  // extern "C"

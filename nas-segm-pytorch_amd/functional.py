@@ -2611,6 +2611,25 @@ def gather_rows(src, idx, out=None):
     return out
 
 
+def augment(src, desc, taps, lut, Ho, Wo):
+    """The sample pipelines of data/datasets.py for one packed batch (data/device.py plans and packs it): uint8
+    ``src`` (the source windows), int64 ``desc`` [B][8], int32 ``taps`` [B][9 (Ho + Wo)] and the Normalise table
+    ``lut`` [3][256] of the output dtype (fp32 or bf16) -> (image B x 3 x Ho x Wo channels_last, mask uint8
+    B x Ho x Wo); one nasseg_augment launch (include/nasseg.h)."""
+    require_device(src, desc, taps, lut)
+    B = desc.shape[0] if desc.dim() == 2 else 0
+    if (src.dtype != torch.uint8 or desc.dtype != torch.int64 or taps.dtype != torch.int32
+            or lut.dtype not in (torch.float32, torch.bfloat16) or src.dim() != 1 or B == 0
+            or tuple(desc.shape) != (B, 8) or tuple(taps.shape) != (B, 9 * (Ho + Wo)) or tuple(lut.shape) != (3, 256)
+            or not all(t.is_contiguous() for t in (src, desc, taps, lut))):
+        raise NassegError("augment: bad packed batch")
+    image = torch.empty((B, 3, Ho, Wo), device=src.device, dtype=lut.dtype, memory_format=torch.channels_last)
+    mask = torch.empty((B, Ho, Wo), device=src.device, dtype=torch.uint8)
+    lib.call(_k("nasseg_augment", lut), ptr(src), src.numel(), ptr(desc), ptr(taps), ptr(lut), ptr(image),
+             ptr(mask), B, Ho, Wo, current_stream())
+    return image, mask
+
+
 def argmax_confusion(logits, gt, n_classes, cm=None, out_size=None, return_preds=False):
     """Fused bilinear up-sampling -> argmax -> uint8 -> confusion-matrix update.
 
