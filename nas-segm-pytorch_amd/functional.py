@@ -7,6 +7,7 @@ no ATen compute op runs on the hot path.  Tensors keep the reference's NCHW
 *shape* but live in ``torch.channels_last`` memory, which is the NHWC layout the
 kernels address directly.
 """
+import collections
 import ctypes
 import os
 import weakref
@@ -69,6 +70,11 @@ def _ws(like, n):
 
 def _vec(like, n):
     return torch.empty((int(n),), device=like.device, dtype=torch.float32)
+
+
+def _bn_parts(stats, n):
+    """(mean, invstd, scale, shift): the views of a statistics vector mean | invstd | scale | shift of n channels"""
+    return stats[0:n], stats[n:2 * n], stats[2 * n:3 * n], stats[3 * n:]
 
 
 # BatchNorm backward whose apply kernel adds up the partial rows of its sums itself (nasseg_bn_bwd_apply_rows): on the
@@ -323,7 +329,7 @@ def _pw_bwd_slabs(kind, cur, z, w, stride, pad, need_dw, need_dx, i, ops):
         return 0
     if (cur.numel() + z.numel()) * cur.element_size() <= _PW_BWD_MIN_BYTES:
         return 0
-    if K % 4 == 0 and i > 0 and ops[i - 1][4] and not (N >= K and K <= 64):
+    if K % 4 == 0 and i > 0 and ops[i - 1].has_bn and not (N >= K and K <= 64):
         # bn_prev in _ConvChain.backward: the producer's BatchNorm backward goes with the backward-data
         # kernel (statistics epilogue) - except where this conv widens (N >= K): there the one kernel plus
         # a bn_bwd_reduce pass over the K-channel gradient moves fewer bytes (4K + 2N per pixel) than
@@ -345,7 +351,7 @@ def _dw_bwd_rows(kind, cur, z, w, stride, pad, dil, need_dw, need_dx, i, ops):
     """> 0: this depthwise op's whole backward runs as ONE kernel, nasseg_dwconv_bwd_bn (the value
     is its number of partial rows): 3x3, between two BatchNorms of the chain (the previous op has
     one - InvertedResidual's expansion), both gradients wanted, a large map."""
-    if not (FUSE_DW_BWD and kind == "dw" and need_dw and need_dx and i > 0 and ops[i - 1][4]):
+    if not (FUSE_DW_BWD and kind == "dw" and need_dw and need_dx and i > 0 and ops[i - 1].has_bn):
         return 0
     if (cur.numel() + z.numel()) * cur.element_size() <= _DW_BWD_MIN_BYTES:
         return 0
@@ -914,546 +920,551 @@ def _irdw_ok(ops, i, weights, cur, pend, needs_in_grad, need_w, training):
             and lib.query("nasseg_dwconv_bwd_bn_rows", B, N, H, W, 3, stride2, 1, 1) > 0)
 
 
+# A chain's config (conv_chain): in_act0 = activation applied to the input on load, one _ChainOp per conv, the CALLER's
+# grad mode, pool = (3, stride, 1) or None, defer = return the last BatchNorm unapplied (Pending), in_pact = activation
+# of a Pending input (None: a plain one; else its statistics vector rides behind the per-op tensors)
+_ChainCfg = collections.namedtuple("_ChainCfg", "in_act0 ops grad_mode pool defer in_pact")
+_ChainOp = collections.namedtuple("_ChainOp", "kind stride pad dil has_bn act training momentum eps")
+# What an op saves for backward: input x (read through the prologue psc, psh), raw conv output z, BatchNorm statistics,
+# weight and the weight packed for backward-data; and, in ctx.meta, (form, prologue activation) with form: plain, the
+# depthwise half of a SepConv stage, InvertedResidual's expansion never stored (z None) and the depthwise conv over it
+_OpSaved = collections.namedtuple("_OpSaved", "x psc psh z stats w wb")
+OP_PLAIN, OP_SEPCONV_DW, OP_IR_PW, OP_IR_DW = range(4)
+
+
+class _ChainForward(object):
+    """One chain's forward by the forms of DESIGN.md "Forward, per op": irdw, conv (or a SepConv stage), tail - each
+    takes ``cur`` and its prologue ``pend`` = (scale, shift, act), returns the next and records one _OpSaved per op"""
+
+    __slots__ = ("cfg", "prm", "w", "wp", "wb", "needs_grad", "saved", "meta", "s")
+
+    def __init__(self, cfg, x, tensors, needs_grad, need_x):
+        ops = cfg.ops
+        self.cfg, self.needs_grad, self.s, self.saved, self.meta = cfg, needs_grad, current_stream(), [], []
+        self.prm = [tensors[k:k + 6] for k in range(0, 6 * len(ops), 6)]  # (weight, gamma, beta, rm, rv, nbt)
+        # every layout of every weight of the chain (forward now, backward-data later) is produced by one launch
+        self.w = [p[0].contiguous() for p in self.prm]
+        items = [(w, "dw" if op.kind == "dw" else "fwd") for op, w in zip(ops, self.w)]
+        bwd_slot = [None] * len(ops)
+        for i, (op, w) in enumerate(zip(ops, self.w)):
+            if not needs_grad or (i == 0 and not need_x):
+                continue
+            if op.kind == "dw":
+                if op.stride == 1 and op.dil * (w.shape[-1] - 1) - op.pad >= 0:
+                    bwd_slot[i] = len(items)
+                    items.append((w, "dwflip"))
+                else:
+                    bwd_slot[i] = i  # transposed gather reads the forward layout
+            else:
+                # (a chain whose producer is a BatchNorm uses the fused transposed kernel)
+                fused = ((i > 0 and ops[i - 1].has_bn) or (i == 0 and cfg.in_act0)) and w.shape[1] % 4 == 0
+                bwd_slot[i] = len(items)
+                items.append((w, 1 if fused else _dense_dgrad_form(w, op.stride, op.pad, op.dil)))
+        packed = _pack_many(x, items)
+        self.wp = packed[:len(ops)]
+        self.wb = [None if j is None else packed[j] for j in bwd_slot]
+
+    def keep(self, i, form, x, pro, z, stats):
+        """op i's record for backward; pro: the prologue (scale, shift, act) its input was read through, or None"""
+        if self.needs_grad:
+            psc, psh, pact = pro if pro is not None else (None, None, ACT_NONE)
+            self.saved.append(_OpSaved(x, psc, psh, z, stats, self.w[i], self.wb[i]))
+            self.meta.append((form, pact))
+
+    def irdw(self, i, cur, pend):
+        """ops i, i + 1: InvertedResidual's pointwise expansion + BatchNorm + activation and its 3x3 depthwise conv +
+        BatchNorm with the expanded map never stored (csrc/irdw.hip).  Returns (cur, pend, stats) after op i + 1."""
+        op, op2 = self.cfg.ops[i], self.cfg.ops[i + 1]
+        _, gamma, beta, rm, rv, nbt = self.prm[i]
+        _, gamma2, beta2, rm2, rv2, nbt2 = self.prm[i + 1]
+        w = self.w[i]
+        B, K, H, W = cur.shape
+        N = w.shape[0]
+        psc, psh, pact = pend if pend is not None else (None, None, ACT_NONE)
+        st1 = _vec(cur, 4 * N)
+        mean1, invstd1, scale1, shift1 = _bn_parts(st1, N)
+        wsm = _ws(cur, lib.query("nasseg_irdw_stats_workspace", K))
+        lib.call(_k("nasseg_irdw_stats", cur), ptr(cur), ptr(w), ptr(psc), ptr(psh), pact, B, H, W, K, N,
+                 float(op.eps), float(op.momentum), ptr(gamma), ptr(beta), ptr(mean1), ptr(invstd1), ptr(scale1),
+                 ptr(shift1), ptr(rm), ptr(rv), ptr(nbt), ptr(wsm), self.s)
+        self.keep(i, OP_IR_PW, cur, pend, None, st1)
+        Ho, Wo = conv_out_size(H, 3, op2.stride, 1, 1), conv_out_size(W, 3, op2.stride, 1, 1)
+        z2 = _new(cur, B, N, Ho, Wo)
+        st2 = _vec(cur, 4 * N)
+        rows2 = lib.query("nasseg_irdw_rows", B, H, W, K, N, op2.stride, 0)
+        part2 = _ws(cur, (rows2 + 64) * 2 * N)
+        lib.call(_k("nasseg_irdw_fwd", cur), ptr(cur), ptr(w), ptr(self.wp[i + 1]), ptr(z2), ptr(psc), ptr(psh),
+                 pact, ptr(scale1), ptr(shift1), op.act, B, H, W, K, N, Ho, Wo, op2.stride, ptr(part2), self.s)
+        mean2, invstd2, scale2, shift2 = _bn_parts(st2, N)
+        lib.call("nasseg_bn_finalize", ptr(part2), rows2, B * Ho * Wo, N, float(op2.eps), float(op2.momentum),
+                 ptr(gamma2), ptr(beta2), ptr(mean2), ptr(invstd2), ptr(scale2), ptr(shift2), ptr(rm2), ptr(rv2),
+                 ptr(nbt2), self.s)
+        # (its input None: the depthwise conv's input does not exist - backward rebuilds it from op i's)
+        self.keep(i + 1, OP_IR_DW, None, (scale1, shift1, op.act), z2, st2)
+        return z2, (scale2, shift2, op2.act), st2
+
+    def conv(self, i, cur, pend, res, stage=None):
+        """op i with its BatchNorm statistics, eval parameters or folded epilogue (which consumes res) - or, stage =
+        i - 1, a SepConv stage's pointwise half (csrc/sepconv.hip; cur, pend: the depthwise half's).
+        Returns cur, pend, stats, res."""
+        op, w = self.cfg.ops[i], self.w[i]
+        _, gamma, beta, rm, rv, nbt = self.prm[i]
+        B, K, H, W = cur.shape
+        last = i == len(self.cfg.ops) - 1
+        dpend = None
+        if stage is not None:  # (geometry of the stage's depthwise output; the prologue belongs to that half)
+            dop, dk = self.cfg.ops[stage], self.w[stage].shape[-1]
+            H, W = (conv_out_size(d, dk, dop.stride, dop.pad, dop.dil) for d in (H, W))
+            dpend, pend = pend, None
+        if op.kind == "dw":  # (pro_ok: the kernel applies pend as it loads; stats_ok: its epilogue emits statistics)
+            N, kh, kw = K, w.shape[-1], w.shape[-1]
+            if w.shape[0] != K or w.shape[1] != 1:
+                raise NassegError("depthwise weight {} does not match C={}".format(tuple(w.shape), K))
+            stats_ok = bool(lib.query("nasseg_dwconv_strip_ok", kh, op.stride, op.dil))
+            pro_ok = stats_ok or (pend is not None and pend[0] is None and pend[2] == ACT_RELU)
+        else:
+            N, Kw, kh, kw = w.shape
+            if Kw != K:
+                raise NassegError("conv weight {} does not match C_in={}".format(tuple(w.shape), K))
+            pro_ok = kh == 1 and kw == 1 and op.stride == 1 and op.pad == 0 and K % 4 == 0 and N % 4 == 0
+            stats_ok = N % 4 == 0
+        Ho, Wo = conv_out_size(H, kh, op.stride, op.pad, op.dil), conv_out_size(W, kw, op.stride, op.pad, op.dil)
+        if Ho <= 0 or Wo <= 0:
+            raise NassegError("conv output would be empty")
+        if pend is not None and not pro_ok:
+            cur = (_affine_act(cur, pend[0], pend[1], None, pend[2]) if pend[0] is not None
+                   else _axpby(cur, None, None, None, pend[2]))
+            pend = None
+        psc, psh, pact = pend if pend is not None else (None, None, ACT_NONE)
+        M = B * Ho * Wo
+        z = _new(cur, B, N, Ho, Wo)
+        fold = (op.has_bn and not op.training and not self.needs_grad
+                and not (op.kind == "dw" and last and res is not None))
+        stats, part, nblk = None, None, 0
+        if op.has_bn:
+            if op.training and M <= 1:
+                raise ValueError("Expected more than 1 value per channel when training, got input "
+                                 "size {}".format((B, N, Ho, Wo)))
+            stats = _vec(cur, 4 * N)
+            mean, invstd, scale, shift = _bn_parts(stats, N)
+            if not op.training:
+                lib.call("nasseg_bn_eval_params", N, float(op.eps), ptr(gamma), ptr(beta), ptr(rm),
+                         ptr(rv), ptr(mean), ptr(invstd), ptr(scale), ptr(shift), self.s)
+            elif stats_ok:
+                if stage is not None:
+                    nblk = lib.query("nasseg_sepconv_blocks", B, K, Ho, Wo, N, dk, dop.stride, dop.dil)
+                elif op.kind == "dw":
+                    nblk = lib.query("nasseg_dwconv_stats_blocks", B, N, Ho, Wo, kh, op.stride, op.dil)
+                else:
+                    nblk = lib.query("nasseg_conv_fwd_stats_rows", B, Ho, Wo, N, K, kh, kw, op.stride, op.pad, op.dil)
+                part = _ws(cur, (nblk + 64) * 2 * N)
+        # inference: BatchNorm (+ act, + residual) folded into the conv's epilogue
+        o_sc, o_sh, o_act = (scale, shift, op.act) if fold else (None, None, ACT_NONE)
+        o_res = res if (fold and last) else None
+        if stage is not None:
+            zdw = _new(cur, B, K, Ho, Wo) if self.needs_grad else None
+            dsc, dsh, dact = dpend if dpend is not None else (None, None, ACT_NONE)
+            lib.call(_k("nasseg_sepconv_fwd", cur), ptr(cur), ptr(self.wp[stage]), ptr(w), ptr(zdw), ptr(z), ptr(dsc),
+                     ptr(dsh), dact, ptr(o_sc), ptr(o_sh), o_act, B, cur.shape[2], cur.shape[3], K, Ho, Wo, N,
+                     dk, dop.stride, dop.pad, dop.dil, ptr(part), self.s)
+            self.keep(stage, OP_SEPCONV_DW, cur, dpend, zdw, None)
+            cur = zdw
+        elif op.kind == "dw":
+            lib.call(_k("nasseg_dwconv", cur), ptr(cur), ptr(self.wp[i]), ptr(z), ptr(psc), ptr(psh), pact, ptr(o_sc),
+                     ptr(o_sh), o_act, B, H, W, K, Ho, Wo, kh, op.stride, op.pad, op.dil, 0, ptr(part), self.s)
+        else:
+            lib.call(_k("nasseg_conv_fwd", cur), ptr(cur), K, ptr(self.wp[i]), ptr(z), N, ptr(psc), ptr(psh), pact,
+                     ptr(o_sc), ptr(o_sh), o_act, ptr(o_res), N, B, H, W, K, Ho, Wo, N, kh, kw,
+                     op.stride, op.pad, op.dil, 0, ptr(part), self.s)
+        self.keep(i, OP_PLAIN, cur, pend, z, stats)
+        if fold or not op.has_bn:
+            return z, None, stats, (None if (fold and last) else res)
+        if op.training and part is not None:
+            lib.call("nasseg_bn_finalize", ptr(part), nblk, M, N, float(op.eps), float(op.momentum),
+                     ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(scale), ptr(shift),
+                     ptr(rm), ptr(rv), ptr(nbt), self.s)
+        elif op.training:
+            ws = _ws(z, lib.query("nasseg_colred_workspace", 1, M, N))
+            lib.call(_k("nasseg_bn_stats", z), ptr(z), N, M, N, float(op.eps), float(op.momentum),
+                     ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(scale), ptr(shift),
+                     ptr(rm), ptr(rv), ptr(nbt), ptr(ws), self.s)
+        return z, (scale, shift, op.act), stats, res
+
+    def tail(self, cur, pend, stats, res):
+        """(y, statistics of a deferred tail, pooling indices, pooling applied the BatchNorm).  Pool (layer_factory.py:
+        161-178): 3x3 max pooling applies a pending last BatchNorm as it loads the raw conv output."""
+        if self.cfg.pool is None:
+            if pend is None:
+                return (_axpby(cur, res, None, None) if res is not None else cur), None, None, False
+            if self.cfg.defer and res is None and pend[0] is not None:
+                # deferred tail: the consumer applies act(scale*z + shift) as it loads (Pending below); what
+                # comes back in backward is still the gradient w.r.t. the BatchNorm's activated output
+                return cur, stats, None, False
+            return _affine_act(cur, pend[0], pend[1], res, pend[2]), None, None, False
+        pk, ps, pp = self.cfg.pool
+        B, N, Hc, Wc = cur.shape
+        Hp, Wp = conv_out_size(Hc, pk, ps, pp, 1), conv_out_size(Wc, pk, ps, pp, 1)
+        if Hp <= 0 or Wp <= 0:
+            raise NassegError("max pooling output would be empty")
+        psc, psh = (pend[0], pend[1]) if pend is not None else (None, None)
+        if (res is not None or (pend is not None and pend[2] != ACT_NONE) or pk != 3 or pp != 1
+                or ps not in (1, 2)):
+            raise NassegError("conv_chain: the pooled tail serves conv + BatchNorm -> 3x3 max pooling only")
+        y = _new(cur, B, N, Hp, Wp)
+        pool_idx = torch.empty((B, Hp, Wp, N), device=cur.device, dtype=torch.uint8) if self.needs_grad else None
+        lib.call(_k("nasseg_maxpool_bn_fwd", cur), ptr(cur), ptr(psc), ptr(psh), ptr(y), ptr(pool_idx), B, Hc,
+                 Wc, N, Hp, Wp, ps, pp, self.s)
+        return y, None, pool_idx, pend is not None
+
+
+# From op i's backward to op i - 1's: gradient g w.r.t. op i - 1's output, the rows of its BatchNorm-backward sums if
+# the kernel that made g emitted them, masked = g carries its act', dres = the residual's gradient still to return
+# (None once an epilogue added it into dx), in_masked = dx carries in_act0'.  _BnBwd: act = the mask g still lacks.
+_Flow = collections.namedtuple("_Flow", "g rows masked dres in_masked")
+_BnBwd = collections.namedtuple("_BnBwd", "scale shift mean invstd sums training act")
+# The forms of an op's backward, DESIGN.md "Backward, per op" (in its order of precedence)
+BWD_IRDW, BWD_DW_BN, BWD_FLAT_BN, BWD_PW_BN, BWD_WGRAD_BN, BWD_APPLY = range(6)
+
+
+class _ChainBackward(collections.namedtuple("_ChainBackward", "ops recs meta need in_act0 fuse_res s")):
+    """One chain's backward, op by op (op): plan picks the form, bn_head runs the BatchNorm backward, then irdw, dw_bn,
+    flat_bn, pw_bn or generic take the _Flow from op i + 1 and return (weight gradient, _Flow for op i - 1)"""
+
+    def plan(self, i, need_dw, need_dx):
+        """(form, its rows or slabs) of op i, which has a BatchNorm"""
+        op, r, (form, pact) = self.ops[i], self.recs[i], self.meta[i]
+        if form == OP_IR_DW:
+            return BWD_IRDW, 1
+        if form == OP_IR_PW:  # (the pointwise backward rebuilds the expansion it never stored: z == NULL)
+            B, K, H, W = r.x.shape
+            return BWD_PW_BN, lib.query("nasseg_conv_pw_bwd_slabs", B, H, W, K, r.w.shape[0])
+        nsl = _pw_bwd_slabs(op.kind, r.x, r.z, r.w, op.stride, op.pad, need_dw, need_dx, i, self.ops)
+        if nsl > 0:
+            return BWD_PW_BN, nsl
+        rows = _dw_bwd_rows(op.kind, r.x, r.z, r.w, op.stride, op.pad, op.dil, need_dw, need_dx, i, self.ops)
+        if rows > 0:
+            return BWD_DW_BN, rows
+        if _flat_bn_ok(op.kind, need_dw, need_dx, r.psc, r.psh, pact, r.w, r.w.shape[0], r.z):
+            return BWD_FLAT_BN, 0
+        if need_dw and _wgrad_bn_ok(op.kind, r.x, r.z, r.w, op.stride, op.pad, op.dil):
+            return BWD_WGRAD_BN, 0
+        return BWD_APPLY, 0
+
+    def bn_head(self, i, fl, plan):
+        """op i's BatchNorm backward sums (from the rows that came with g, or reduced) and, BWD_APPLY, dz: returns
+        (_BnBwd, dz, dgamma, dbeta)"""
+        op, r = self.ops[i], self.recs[i]
+        N = r.w.shape[0]
+        M = r.x.shape[0] * r.x.shape[2] * r.x.shape[3] if r.z is None else r.z.shape[0] * r.z.shape[2] * r.z.shape[3]
+        mean, invstd, scale, shift = _bn_parts(r.stats, N)
+        sums = _vec(fl.g, 2 * N)
+        act_left = ACT_NONE if (fl.rows is not None or fl.masked) else op.act  # (the mask still to be applied to g)
+        # g arrived masked with its per-workgroup {sum g, sum g*xhat} rows: few enough for the apply kernel to add
+        # them up itself (lazy_rows), or summed here - else the sums by a reduction (or its rows, for the apply)
+        lazy_rows = fl.rows if (fl.rows is not None and plan == BWD_APPLY and _rows_small(fl.rows[1], N)) else None
+        if fl.rows is not None and lazy_rows is None:
+            lib.call("nasseg_rows_sum", ptr(fl.rows[0]), fl.rows[1], 2 * N, ptr(sums), self.s)
+        elif fl.rows is None:
+            lazy_rows = _bn_bwd_reduce(fl.g, r.z, scale, shift, mean, invstd, act_left, sums, M, N, plan == BWD_APPLY)
+        dgamma = sums[N:2 * N] if self.need[3 + 6 * i + 1] else None
+        dbeta = sums[0:N] if self.need[3 + 6 * i + 2] else None
+        dz = None
+        if plan == BWD_APPLY:
+            dz = _bn_bwd_apply(fl.g, r.z, scale, shift, mean, invstd, sums, M, N, op.training, act_left,
+                               torch.empty_like(r.z), lazy_rows)
+        return _BnBwd(scale, shift, mean, invstd, sums, op.training, act_left), dz, dgamma, dbeta
+
+    def producer_bn(self, i, K):
+        """(z, scale, shift, mean, invstd, act) of the chain's BatchNorm that produced op i's input, for the epilogue of
+        op i's backward-data - at op 0 after an activation on load (DilConv, pre_clf) an identity BatchNorm: act'"""
+        if i > 0 and self.ops[i - 1].has_bn and K % 4 == 0:
+            p = self.recs[i - 1]
+            mean, invstd, scale, shift = _bn_parts(p.stats, K)
+            return p.z, scale, shift, mean, invstd, self.ops[i - 1].act
+        if i == 0 and self.in_act0 and K % 4 == 0:
+            x = self.recs[0].x
+            if self.ops[0].kind == "dw":
+                one, zero = _identity_vectors(x, K)
+                return x, one, zero, zero, one, self.in_act0
+            return x, None, None, None, None, self.in_act0  # mask-only epilogue
+        return None
+
+    def irdw(self, i, fl, bn):
+        """the 3x3 depthwise conv behind a rebuilt expansion: nasseg_irdw_bwd with z1 = W1 x from op i - 1"""
+        op, r = self.ops[i], self.recs[i]
+        x_in, xpsc, xpsh, _, st1, w1, _ = self.recs[i - 1]
+        Bc, K1, H, W = x_in.shape
+        _, K, Ho, Wo = r.z.shape
+        mean1, invstd1, scale1, shift1 = _bn_parts(st1, K)
+        rows = lib.query("nasseg_irdw_rows", Bc, H, W, K1, K, op.stride, 1)
+        dwt = torch.empty_like(r.w)
+        ws = _ws(fl.g, rows * 9 * K)
+        part = _ws(fl.g, (rows + 64) * 2 * K)
+        g_in = _new(fl.g, Bc, K, H, W)
+        lib.call(_k("nasseg_irdw_bwd", x_in), ptr(x_in), ptr(w1), ptr(fl.g), ptr(r.z), ptr(r.wb), int(op.stride == 1),
+                 ptr(g_in), _finish_wgrad(ws, dwt, 9, K, 1, 0), ptr(ws), ptr(xpsc), ptr(xpsh), self.meta[i - 1][1],
+                 ptr(scale1), ptr(shift1), ptr(mean1), ptr(invstd1), self.ops[i - 1].act,
+                 ptr(bn.scale), ptr(bn.shift), ptr(bn.mean), ptr(bn.invstd), ptr(bn.sums), int(bn.training), bn.act,
+                 Bc, H, W, K1, K, Ho, Wo, op.stride, ptr(part), self.s)
+        return dwt, _Flow(g_in, (part, rows), False, fl.dres, fl.in_masked)
+
+    def dw_bn(self, i, fl, bn, rows):
+        """3x3 depthwise conv between two BatchNorms of the chain, its whole backward in one pass (csrc/dwconv.hip):
+        BatchNorm backward on load, weight gradient, masked input gradient + the sums of the BatchNorm in front"""
+        op, r = self.ops[i], self.recs[i]
+        Bc, K, H, W = r.x.shape
+        _, _, Ho, Wo = r.z.shape
+        zp, psc_, psh_, pmu_, pis_, pact_ = self.producer_bn(i, K)
+        dwt = torch.empty_like(r.w)
+        ws = _ws(r.x, rows * 9 * K)
+        part = _ws(r.x, (rows + 64) * 2 * K)
+        g_in = _new(r.x, Bc, K, H, W)
+        lib.call(_k("nasseg_dwconv_bwd_bn", r.x), ptr(r.x), ptr(fl.g), ptr(r.z), ptr(r.wb), int(op.stride == 1),
+                 ptr(g_in), _finish_wgrad(ws, dwt, 9, K, 1, 0), ptr(ws), ptr(psc_), ptr(psh_), ptr(pmu_),
+                 ptr(pis_), pact_, ptr(bn.scale), ptr(bn.shift), ptr(bn.mean), ptr(bn.invstd), ptr(bn.sums),
+                 int(bn.training), bn.act, Bc, H, W, K, Ho, Wo, 3, op.stride, op.pad, op.dil, ptr(part), self.s)
+        return dwt, _Flow(g_in, (part, rows), False, fl.dres, fl.in_masked)
+
+    def flat_bn(self, i, fl, bn):
+        """the stem (small-K k x k conv, no gradient for the image): BatchNorm backward on load in the
+        weight-gradient kernel, dz never written (nasseg_conv_wgrad_bn_flat)"""
+        op, r = self.ops[i], self.recs[i]
+        Bc, K, H, W = r.x.shape
+        N, _, kh, kw = r.w.shape
+        _, _, Ho, Wo = r.z.shape
+        dwt = torch.empty_like(r.w)
+        ws = _ws(r.x, lib.query("nasseg_conv_wgrad_workspace", Bc, Ho, Wo, N, K, kh, kw))
+        lib.call(_k("nasseg_conv_wgrad_bn_flat", r.x), ptr(r.x), K, ptr(fl.g), N, ptr(r.z), N,
+                 _finish_wgrad(ws, dwt, kh * kw, N, K, 1), ptr(ws), ptr(bn.scale), ptr(bn.shift), ptr(bn.mean),
+                 ptr(bn.invstd), ptr(bn.sums), int(bn.training), bn.act, Bc, H, W, K, Ho, Wo, N, kh, kw,
+                 op.stride, op.pad, op.dil, self.s)
+        return dwt, _Flow(None, None, False, fl.dres, fl.in_masked)
+
+    def pw_bn(self, i, fl, bn, nsl):
+        """pointwise conv + BatchNorm in ONE kernel, dz never written (csrc/conv_pwbwd.hip).  Op 0 after an activation
+        on load, or a widening conv behind a BatchNorm of the chain (_pw_bwd_slabs): dx is masked with act' from the
+        ACTIVATED input tile and, K <= 64, comes with the per-slab sums of that BatchNorm's backward (dx_stats)."""
+        r, pact = self.recs[i], self.meta[i][1]
+        Bc, K, H, W = r.x.shape
+        N = r.w.shape[0]
+        dwt = torch.empty_like(r.w)
+        ws = _ws(r.x, nsl * N * K)
+        g_in = _new(r.x, Bc, K, H, W)
+        behind_bn = i > 0 and self.ops[i - 1].has_bn
+        dx_act = pact if ((i == 0 and self.in_act0 and r.psc is None and r.psh is None) or behind_bn) else ACT_NONE
+        part = pmu_ = pis_ = None
+        skip_g = fl.dres if (self.fuse_res and i == 0 and K % 4 == 0) else None  # (x is also the block's skip)
+        if behind_bn and K <= 64:
+            pmu_, pis_ = _bn_parts(self.recs[i - 1].stats, K)[:2]
+            part = _ws(r.x, (nsl + 64) * 2 * K)
+        # (z only where the kernel loads it: where it rebuilds z = W x the argument is NULL - an explicit
+        #  contract instead of a pointer the kernel ignores, and NULL is also what says "never stored")
+        z_arg = r.z if (r.z is not None and lib.query("nasseg_conv_pw_bwd_reads_z", Bc, H, W, K, N)) else None
+        lib.call(_k("nasseg_conv_pw_bwd_bn", r.x), ptr(r.x), ptr(fl.g), ptr(z_arg), ptr(r.wb), ptr(g_in),
+                 _finish_wgrad(ws, dwt, 1, N, K, 0), ptr(ws), ptr(r.psc), ptr(r.psh), pact, dx_act,
+                 ptr(bn.scale), ptr(bn.shift), ptr(bn.mean), ptr(bn.invstd), ptr(bn.sums), int(bn.training), bn.act,
+                 Bc, H, W, K, N, ptr(pmu_), ptr(pis_), ptr(part), ptr(skip_g), self.s)
+        return dwt, _Flow(g_in, (part, nsl) if part is not None else None, behind_bn,
+                          fl.dres if skip_g is None else None, bool(dx_act) and i == 0)
+
+    def generic(self, i, fl, bn, dz, need_dw, need_dx):
+        """a depthwise or dense conv: weight gradient (bn given: with the BatchNorm backward on load, which leaves dz)
+        and backward-data with the producer's BatchNorm in its epilogue - or, op 0, the residual's gradient"""
+        op, r, pact = self.ops[i], self.recs[i], self.meta[i][1]
+        Bc, K, H, W = r.x.shape
+        _, N, Ho, Wo = r.z.shape
+        kh, kw = r.w.shape[2], r.w.shape[3]
+        bn_prev = self.producer_bn(i, K) if need_dx else None
+        dw = op.kind == "dw"
+        geom = ((Bc, H, W, K, Ho, Wo, kh, op.stride, op.pad, op.dil) if dw
+                else (Bc, H, W, K, Ho, Wo, N, kh, kw, op.stride, op.pad, op.dil))
+        dwt = None
+        if bn is not None:
+            dwt, dz = _wgrad_bn(op.kind, r.x, fl.g, r.z, r.w, r.psc, r.psh, pact, bn, geom if dw else (Bc, H, W, K, N))
+        elif need_dw:
+            dwt = (_dw_wgrad if dw else _dense_wgrad)(r.x, dz, r.w, r.psc, r.psh, pact, geom)
+        if not need_dx:
+            return dwt, _Flow(None, None, False, fl.dres, fl.in_masked)
+        if dw:
+            g, rows = _dw_backward_data(dz, r.wb, kh, (Bc, K, H, W), op.stride, op.pad, op.dil, bn_prev)
+            return dwt, _Flow(g, rows, False, fl.dres, fl.in_masked)
+        if bn_prev is not None:
+            g = _new(r.x, Bc, K, H, W)
+            zp, psc_, psh_, pmu_, pis_, pact_ = bn_prev
+            pw1 = kh == 1 and kw == 1 and op.stride == 1 and op.pad == 0
+            nb = lib.query("nasseg_conv_fwd_stats_blocks", Bc, H, W, K, N, 2 * int(pw1)) if pmu_ is not None else 0
+            part = _ws(r.x, (nb + 64) * 2 * K) if nb else None
+            lib.call(_k("nasseg_conv_bwd_data_bn", dz), ptr(dz), N, ptr(r.wb), ptr(g), K, ptr(zp), K,
+                     ptr(psc_), ptr(psh_), ptr(pmu_), ptr(pis_), pact_, Bc, Ho, Wo, N, H, W,
+                     K, kh, kw, op.stride, op.pad, op.dil, ptr(part), self.s)
+            return dwt, _Flow(g, (part, nb), False, fl.dres, fl.in_masked)
+        res = fl.dres if (self.fuse_res and i == 0) else None  # (added in the epilogue: it is inside dx)
+        g = _dense_backward_data(dz, r.wb, _dense_dgrad_form(r.w, op.stride, op.pad, op.dil), (Bc, K, H, W), N, kh,
+                                 kw, op.stride, op.pad, op.dil, res)
+        return dwt, _Flow(g, None, False, fl.dres if res is None else None, fl.in_masked)
+
+    def op(self, i, fl):
+        """op i's backward: ((dw, dgamma, dbeta), _Flow for op i - 1); its g None ends the chain's backward"""
+        need_dw, need_dx = self.need[3 + 6 * i], i > 0 or self.need[1]
+        go_on = need_dw or need_dx
+        bn, dz, dgamma, dbeta, plan, n = None, fl.g, None, None, BWD_APPLY, 0
+        if self.ops[i].has_bn:
+            plan, n = self.plan(i, need_dw, need_dx) if go_on else (None, 0)
+            bn, dz, dgamma, dbeta = self.bn_head(i, fl, plan)
+        if not go_on:
+            return (None, dgamma, dbeta), fl._replace(g=None)
+        if plan == BWD_IRDW:
+            dwt, fl = self.irdw(i, fl, bn)
+        elif plan == BWD_DW_BN:
+            dwt, fl = self.dw_bn(i, fl, bn, n)
+        elif plan == BWD_FLAT_BN:
+            dwt, fl = self.flat_bn(i, fl, bn)
+        elif plan == BWD_PW_BN:
+            dwt, fl = self.pw_bn(i, fl, bn, n)
+        else:
+            dwt, fl = self.generic(i, fl, bn if plan == BWD_WGRAD_BN else None, dz, need_dw, need_dx)
+        return (dwt, dgamma, dbeta), fl
+
+
 class _ConvChain(torch.autograd.Function):
     """A run of convolutions (dense on the MFMA path or depthwise), each optionally followed
     by BatchNorm (+ReLU/ReLU6), as ONE autograd node in which a normalised activation that
     only feeds the next convolution is never written: the producer emits the raw conv output
     z plus the BatchNorm statistics (epilogue), the consumer applies act(scale*z + shift) as
     it loads its operand (prologue), backward recomputes the same on load.  Only the chain's
-    final output is materialised (with the block's residual add fused in).
-
-    cfg = (in_act0, ops); ops[i] = (kind, stride, pad, dil, has_bn, act, training, momentum, eps)
-    with kind 'dense' | 'dw'; tensors = per op (weight, gamma, beta, running_mean,
-    running_var, num_batches_tracked) with None where absent.
-    """
+    final output is materialised (with the block's residual add fused in).  cfg: a _ChainCfg;
+    tensors: per op (weight, gamma, beta, running_mean, running_var, num_batches_tracked), None
+    where absent, then the statistics vector of a Pending input (or None)."""
 
     @staticmethod
     def forward(ctx, cfg, x, residual, *tensors):
-        in_act0, ops = cfg[:2]
         res_is_x = residual is not None and residual is x  # (InvertedResidual: the block's input is its skip)
         x = _cl(x)
-        s = current_stream()
         # the statistics vector a deferred tail hands out never has a gradient: without this autograd would
         # materialise a zero "gradient" for it in every backward (one fill launch per chain and step)
         ctx.set_materialize_grads(False)
         # (under no_grad ctx.needs_input_grad still reports the parameters' requires_grad flags: nothing
-        #  will ever call backward then, and inference may fold every BatchNorm into its conv's epilogue.
-        #  The grad mode is the CALLER's - cfg[2]: inside forward() autograd has switched it off)
-        needs_grad = cfg[2] and any(ctx.needs_input_grad)
+        #  will ever call backward then, and inference may fold every BatchNorm into its conv's epilogue)
+        needs_grad = cfg.grad_mode and any(ctx.needs_input_grad)
         res = _cl(residual) if residual is not None else None
-        cur, pend = x, ((None, None, in_act0) if in_act0 else None)
-        saved, meta = [], []
-        n_ops = len(ops)
-        in_pending = len(cfg) > 5 and cfg[5] is not None
-        if in_pending:
-            # the input is another chain's Pending: its BatchNorm + activation are op 0's prologue (tensors[-1]: the
-            # producer's statistics vector); what backward returns for x is the gradient w.r.t. the ACTIVATED
-            # input - exactly what a plain backward-data of op 0 computes
-            K0 = x.shape[1]
-            in_st = tensors[6 * n_ops]
-            pend = (in_st[2 * K0:3 * K0], in_st[3 * K0:], cfg[5])
-        # every layout of every weight of the chain (forward now, backward-data later) is
-        # produced by one launch
-        weights = [tensors[6 * i].contiguous() for i in range(n_ops)]
-        items, bwd_slot = [], [None] * n_ops
-        for i, op in enumerate(ops):
-            items.append((weights[i], "dw" if op[0] == "dw" else "fwd"))
+        pend = (None, None, cfg.in_act0) if cfg.in_act0 else None
+        if cfg.in_pact is not None:
+            # the input is another chain's Pending: its BatchNorm + activation are op 0's prologue; backward returns
+            # the gradient w.r.t. the ACTIVATED input - exactly what a plain backward-data of op 0 computes
+            _, _, scale, shift = _bn_parts(tensors[-1], x.shape[1])
+            pend = (scale, shift, cfg.in_pact)
+        f = _ChainForward(cfg, x, tensors, needs_grad, ctx.needs_input_grad[1])
+        ops, n = cfg.ops, len(cfg.ops)
+        cur, stats, i = x, None, 0
+        while i < n:
+            if (needs_grad and i + 1 < n
+                    and _irdw_ok(ops, i, f.w, cur, pend, i > 0 or ctx.needs_input_grad[1],
+                                 ctx.needs_input_grad[3 + 6 * i] and ctx.needs_input_grad[3 + 6 * (i + 1)],
+                                 ops[i].training)):
+                cur, pend, stats = f.irdw(i, cur, pend)
+                i += 2
+            elif (ops[i].kind == "dw" and not ops[i].has_bn and i + 1 < n and FUSE_SEPCONV
+                  and ops[i + 1].kind == "dense" and not (i + 2 == n and res is not None and not needs_grad)
+                  and _sepconv_ok(cur, f.w[i], f.w[i + 1], ops[i], ops[i + 1], needs_grad)):
+                # SepConv / DilConv stage: this depthwise conv and the pointwise conv i + 1 as ONE kernel
+                cur, pend, stats, res = f.conv(i + 1, cur, pend, res, stage=i)
+                i += 2
+            else:
+                cur, pend, stats, res = f.conv(i, cur, pend, res)
+                i += 1
+        y, tail, pool_idx, pool_fused = f.tail(cur, pend, stats, res)
         if needs_grad:
-            for i, (kind, stride, pad, dil) in enumerate(o[:4] for o in ops):
-                if i == 0 and not ctx.needs_input_grad[1]:
-                    continue
-                if kind == "dw":
-                    k = weights[i].shape[-1]
-                    if stride == 1 and dil * (k - 1) - pad >= 0:
-                        bwd_slot[i] = len(items)
-                        items.append((weights[i], "dwflip"))
-                    else:
-                        bwd_slot[i] = i  # transposed gather reads the forward layout
-                else:
-                    # (a chain whose producer is a BatchNorm uses the fused transposed kernel)
-                    fused = ((i > 0 and ops[i - 1][4]) or (i == 0 and in_act0)) and weights[i].shape[1] % 4 == 0
-                    bwd_slot[i] = len(items)
-                    items.append((weights[i], 1 if fused else _dense_dgrad_form(weights[i], stride, pad, dil)))
-        packed = _pack_many(x, items)
-        fused_dw = None  # (z_dw, ...) of a depthwise conv already computed together with the next op
-        skip_op = False
-        for i, (kind, stride, pad, dil, has_bn, act, training, momentum, eps) in enumerate(ops):
-            if skip_op:  # (the depthwise half of an InvertedResidual expansion: done with op i - 1 below)
-                skip_op = False
-                continue
-            w, gamma, beta, rm, rv, nbt = tensors[6 * i:6 * i + 6]
-            w = weights[i]
-            B, K, H, W = cur.shape
-            last = i == n_ops - 1
-            if (needs_grad and fused_dw is None and i + 1 < n_ops
-                    and _irdw_ok(ops, i, weights, cur, pend, i > 0 or ctx.needs_input_grad[1],
-                                 ctx.needs_input_grad[3 + 6 * i] and ctx.needs_input_grad[3 + 6 * (i + 1)], training)):
-                # ---- expansion + depthwise with the expanded map never stored (csrc/irdw.hip) ----
-                N = w.shape[0]
-                psc, psh, pact = pend if pend is not None else (None, None, ACT_NONE)
-                st1 = _vec(cur, 4 * N)
-                mean1, invstd1, scale1, shift1 = st1[0:N], st1[N:2 * N], st1[2 * N:3 * N], st1[3 * N:]
-                wsm = _ws(cur, lib.query("nasseg_irdw_stats_workspace", K))
-                lib.call(_k("nasseg_irdw_stats", cur), ptr(cur), ptr(w), ptr(psc), ptr(psh), pact, B, H, W, K, N,
-                         float(eps), float(momentum), ptr(gamma), ptr(beta), ptr(mean1), ptr(invstd1), ptr(scale1),
-                         ptr(shift1), ptr(rm), ptr(rv), ptr(nbt), ptr(wsm), s)
-                saved.extend([cur, psc, psh, None, st1, w, packed[bwd_slot[i]] if bwd_slot[i] is not None else None])
-                meta.append((pact,))
-                _, stride2, pad2, dil2, _, act2, _, momentum2, eps2 = ops[i + 1]
-                w2, gamma2, beta2, rm2, rv2, nbt2 = tensors[6 * (i + 1):6 * (i + 1) + 6]
-                w2 = weights[i + 1]
-                Ho, Wo = conv_out_size(H, 3, stride2, 1, 1), conv_out_size(W, 3, stride2, 1, 1)
-                z2 = _new(cur, B, N, Ho, Wo)
-                st2 = _vec(cur, 4 * N)
-                rows2 = lib.query("nasseg_irdw_rows", B, H, W, K, N, stride2, 0)
-                part2 = _ws(cur, (rows2 + 64) * 2 * N)
-                lib.call(_k("nasseg_irdw_fwd", cur), ptr(cur), ptr(w), ptr(packed[i + 1]), ptr(z2), ptr(psc), ptr(psh),
-                         pact, ptr(scale1), ptr(shift1), act, B, H, W, K, N, Ho, Wo, stride2, ptr(part2), s)
-                lib.call("nasseg_bn_finalize", ptr(part2), rows2, B * Ho * Wo, N, float(eps2), float(momentum2),
-                         ptr(gamma2), ptr(beta2), ptr(st2[0:N]), ptr(st2[N:2 * N]), ptr(st2[2 * N:3 * N]),
-                         ptr(st2[3 * N:]), ptr(rm2), ptr(rv2), ptr(nbt2), s)
-                # (input None: the depthwise conv's input does not exist - backward rebuilds it from op i's)
-                saved.extend([None, scale1, shift1, z2, st2, w2,
-                              packed[bwd_slot[i + 1]] if bwd_slot[i + 1] is not None else None])
-                meta.append((act,))
-                cur, pend = z2, (st2[2 * N:3 * N], st2[3 * N:], act2)
-                skip_op = True
-                continue
-            if (kind == "dw" and not has_bn and not last and FUSE_SEPCONV and ops[i + 1][0] == "dense"
-                    and not (i + 2 == n_ops and res is not None and not needs_grad)
-                    and _sepconv_ok(cur, w, weights[i + 1], ops[i], ops[i + 1], needs_grad)):
-                # SepConv / DilConv stage: this depthwise conv and the pointwise conv that follows
-                # run as ONE kernel (csrc/sepconv.hip) when op i+1 comes up; nothing to do here but
-                # remember the stage's input and its prologue
-                fused_dw = (cur, pend, w, packed[i], i)
-                continue
-            if fused_dw is not None:
-                # the pointwise half of a fused stage: its input is the (virtual) depthwise output
-                dk = fused_dw[2].shape[-1]
-                _, ds_, dp_, dd_ = ops[fused_dw[4]][:4]
-                H, W = conv_out_size(H, dk, ds_, dp_, dd_), conv_out_size(W, dk, ds_, dp_, dd_)
-                pend = None  # (the prologue belongs to the depthwise half: kept in fused_dw)
-            if kind == "dw":
-                k = w.shape[-1]
-                if w.shape[0] != K or w.shape[1] != 1:
-                    raise NassegError("depthwise weight {} does not match C={}".format(tuple(w.shape), K))
-                N, kh, kw = K, k, k
-                strip = bool(lib.query("nasseg_dwconv_strip_ok", k, stride, dil))
-                pro_ok = strip or (pend is not None and pend[0] is None and pend[2] == ACT_RELU)
-                stats_ok = strip
-            else:
-                N, Kw, kh, kw = w.shape
-                if Kw != K:
-                    raise NassegError("conv weight {} does not match C_in={}".format(tuple(w.shape), K))
-                pointwise = kh == 1 and kw == 1 and stride == 1 and pad == 0
-                pro_ok = pointwise and K % 4 == 0 and N % 4 == 0
-                stats_ok = N % 4 == 0
-            Ho, Wo = conv_out_size(H, kh, stride, pad, dil), conv_out_size(W, kw, stride, pad, dil)
-            if Ho <= 0 or Wo <= 0:
-                raise NassegError("conv output would be empty")
-            if pend is not None and not pro_ok:
-                cur = (_affine_act(cur, pend[0], pend[1], None, pend[2]) if pend[0] is not None
-                       else _axpby(cur, None, None, None, pend[2]))
-                pend = None
-            psc, psh, pact = pend if pend is not None else (None, None, ACT_NONE)
-            M = B * Ho * Wo
-            z = _new(cur, B, N, Ho, Wo)
-            fold = has_bn and not training and not needs_grad and not (kind == "dw" and last and res is not None)
-            stats = part = None
-            nblk = 0
-            if has_bn:
-                if training and M <= 1:
-                    raise ValueError("Expected more than 1 value per channel when training, got input "
-                                     "size {}".format((B, N, Ho, Wo)))
-                stats = _vec(cur, 4 * N)  # mean | invstd | scale | shift
-                mean, invstd, scale, shift = (stats[0:N], stats[N:2 * N], stats[2 * N:3 * N],
-                                              stats[3 * N:])
-                if not training:
-                    lib.call("nasseg_bn_eval_params", N, float(eps), ptr(gamma), ptr(beta), ptr(rm),
-                             ptr(rv), ptr(mean), ptr(invstd), ptr(scale), ptr(shift), s)
-                elif stats_ok:
-                    if fused_dw is not None:
-                        nblk = lib.query("nasseg_sepconv_blocks", B, K, Ho, Wo, N, dk, ds_, dd_)
-                    elif kind == "dw":
-                        nblk = lib.query("nasseg_dwconv_stats_blocks", B, N, Ho, Wo, kh, stride, dil)
-                    else:
-                        nblk = lib.query("nasseg_conv_fwd_stats_rows", B, Ho, Wo, N, K, kh, kw, stride, pad, dil)
-                    part = _ws(cur, (nblk + 64) * 2 * N)
-            o_sc = o_sh = o_res = None
-            o_act = ACT_NONE
-            if fold:  # inference: BN (+act, +residual) folded into the conv's epilogue
-                o_sc, o_sh, o_act = scale, shift, act
-                if last and res is not None:
-                    o_res = res
-            wp = packed[i]
-            if fused_dw is not None:
-                # (cur is still the depthwise conv's input: geometry of the stage from op i-1)
-                xin, dpend, dww, dwp, di = fused_dw
-                fused_dw = None
-                zdw = _new(xin, B, K, Ho, Wo) if needs_grad else None
-                dsc, dsh, dact = dpend if dpend is not None else (None, None, ACT_NONE)
-                lib.call(_k("nasseg_sepconv_fwd", xin), ptr(xin), ptr(dwp), ptr(w), ptr(zdw), ptr(z), ptr(dsc),
-                         ptr(dsh), dact, ptr(o_sc), ptr(o_sh), o_act, B, xin.shape[2], xin.shape[3], K, Ho, Wo, N,
-                         dk, ds_, dp_, dd_, ptr(part), s)
-                if needs_grad:
-                    saved.extend([xin, dsc, dsh, zdw, None, dww,
-                                  packed[bwd_slot[di]] if bwd_slot[di] is not None else None])
-                    meta.append((dact,))
-                    cur = zdw
-            elif kind == "dw":
-                lib.call(_k("nasseg_dwconv", cur), ptr(cur), ptr(wp), ptr(z), ptr(psc), ptr(psh), pact, ptr(o_sc),
-                         ptr(o_sh), o_act, B, H, W, K, Ho, Wo, kh, stride, pad, dil, 0, ptr(part), s)
-            else:
-                lib.call(_k("nasseg_conv_fwd", cur), ptr(cur), K, ptr(wp), ptr(z), N, ptr(psc), ptr(psh), pact,
-                         ptr(o_sc), ptr(o_sh), o_act, ptr(o_res), N, B, H, W, K, Ho, Wo, N, kh, kw,
-                         stride, pad, dil, 0, ptr(part), s)
-            if needs_grad:
-                saved.extend([cur, psc, psh, z, stats, w,
-                              packed[bwd_slot[i]] if bwd_slot[i] is not None else None])
-                meta.append((pact,))
-            if fold:
-                cur, pend = z, None
-                if last and res is not None:
-                    res = None  # consumed by the epilogue
-                continue
-            if has_bn:
-                if training:
-                    if part is not None:
-                        lib.call("nasseg_bn_finalize", ptr(part), nblk, M, N, float(eps), float(momentum),
-                                 ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(scale), ptr(shift),
-                                 ptr(rm), ptr(rv), ptr(nbt), s)
-                    else:
-                        ws = _ws(cur, lib.query("nasseg_colred_workspace", 1, M, N))
-                        lib.call(_k("nasseg_bn_stats", z), ptr(z), N, M, N, float(eps), float(momentum),
-                                 ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(scale), ptr(shift),
-                                 ptr(rm), ptr(rv), ptr(nbt), ptr(ws), s)
-                cur, pend = z, (scale, shift, act)
-            else:
-                cur, pend = z, None
-        pool = cfg[3] if len(cfg) > 3 else None
-        defer = len(cfg) > 4 and cfg[4]
-        tail = None
-        pool_idx = None
-        pool_fused = False
-        if pool is not None:
-            # Pool (src/nn/layer_factory.py:161-178): 3x3 max pooling behind the chain's last BatchNorm.  With the
-            # BatchNorm still pending (training, or inference under autograd) the pooling applies it as it loads
-            # the raw conv output - the normalised map is never written; folded into the conv's epilogue
-            # (inference without grad) the pooling reads the finished map.  One node either way.
-            pk, ps, pp = pool
-            B, N, Hc, Wc = cur.shape
-            Hp, Wp = conv_out_size(Hc, pk, ps, pp, 1), conv_out_size(Wc, pk, ps, pp, 1)
-            if Hp <= 0 or Wp <= 0:
-                raise NassegError("max pooling output would be empty")
-            psc, psh = (pend[0], pend[1]) if pend is not None else (None, None)
-            if (res is not None or (pend is not None and pend[2] != ACT_NONE) or pk != 3 or pp != 1
-                    or ps not in (1, 2)):
-                raise NassegError("conv_chain: the pooled tail serves conv + BatchNorm -> 3x3 max pooling only")
-            y = _new(cur, B, N, Hp, Wp)
-            if needs_grad:
-                pool_idx = torch.empty((B, Hp, Wp, N), device=cur.device, dtype=torch.uint8)
-            lib.call(_k("nasseg_maxpool_bn_fwd", cur), ptr(cur), ptr(psc), ptr(psh), ptr(y), ptr(pool_idx), B, Hc,
-                     Wc, N, Hp, Wp, ps, pp, s)
-            pool_fused = pend is not None
-        elif pend is not None:
-            if defer and res is None and pend[0] is not None:
-                # deferred tail: the consumer applies act(scale*z + shift) as it loads (Pending below); what
-                # comes back in backward is still the gradient w.r.t. the BatchNorm's activated output
-                y, tail = cur, stats
-            else:
-                y = _affine_act(cur, pend[0], pend[1], res, pend[2])
-        elif res is not None:
-            y = _axpby(cur, res, None, None)
-        else:
-            y = cur
-        if needs_grad:
-            if pool is not None:
-                saved.append(pool_idx)
-            ctx.save_for_backward(*[t for t in saved])
-            ctx.meta = (cfg, meta, residual is not None, tuple(x.shape), pool_fused, res_is_x)
+            ctx.save_for_backward(*[t for rec in f.saved for t in rec] + ([pool_idx] if cfg.pool is not None else []))
+            ctx.meta = (cfg, f.meta, residual is not None, res_is_x, pool_fused)
             ctx.n_inputs = 3 + len(tensors)
-        if defer:
-            if tail is None:
-                return y, None
+        if not cfg.defer:
+            return y
+        if tail is not None:
             ctx.mark_non_differentiable(tail)
-            return y, tail  # (mean | invstd | scale | shift of the last BatchNorm)
-        return y
+        return y, tail  # (mean | invstd | scale | shift of the last BatchNorm, or None)
 
     @staticmethod
     def backward(ctx, dy, *_unused):
         if dy is None:  # (no gradient reaches the chain's output: nothing to hand on)
             return (None,) * ctx.n_inputs
-        cfg, meta, has_res, x_shape = ctx.meta[:4]
-        pool_fused = ctx.meta[4] if len(ctx.meta) > 4 else False
-        in_act0, ops = cfg[:2]
-        pool = cfg[3] if len(cfg) > 3 else None
-        sv = ctx.saved_tensors
-        fused_in0 = bool(in_act0)  # (forward packed op 0's backward-data weights for the fused kernel)
+        cfg, meta, has_res, res_is_x, pool_fused = ctx.meta
+        n = len(cfg.ops)
+        sv, k = ctx.saved_tensors, len(_OpSaved._fields)
+        recs = [_OpSaved._make(sv[j:j + k]) for j in range(0, k * n, k)]
+        need = ctx.needs_input_grad
         g = _cl(dy)
-        s = current_stream()
-        n_ops = len(ops)
-        grads = [None] * (6 * n_ops)
-        dres = g if (has_res and ctx.needs_input_grad[2]) else None
+        dres = g if (has_res and need[2]) else None
         # x is also the residual: both gradients go to the same tensor, and autograd would add them with a launch of
         # its own - where op 0's input gradient comes from the plain backward-data call, its epilogue adds dres
-        fuse_res = (FUSE_RES_GRAD and len(ctx.meta) > 5 and ctx.meta[5] and dres is not None
-                    and ctx.needs_input_grad[1] and not in_act0)
-        pre = None  # BatchNorm-backward partial rows of op i that came with g (fused dgrad epilogue)
-        g_masked = False  # g already carries act' of op i's activation (with or without such rows)
-        if _TAIL_ROWS and pool is None:
-            # a consumer of this chain's deferred tail (_CatReduce) has already masked the gradient and summed
-            # it against the last BatchNorm's xhat: its rows come by the side (keyed by the gradient tensor itself)
-            ent = _TAIL_ROWS.pop(dy.data_ptr(), None)
-            # ... AND still holding what that consumer wrote: with a second consumer of the same Pending autograd may
-            # have accumulated another gradient INTO this tensor (same object, same address) - the version
-            # counter tells, and the chain then runs its own reduction over the summed gradient
-            if ent is not None and ent[0]() is dy and dy._version == ent[3] and ops[-1][4]:
-                pre = (ent[1], ent[2])
-        if pool is not None:
-            # the pooled tail: gradient w.r.t. the last BatchNorm's output by a gather over the windows -
-            # together with that BatchNorm's backward sums when the pooling had applied it on load
-            pk, ps, pp = pool
-            pool_idx = sv[7 * n_ops]
-            z_last, st_last = sv[7 * (n_ops - 1) + 3], sv[7 * (n_ops - 1) + 4]
-            Bp, Np, Hz, Wz = z_last.shape
-            g_full = _new(g, Bp, Np, Hz, Wz)
-            nb = lib.query("nasseg_maxpool_bn_bwd_blocks", Bp, Hz, Wz, Np, pk, ps, pp) if pool_fused else 0
-            if nb > 0:
-                part = _ws(g, (nb + 64) * 2 * Np)
-                lib.call(_k("nasseg_maxpool_bn_bwd", g), ptr(g), ptr(pool_idx), ptr(z_last), ptr(st_last[0:Np]),
-                         ptr(st_last[Np:2 * Np]), ptr(g_full), ptr(part), Bp, Hz, Wz, Np, g.shape[2], g.shape[3],
-                         ps, pp, s)
-                pre = (part, nb)
-            else:
-                lib.call(_k("nasseg_pool_bwd", g), 0, ptr(g), ptr(pool_idx), ptr(g_full), Bp, Hz, Wz, Np,
-                         g.shape[2], g.shape[3], pk, ps, pp, s)
-            g = g_full
-        masked_in0 = False  # dx already multiplied by in_act0' (one-kernel pointwise backward of op 0)
-        for i in range(n_ops - 1, -1, -1):
-            kind, stride, pad, dil, has_bn, act, training, momentum, eps = ops[i]
-            cur, psc, psh, z, stats, w, wb = sv[7 * i:7 * i + 7]
-            (pact,) = meta[i]
-            # InvertedResidual's expansion that was never stored (forward: _irdw_ok): the depthwise op has no input
-            # tensor, the expansion no output tensor - their one-kernel backwards rebuild it
-            ir_dw = cur is None
-            ir_pw = z is None
-            if ir_pw:
-                B, N, Ho, Wo = cur.shape[0], w.shape[0], cur.shape[2], cur.shape[3]
-            else:
-                B, N, Ho, Wo = z.shape
-            M = B * Ho * Wo
-            need_dw = ctx.needs_input_grad[3 + 6 * i]
-            need_dx = i > 0 or ctx.needs_input_grad[1]
-            fused_bn = None  # BatchNorm backward applied by the weight-gradient kernel on load
-            if has_bn:
-                mean, invstd, scale, shift = stats[0:N], stats[N:2 * N], stats[2 * N:3 * N], stats[3 * N:]
-                sums = _vec(g, 2 * N)
-                act_left = ACT_NONE if (pre is not None or g_masked) else act  # (the mask still to be applied to g)
-                pw_bact = act_left
-                go_on = need_dw or need_dx
-                if ir_pw:
-                    pw_nsl, dw_rows = lib.query("nasseg_conv_pw_bwd_slabs", B, Ho, Wo, cur.shape[1], N), 0
-                elif ir_dw:
-                    pw_nsl, dw_rows = 0, 1
-                else:
-                    pw_nsl = _pw_bwd_slabs(kind, cur, z, w, stride, pad, need_dw, need_dx, i, ops) if go_on else 0
-                    dw_rows = (_dw_bwd_rows(kind, cur, z, w, stride, pad, dil, need_dw, need_dx, i, ops)
-                               if go_on else 0)
-                # the stem (small-K k x k conv, no gradient for the image): BatchNorm backward on load in the
-                # weight-gradient kernel, dz never written (nasseg_conv_wgrad_bn_flat)
-                flat_bn = go_on and not (ir_pw or ir_dw) and _flat_bn_ok(kind, need_dw, need_dx, psc, psh, pact, w, N, z)
-                on_load = go_on and (pw_nsl > 0 or dw_rows > 0 or flat_bn)  # (a kernel below applies the BatchNorm backward)
-                wgrad_bn = go_on and not on_load and need_dw and _wgrad_bn_ok(kind, cur, z, w, stride, pad, dil)
-                plain_apply = go_on and not on_load and not wgrad_bn  # (dz by a bn_bwd_apply pass)
-                lazy_rows = None  # the sums as rows the apply kernel adds up itself
-                if pre is not None:
-                    # g arrived masked, with its per-workgroup {sum g, sum g*xhat} rows
-                    if plain_apply and _rows_small(pre[1], N):
-                        lazy_rows = (pre[0], pre[1])
-                    else:
-                        lib.call("nasseg_rows_sum", ptr(pre[0]), pre[1], 2 * N, ptr(sums), s)
-                else:
-                    lazy_rows = _bn_bwd_reduce(g, z, scale, shift, mean, invstd, act_left, sums, M, N, plain_apply)
-                if ctx.needs_input_grad[3 + 6 * i + 1]:
-                    grads[6 * i + 1] = sums[N:2 * N]
-                if ctx.needs_input_grad[3 + 6 * i + 2]:
-                    grads[6 * i + 2] = sums[0:N]
-                if not go_on:
-                    g = None
-                    break
-                if on_load:
-                    dz = None  # (the one-kernel backward / flat weight gradient below applies the BatchNorm backward on load)
-                elif wgrad_bn:
-                    # the weight-gradient kernel below computes dz while it loads g and z (masking
-                    # g first if it did not arrive masked) and leaves it behind for the
-                    # backward-data kernel
-                    fused_bn = (scale, shift, mean, invstd, sums, training, act_left)
-                    dz = None
-                else:
-                    dz = _bn_bwd_apply(g, z, scale, shift, mean, invstd, sums, M, N, training, act_left,
-                                       torch.empty_like(z), lazy_rows)
-            else:
-                dz = g
-                pw_nsl = dw_rows = 0
-                flat_bn = False
-                if not (need_dw or need_dx):
-                    g = None
-                    break
-            if ir_dw:
-                # ---- the depthwise conv behind a rebuilt expansion: nasseg_dwconv_bwd_bn with z1 = W1 x from op i - 1 ----
-                x_in, xpsc, xpsh, _, st1, w1, _ = sv[7 * (i - 1):7 * (i - 1) + 7]
-                (xpact,) = meta[i - 1]
-                Bc, K1, H, W = x_in.shape
-                K = N
-                rows = lib.query("nasseg_irdw_rows", Bc, H, W, K1, K, stride, 1)
-                dwt = torch.empty_like(w)
-                ws = _ws(g, rows * 9 * K)
-                part = _ws(g, (rows + 64) * 2 * K)
-                g_in = _new(g, Bc, K, H, W)
-                lib.call(_k("nasseg_irdw_bwd", x_in), ptr(x_in), ptr(w1), ptr(g), ptr(z), ptr(wb), int(stride == 1),
-                         ptr(g_in), _finish_wgrad(ws, dwt, 9, K, 1, 0), ptr(ws), ptr(xpsc), ptr(xpsh), xpact,
-                         ptr(st1[2 * K:3 * K]), ptr(st1[3 * K:]), ptr(st1[0:K]), ptr(st1[K:2 * K]), ops[i - 1][5],
-                         ptr(scale), ptr(shift), ptr(mean), ptr(invstd), ptr(sums), int(training), pw_bact,
-                         Bc, H, W, K1, K, Ho, Wo, stride, ptr(part), s)
-                grads[6 * i] = dwt
-                g, pre = g_in, (part, rows)
-                g_masked = False
-                continue
-            Bc, K, H, W = cur.shape
-            pre = None
-            g_masked = False
-            bn_prev = None
-            if need_dx and i > 0 and ops[i - 1][4] and K % 4 == 0:
-                # the producer of this conv's input is a BatchNorm of the chain: fuse the first
-                # half of ITS backward into the backward-data kernel below
-                zp, stp = sv[7 * (i - 1) + 3], sv[7 * (i - 1) + 4]
-                bn_prev = (zp, stp[2 * K:3 * K], stp[3 * K:], stp[0:K], stp[K:2 * K], ops[i - 1][5])
-            elif need_dx and i == 0 and in_act0 and K % 4 == 0 and (kind == "dw" or fused_in0):
-                # the chain's input went through an activation on load (ReLU ahead of DilConv's
-                # depthwise conv, of pre_clf's 1x1): the same epilogue with an identity BatchNorm
-                # multiplies dx by act'(x) - no separate pass over dx and x
-                if kind == "dw":
-                    one, zero = _identity_vectors(cur, K)
-                    bn_prev = (cur, one, zero, zero, one, in_act0)
-                else:
-                    bn_prev = (cur, None, None, None, None, in_act0)  # mask-only epilogue
-            if kind == "dw" and dw_rows > 0:
-                # 3x3 depthwise conv between two BatchNorms of the chain: its whole backward in one
-                # pass (csrc/dwconv.hip: dw3x3_bwd_bn_kernel) - BatchNorm backward on load, weight
-                # gradient, masked input gradient + the partial sums of the BatchNorm in front
-                zp, psc_, psh_, pmu_, pis_, pact_ = bn_prev
-                dwt = torch.empty_like(w)
-                ws = _ws(cur, dw_rows * 9 * K)
-                part = _ws(cur, (dw_rows + 64) * 2 * K)
-                g_in = _new(cur, Bc, K, H, W)
-                # (wb: what forward packed for this op's backward-data - rotated for stride 1, plain else)
-                lib.call(_k("nasseg_dwconv_bwd_bn", cur), ptr(cur), ptr(g), ptr(z), ptr(wb), int(stride == 1),
-                         ptr(g_in), _finish_wgrad(ws, dwt, 9, K, 1, 0), ptr(ws), ptr(psc_), ptr(psh_), ptr(pmu_),
-                         ptr(pis_), pact_, ptr(scale), ptr(shift), ptr(mean), ptr(invstd), ptr(sums), int(training),
-                         pw_bact, Bc, H, W, K, Ho, Wo, 3, stride, pad, dil, ptr(part), s)
-                grads[6 * i] = dwt
-                g, pre = g_in, (part, dw_rows)
-                continue
-            if kind == "dw":
-                k = w.shape[-1]
-                if fused_bn is not None:
-                    grads[6 * i], dz = _wgrad_bn("dw", cur, g, z, w, psc, psh, pact, fused_bn,
-                                                 (Bc, H, W, K, Ho, Wo, k, stride, pad, dil))
-                elif need_dw:
-                    grads[6 * i] = _dw_wgrad(cur, dz, w, psc, psh, pact,
-                                             (Bc, H, W, K, Ho, Wo, k, stride, pad, dil))
-                g = None
-                if need_dx:
-                    g, pre = _dw_backward_data(dz, wb, k, (Bc, K, H, W), stride, pad, dil, bn_prev)
-            else:
-                _, _, kh, kw = w.shape
-                if flat_bn:
-                    dwt = torch.empty_like(w)
-                    ws = _ws(cur, lib.query("nasseg_conv_wgrad_workspace", Bc, Ho, Wo, N, K, kh, kw))
-                    lib.call(_k("nasseg_conv_wgrad_bn_flat", cur), ptr(cur), K, ptr(g), N, ptr(z), N,
-                             _finish_wgrad(ws, dwt, kh * kw, N, K, 1), ptr(ws), ptr(scale), ptr(shift), ptr(mean),
-                             ptr(invstd), ptr(sums), int(training), act_left, Bc, H, W, K, Ho, Wo, N, kh, kw,
-                             stride, pad, dil, s)
-                    grads[6 * i] = dwt
-                    g = None
-                    continue
-                if pw_nsl > 0:
-                    # pointwise conv + BatchNorm, nothing to fuse towards the producer: BatchNorm
-                    # backward on load, weight gradient and input gradient in ONE kernel - dz is
-                    # neither written nor read back (csrc/conv_pwbwd.hip)
-                    nsl, bact_ = pw_nsl, pw_bact
-                    dwt = torch.empty_like(w)
-                    ws = _ws(cur, nsl * N * K)
-                    g_in = _new(cur, Bc, K, H, W)
-                    # op 0 of a chain that applies an activation to its input on load, or a widening conv
-                    # behind a BatchNorm of the chain (_pw_bwd_slabs): dx is masked with act' here - the
-                    # kernel takes the mask from the ACTIVATED input tile it holds - and what goes on to op
-                    # i - 1 is the gradient w.r.t. its BatchNorm's output
-                    behind_bn = i > 0 and ops[i - 1][4]
-                    dx_act = pact if ((i == 0 and in_act0 and psc is None and psh is None) or behind_bn) else ACT_NONE
-                    # ... and, K <= 64, comes with the per-slab sums of that BatchNorm's backward (dx_stats)
-                    part = pmu_ = pis_ = None
-                    skip_g = dres if (fuse_res and i == 0 and K % 4 == 0) else None  # (x is also the block's skip)
-                    if behind_bn and K <= 64:
-                        stp = sv[7 * (i - 1) + 4]
-                        pmu_, pis_ = stp[0:K], stp[K:2 * K]
-                        part = _ws(cur, (nsl + 64) * 2 * K)
-                    # (z only where the kernel loads it: where it rebuilds z = W x the argument is NULL - an explicit
-                    #  contract instead of a pointer the kernel ignores, and NULL is also what says "never stored")
-                    z_arg = z if (z is not None and lib.query("nasseg_conv_pw_bwd_reads_z", Bc, H, W, K, N)) else None
-                    lib.call(_k("nasseg_conv_pw_bwd_bn", cur), ptr(cur), ptr(g), ptr(z_arg), ptr(wb), ptr(g_in),
-                             _finish_wgrad(ws, dwt, 1, N, K, 0), ptr(ws), ptr(psc), ptr(psh), pact, dx_act,
-                             ptr(scale), ptr(shift), ptr(mean), ptr(invstd), ptr(sums), int(training), bact_,
-                             Bc, H, W, K, N, ptr(pmu_), ptr(pis_), ptr(part), ptr(skip_g), s)
-                    if skip_g is not None:
-                        dres = None  # (it is inside dx)
-                    grads[6 * i] = dwt
-                    g = g_in
-                    masked_in0 = bool(dx_act) and i == 0
-                    g_masked = behind_bn
-                    if part is not None:
-                        pre = (part, nsl)
-                    continue
-                if fused_bn is not None:
-                    grads[6 * i], dz = _wgrad_bn("dense", cur, g, z, w, psc, psh, pact, fused_bn,
-                                                 (Bc, H, W, K, N))
-                elif need_dw:
-                    grads[6 * i] = _dense_wgrad(cur, dz, w, psc, psh, pact,
-                                                (Bc, H, W, K, Ho, Wo, N, kh, kw, stride, pad, dil))
-                g = None
-                if need_dx:
-                    if bn_prev is not None:
-                        g = _new(cur, Bc, K, H, W)
-                        zp, psc_, psh_, pmu_, pis_, pact_ = bn_prev
-                        pw1 = kh == 1 and kw == 1 and stride == 1 and pad == 0
-                        nb = (lib.query("nasseg_conv_fwd_stats_blocks", Bc, H, W, K, N, 2 * int(pw1))
-                              if pmu_ is not None else 0)
-                        part = _ws(cur, (nb + 64) * 2 * K) if nb else None
-                        lib.call(_k("nasseg_conv_bwd_data_bn", dz), ptr(dz), N, ptr(wb), ptr(g), K, ptr(zp), K,
-                                 ptr(psc_), ptr(psh_), ptr(pmu_), ptr(pis_), pact_, Bc, Ho, Wo, N, H, W,
-                                 K, kh, kw, stride, pad, dil, ptr(part), s)
-                        pre = (part, nb)
-                    else:
-                        g = _dense_backward_data(dz, wb, _dense_dgrad_form(w, stride, pad, dil),
-                                                 (Bc, K, H, W), N, kh, kw, stride, pad, dil,
-                                                 dres if (fuse_res and i == 0) else None)
-                        if fuse_res and i == 0:
-                            dres = None  # (it is inside dx)
+        fuse_res = FUSE_RES_GRAD and res_is_x and dres is not None and need[1] and not cfg.in_act0
+        fl = _Flow(g, None, False, dres, False)
+        if cfg.pool is not None:
+            fl = _pool_backward(cfg.pool, fl, recs[-1], sv[k * n], pool_fused)
+        elif _TAIL_ROWS:
+            # a consumer of this chain's deferred tail (_CatReduce, a junction, ...) has already masked the gradient
+            # and summed it against the last BatchNorm's xhat: its rows come by the side of the gradient tensor
+            rows = _take_tail_rows(dy)
+            fl = fl._replace(rows=rows if cfg.ops[-1].has_bn else None)
+        chain = _ChainBackward(cfg.ops, recs, meta, need, cfg.in_act0, fuse_res, current_stream())
+        grads = [None] * (6 * n)
+        for i in range(n - 1, -1, -1):
+            grads[6 * i:6 * i + 3], fl = chain.op(i, fl)
+            if fl.g is None:
+                break
         dx = None
-        if g is not None and ctx.needs_input_grad[1]:
-            dx = g
-            if in_act0 and pre is None and not masked_in0:
+        if fl.g is not None and need[1]:
+            dx = fl.g
+            if cfg.in_act0 and fl.rows is None and not fl.in_masked:
                 # the chain started with an activation applied on load and the backward-data
                 # kernel had no fused mask for this geometry
-                dx = _act_bwd(dx, sv[0], in_act0)
-        return (None, dx, dres) + tuple(grads) + ((None,) if (len(cfg) > 5 and cfg[5] is not None) else ())
+                dx = _act_bwd(dx, recs[0].x, cfg.in_act0)
+        return (None, dx, fl.dres) + tuple(grads) + (None,)
+
+
+def _pool_backward(pool, fl, last, pool_idx, pool_fused):
+    """the pooled tail: gradient w.r.t. the last BatchNorm's output by a gather over the windows - together with
+    that BatchNorm's backward sums when the pooling had applied it on load"""
+    (pk, ps, pp), g, s = pool, fl.g, current_stream()
+    Bp, Np, Hz, Wz = last.z.shape
+    g_full = _new(g, Bp, Np, Hz, Wz)
+    nb = lib.query("nasseg_maxpool_bn_bwd_blocks", Bp, Hz, Wz, Np, pk, ps, pp) if pool_fused else 0
+    if nb <= 0:
+        lib.call(_k("nasseg_pool_bwd", g), 0, ptr(g), ptr(pool_idx), ptr(g_full), Bp, Hz, Wz, Np,
+                 g.shape[2], g.shape[3], pk, ps, pp, s)
+        return fl._replace(g=g_full)
+    mean, invstd = _bn_parts(last.stats, Np)[:2]
+    part = _ws(g, (nb + 64) * 2 * Np)
+    lib.call(_k("nasseg_maxpool_bn_bwd", g), ptr(g), ptr(pool_idx), ptr(last.z), ptr(mean), ptr(invstd),
+             ptr(g_full), ptr(part), Bp, Hz, Wz, Np, g.shape[2], g.shape[3], ps, pp, s)
+    return fl._replace(g=g_full, rows=(part, nb))
 
 
 # BatchNorm-backward partial rows handed from a consumer's backward to the producer chain's, by the side of
-# the gradient tensor: data_ptr -> (weakref to that tensor, rows, number of rows).  An entry is only honoured
-# for the very tensor object it was made for (a dead or different object: the chain reduces as usual).
+# the gradient tensor: data_ptr -> (weakref to that tensor, rows, number of rows, its version).  An entry is only
+# honoured for the very tensor object it was made for (a dead or different object: the chain reduces as usual).
 _TAIL_ROWS = {}
 FUSE_TAIL_ROWS = os.environ.get("NASSEG_FUSE_TAIL_ROWS", "1") != "0"
+
+
+def _sweep_tail_rows():
+    """drop the rows whose gradient tensor died unconsumed (a backward that stopped short)"""
+    for key in [k for k, e in _TAIL_ROWS.items() if e[0]() is None]:
+        del _TAIL_ROWS[key]
+
+
+def _hand_tail_rows(g, rows, nrows):
+    """hand the producer chain's backward the rows of its BatchNorm-backward sums that come with gradient ``g``"""
+    _sweep_tail_rows()
+    _TAIL_ROWS[g.data_ptr()] = (weakref.ref(g), rows, nrows, g._version)
+
+
+def _take_tail_rows(g):
+    """(rows, nrows) handed over with gradient ``g`` - or None, also where g is another object or autograd has since
+    accumulated another consumer's gradient into it (its version moved: the chain reduces the sum itself)"""
+    ent = _TAIL_ROWS.pop(g.data_ptr(), None)
+    if ent is not None and ent[0]() is g and g._version == ent[3]:
+        return ent[1], ent[2]
+    return None
 
 
 class Pending(object):
@@ -1469,8 +1480,8 @@ class Pending(object):
         self.z, self.stats, self.act = z, stats, int(act)  # stats: mean | invstd | scale | shift, C each
         self._mat = None
 
-    scale = property(lambda self: self.stats[2 * self.z.shape[1]:3 * self.z.shape[1]])
-    shift = property(lambda self: self.stats[3 * self.z.shape[1]:])
+    scale = property(lambda self: _bn_parts(self.stats, self.z.shape[1])[2])
+    shift = property(lambda self: _bn_parts(self.stats, self.z.shape[1])[3])
     shape = property(lambda self: self.z.shape)
     dtype = property(lambda self: self.z.dtype)
     device = property(lambda self: self.z.device)
@@ -1530,7 +1541,7 @@ class _Junction(torch.autograd.Function):
         C = z.shape[1]
         fin = None
         if n_fin:
-            fin = z if stats is None else _affine_act(z, stats[2 * C:3 * C], stats[3 * C:], None, act)
+            fin = z if stats is None else _affine_act(z, *_bn_parts(stats, C)[2:], None, act)
         outs = [z.view_as(z) for _ in range(n_raw)] + [fin.view_as(fin) for _ in range(n_fin)]
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(z if stats is not None else None, stats)
@@ -1568,9 +1579,7 @@ class _Junction(torch.autograd.Function):
         lib.call(_k("nasseg_grad_junction", out), *(args + [len(live), ptr(z) if stats is not None else None,
                  ptr(stats), act, ptr(out), ptr(rows), B, H, W, C, s]))
         if rows is not None:
-            for key in [k for k, e in _TAIL_ROWS.items() if e[0]() is None]:
-                del _TAIL_ROWS[key]
-            _TAIL_ROWS[out.data_ptr()] = (weakref.ref(out), rows, nrows, out._version)
+            _hand_tail_rows(out, rows, nrows)
         return out, None, None, None, None
 
 
@@ -1600,35 +1609,25 @@ def conv_chain(x, ops, in_act0=ACT_NONE, residual=None, pool=None, defer_tail=Fa
     the normalised output when the chain ends in a BatchNorm that is not folded (no residual, no pooling)."""
     cfg_ops, tensors = [], []
     for weight, stride, padding, dilation, depthwise, bn, act in ops:
-        if bn is None:
-            cfg_ops.append(("dw" if depthwise else "dense", int(stride), int(padding), int(dilation),
-                            False, ACT_NONE, False, 0.0, 0.0))
-            tensors.extend([weight, None, None, None, None, None])
-        else:
-            gamma, beta, rm, rv, nbt, training, momentum, eps = bn
-            cfg_ops.append(("dw" if depthwise else "dense", int(stride), int(padding), int(dilation),
-                            True, int(act), bool(training), float(momentum), float(eps)))
-            tensors.extend([weight, gamma, beta, rm, rv, nbt if training else None])
-    cfg = (int(in_act0), tuple(cfg_ops), torch.is_grad_enabled())
+        gamma, beta, rm, rv, nbt, training, momentum, eps = bn if bn is not None else (None,) * 5 + (False, 0.0, 0.0)
+        cfg_ops.append(_ChainOp("dw" if depthwise else "dense", int(stride), int(padding), int(dilation),
+                                bn is not None, int(act) if bn is not None else ACT_NONE, bool(training),
+                                float(momentum), float(eps)))
+        tensors.extend([weight, gamma, beta, rm, rv, nbt if training else None])
+    in_st = in_pact = None
     if isinstance(x, Pending):
         if in_act0 != ACT_NONE or not cfg_ops:
             x = x.materialize()  # (an activation on top of a pending one: not fused)
         else:
-            # cfg[3] pool, cfg[4] deferred tail, cfg[5] the pending input's activation (its statistics vector
-            # rides behind the per-op tensors)
-            defer = bool(defer_tail and residual is None and pool is None and cfg_ops[-1][4])
-            full = cfg + ((int(pool[0]), int(pool[1]), int(pool[2])) if pool is not None else None, defer, x.act)
-            out = _ConvChain.apply(full, x.z, residual, *(tensors + [x.stats]))
-            if not defer:
-                return out
-            y, stats = out
-            return y if stats is None else Pending(y, stats, cfg_ops[-1][5])
-    if pool is not None:
-        cfg = cfg + ((int(pool[0]), int(pool[1]), int(pool[2])),)
-    elif defer_tail and residual is None and cfg_ops and cfg_ops[-1][4]:
-        y, stats = _ConvChain.apply(cfg + (None, True), x, residual, *tensors)
-        return y if stats is None else Pending(y, stats, cfg_ops[-1][5])
-    return _ConvChain.apply(cfg, x, residual, *tensors)
+            x, in_st, in_pact = x.z, x.stats, x.act
+    defer = bool(defer_tail and residual is None and pool is None and cfg_ops and cfg_ops[-1].has_bn)
+    cfg = _ChainCfg(int(in_act0), tuple(cfg_ops), torch.is_grad_enabled(),
+                    (int(pool[0]), int(pool[1]), int(pool[2])) if pool is not None else None, defer, in_pact)
+    out = _ConvChain.apply(cfg, x, residual, *(tensors + [in_st]))
+    if not defer:
+        return out
+    y, stats = out
+    return y if stats is None else Pending(y, stats, cfg_ops[-1].act)
 
 
 def conv_bn_act(x, weight, gamma, beta, running_mean, running_var, num_batches_tracked, training,
@@ -1651,7 +1650,7 @@ class _BatchNormAct(torch.autograd.Function):
         M = B * H * W
         s = current_stream()
         stats = _vec(x, 4 * C)  # mean | invstd | scale | shift
-        mean, invstd, scale, shift = stats[0:C], stats[C:2 * C], stats[2 * C:3 * C], stats[3 * C:]
+        mean, invstd, scale, shift = _bn_parts(stats, C)
         if training:
             if M <= 1:
                 # same condition and exception class as torch.nn.functional.batch_norm
@@ -1679,7 +1678,7 @@ class _BatchNormAct(torch.autograd.Function):
         dy = _cl(dy)
         B, C, H, W = x.shape
         M = B * H * W
-        mean, invstd, scale, shift = stats[0:C], stats[C:2 * C], stats[2 * C:3 * C], stats[3 * C:]
+        mean, invstd, scale, shift = _bn_parts(stats, C)
         s = current_stream()
         sums = _vec(x, 2 * C)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
@@ -1869,8 +1868,7 @@ class _CatBNReluConv(torch.autograd.Function):
         s = current_stream()
         needs_grad = grad_mode and any(ctx.needs_input_grad)  # (grad_mode: the caller's, see _ConvChain)
         stats = _vec(x, 8 * C)  # [mean | invstd | scale | shift] x [2C]
-        mean, invstd, scale, shift = (stats[0:2 * C], stats[2 * C:4 * C], stats[4 * C:6 * C],
-                                      stats[6 * C:8 * C])
+        mean, invstd, scale, shift = _bn_parts(stats, 2 * C)
         if training:
             if M <= 1:
                 raise ValueError("Expected more than 1 value per channel when training, got input "
@@ -1909,8 +1907,7 @@ class _CatBNReluConv(torch.autograd.Function):
         B, C, H, W = x.shape
         M = B * H * W
         s = current_stream()
-        mean, invstd, scale, shift = (stats[0:2 * C], stats[2 * C:4 * C], stats[4 * C:6 * C],
-                                      stats[6 * C:8 * C])
+        mean, invstd, scale, shift = _bn_parts(stats, 2 * C)
         need_w = ctx.needs_input_grad[7]
         need_bn = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
         dbn = _vec(x, 4 * C) if need_bn else None  # [dbeta(2C) | dgamma(2C)]
@@ -1975,7 +1972,7 @@ class _BNReluConv(torch.autograd.Function):
         s = current_stream()
         needs_grad = grad_mode and any(ctx.needs_input_grad)
         stats = _vec(x, 4 * C)  # mean | invstd | scale | shift
-        mean, invstd, scale, shift = stats[0:C], stats[C:2 * C], stats[2 * C:3 * C], stats[3 * C:]
+        mean, invstd, scale, shift = _bn_parts(stats, C)
         if training:
             if M <= 1:
                 raise ValueError("Expected more than 1 value per channel when training, got input "
@@ -2006,7 +2003,7 @@ class _BNReluConv(torch.autograd.Function):
         B, C, H, W = x.shape
         M = B * H * W
         s = current_stream()
-        mean, invstd, scale, shift = stats[0:C], stats[C:2 * C], stats[2 * C:3 * C], stats[3 * C:]
+        mean, invstd, scale, shift = _bn_parts(stats, C)
         need_dx = ctx.needs_input_grad[0]
         need_bn = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         dx = dgamma = dbeta = dw = None
@@ -2061,7 +2058,7 @@ class _CatReduce(torch.autograd.Function):
         s = current_stream()
         needs_grad = grad_mode and any(ctx.needs_input_grad)
         stats = _vec(x, 4 * Ct)  # mean | invstd | scale | shift
-        mean, invstd, scale, shift = stats[0:Ct], stats[Ct:2 * Ct], stats[2 * Ct:3 * Ct], stats[3 * Ct:]
+        mean, invstd, scale, shift = _bn_parts(stats, Ct)
         if training and M <= 1:
             raise ValueError("Expected more than 1 value per channel when training, got input "
                              "size {}".format((B, Ct, Ho, Wo)))
@@ -2069,7 +2066,7 @@ class _CatReduce(torch.autograd.Function):
         nblk = lib.query("nasseg_cat_src_blocks", B, Ho, Wo, C)
         part = _ws(x, (nblk + 64) * 2 * Ct) if training else None
         for off, (t, st, act) in enumerate(((x, xst, act_x), (y, yst, act_y))):
-            sc, sh = (st[2 * C:3 * C], st[3 * C:]) if st is not None else (None, None)
+            sc, sh = _bn_parts(st, C)[2:] if st is not None else (None, None)
             lib.call(_k("nasseg_cat_src_fwd", t), ptr(t), ptr(sc), ptr(sh), act if st is not None else ACT_NONE,
                      ptr(slab), Ct, off * C, ptr(part), B, t.shape[2], t.shape[3], C, Ho, Wo, s)
         if training:
@@ -2094,15 +2091,14 @@ class _CatReduce(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        for key in [k for k, e in _TAIL_ROWS.items() if e[0]() is None]:
-            del _TAIL_ROWS[key]  # (rows whose gradient tensor died unconsumed: a backward that stopped short)
+        _sweep_tail_rows()
         slab, stats, wb, w, zx, zy, xst, yst = ctx.saved_tensors
         training, N, x_shape, y_shape, act_x, act_y = ctx.cfg
         dout = _cl(dout)
         B, Ct, Ho, Wo = slab.shape
         C = Ct // 2
         s = current_stream()
-        mean, invstd, scale, shift = stats[0:Ct], stats[Ct:2 * Ct], stats[2 * Ct:3 * Ct], stats[3 * Ct:]
+        mean, invstd, scale, shift = _bn_parts(stats, Ct)
         need_in = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         need_bn = ctx.needs_input_grad[5] or ctx.needs_input_grad[6]
         dx = dy = dgamma = dbeta = dw = None
@@ -2146,13 +2142,14 @@ class _CatReduce(torch.autograd.Function):
                         nws = lib.query("nasseg_bilinear_bwd_workspace", B, H, W, C, Ho, Wo)
                         ws = ptr(_ws(d, nws)) if nws else None
                         if rows is not None:
-                            lib.call(_k("nasseg_bilinear_bwd_act", d), ptr(d), C, 0, ptr(z), ptr(st[2 * C:3 * C]),
-                                     ptr(st[3 * C:]), act, ptr(full), B, H, W, C, Ho, Wo, ws, s)
+                            _, _, sc, sh = _bn_parts(st, C)
+                            lib.call(_k("nasseg_bilinear_bwd_act", d), ptr(d), C, 0, ptr(z), ptr(sc), ptr(sh), act,
+                                     ptr(full), B, H, W, C, Ho, Wo, ws, s)
                         else:
                             lib.call(_k("nasseg_bilinear_bwd", d), ptr(d), C, 0, ptr(full), B, H, W, C, Ho, Wo, ws, s)
                         d = full
                     if rows is not None:
-                        _TAIL_ROWS[d.data_ptr()] = (weakref.ref(d), rows, nrows, d._version)
+                        _hand_tail_rows(d, rows, nrows)
                     grads.append(d)
                 dx, dy = grads
         if ctx.needs_input_grad[10]:
@@ -2222,7 +2219,7 @@ class _AddPending(torch.autograd.Function):
         y = torch.empty_like(za)
 
         def vecs(st):
-            return (None, None) if st is None else (st[2 * C:3 * C], st[3 * C:])
+            return (None, None) if st is None else _bn_parts(st, C)[2:]
 
         (sa, ha), (sb, hb) = vecs(sta), vecs(stb)
         lib.call(_k("nasseg_add_act2", za), ptr(za), ptr(sa), ptr(ha), act_a, None, ptr(zb), ptr(sb), ptr(hb), act_b,
@@ -2308,7 +2305,7 @@ class _ParamSumPending(torch.autograd.Function):
         y = torch.empty_like(za)
 
         def vecs(st):
-            return (None, None) if st is None else (st[2 * C:3 * C], st[3 * C:])
+            return (None, None) if st is None else _bn_parts(st, C)[2:]
 
         (sa, ha), (sb, hb) = vecs(sta), vecs(stb)
         lib.call(_k("nasseg_add_act2", za), ptr(za), ptr(sa), ptr(ha), act_a, ptr(a), ptr(zb), ptr(sb), ptr(hb), act_b,
@@ -2319,8 +2316,7 @@ class _ParamSumPending(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        for key in [k for k, e in _TAIL_ROWS.items() if e[0]() is None]:
-            del _TAIL_ROWS[key]
+        _sweep_tail_rows()
         za, zb, sta, stb, a, b = ctx.saved_tensors
         act_a, act_b = ctx.acts
         dy = _cl(dy)
@@ -2343,7 +2339,7 @@ class _ParamSumPending(torch.autograd.Function):
             da, db = sums[0:C], sums[C:2 * C]
         for g, rows in ((ga, rows_a), (gb, rows_b)):
             if rows is not None:
-                _TAIL_ROWS[g.data_ptr()] = (weakref.ref(g), rows, nrows, g._version)
+                _hand_tail_rows(g, rows, nrows)
         return ga, gb, None, None, da, db, None, None
 
 
