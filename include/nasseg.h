@@ -415,6 +415,20 @@ int nasseg_ce_fwd(const float* logits, const void* target, int elem_size, int64_
                   int ignore, float* out, float* ws, void* stream);
 int nasseg_ce_bwd(const float* logits, const void* target, int elem_size, const float* stats,
                   const float* gscale, int64_t P, int C, int ignore, float* dlogits, void* stream);
+/* The same loss plus the distillation term kd_crit = nn.MSELoss() of the decoder-only step
+ * (main_search.py:455-458; trainer.py:147-149: loss + kd_coeff * kd_crit(output, kd_y)) from one pass over the
+ * logits.  teacher: fp32 [P][C] like the logits, whatever their storage.  Forward: ce = the NLL, bit-identical to
+ * nasseg_ce_fwd's out[0]; mse = sum((x - t)^2) / (P*C) over ALL elements (ignored pixels included: MSELoss has no
+ * ignore index); stats = nasseg_ce_fwd's out; ws: nasseg_ce_mse_workspace() floats.  ce and mse are two separate
+ * device scalars.  Backward: dlogits = g_ce * dNLL + g_mse * 2 (x - t) / (P*C), written once (g_ce, g_mse: device
+ * scalars, null = 1); with g_mse = 0 it is bit-identical to nasseg_ce_bwd's.  Deterministic: per-block partials,
+ * fixed-order fp64 finalize. */
+int64_t nasseg_ce_mse_workspace(void);
+int nasseg_ce_mse_fwd(const float* logits, const void* target, int elem_size, const float* teacher, int64_t P,
+                      int C, int ignore, float* ce, float* mse, float* stats, float* ws, void* stream);
+int nasseg_ce_mse_bwd(const float* logits, const void* target, int elem_size, const float* teacher,
+                      const float* stats, const float* g_ce, const float* g_mse, int64_t P, int C, int ignore,
+                      float* dlogits, void* stream);
 
 /* berHu loss of the depth head (BASELINE config 5; absent from the reference - Laina et al.
  * 2016 eq. 2, "parity unpinned") */
@@ -452,6 +466,16 @@ int64_t nasseg_optim_chunk(void);
 int nasseg_optim_step(const int64_t* tensors, int n_tensors, const int* chunks, int n_chunks, const double* hyper,
                       int n_hyper, const double* clips, int n_clip, float* dstep, double* partial, float* norms,
                       void* stream);
+/* ---- Polyak averaging: src/engine/trainer.py:167-169,270-272 (avg_p.mul_(d).add_(1 - d, p) for every parameter
+ * after every step) - one launch for all of them.
+ *   tensors  DEVICE int64 [n_tensors][4]: parameter (read) and average (written) addresses, numel, flags (bit 0: both
+ *            addresses are 16-byte aligned).  fp32, dense, average laid out like the parameter.  The kernel writes
+ *            through this table: a caller recording the call must name the averages it writes (graph_dag).
+ *   chunks   DEVICE int32 [n_chunks][2] = {tensor, first element}: nasseg_optim_chunk() elements each.
+ *   decay, alpha: (float)d and (float)(1 - d), 1 - d computed in double - the scalars ATen receives.
+ * Rounded as avg.mul_(decay).add_(param, alpha=alpha) is on this platform: fmaf(alpha, p, avg * decay). */
+int nasseg_polyak(const int64_t* tensors, int n_tensors, const int* chunks, int n_chunks, float decay, float alpha,
+                  void* stream);
 
 /* ---- hipGraph scheduling of a captured step (reference src/nn/micro_decoders.py:54-139: the five
  * ops of a ContextualCell read one input, the two cells of a MergeCell share nothing) ---------------------------------
@@ -598,6 +622,11 @@ int nasseg_bf16_ce_fwd(const nasseg_bf16_t* logits, const void* target, int elem
                   int ignore, float* out, float* ws, void* stream);
 int nasseg_bf16_ce_bwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* stats,
                   const float* gscale, int64_t P, int C, int ignore, nasseg_bf16_t* dlogits, void* stream);
+int nasseg_bf16_ce_mse_fwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* teacher,
+                           int64_t P, int C, int ignore, float* ce, float* mse, float* stats, float* ws, void* stream);
+int nasseg_bf16_ce_mse_bwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* teacher,
+                           const float* stats, const float* g_ce, const float* g_mse, int64_t P, int C, int ignore,
+                           nasseg_bf16_t* dlogits, void* stream);
 int nasseg_bf16_berhu_fwd(const nasseg_bf16_t* pred, const nasseg_bf16_t* target, int64_t n, float* out, float* ws,
                      void* stream);
 int nasseg_bf16_berhu_bwd(const nasseg_bf16_t* pred, const nasseg_bf16_t* target, const float* stats,

@@ -206,11 +206,64 @@ __global__ __launch_bounds__(256) void optim_apply_kernel(OptimArgs a) {
   }
 }
 
+// Polyak averaging of every parameter tensor in one launch (src/engine/trainer.py:167-169,270-272:
+// avg_p.mul_(d).add_(1 - d, p) per tensor, two ATen launches each).  Table rows {param, avg, numel, flags}.
+enum { P_P = 0, P_AVG, P_NUMEL, P_FLAGS, P_COLS };
+
+// avg <- avg * decay + alpha * p, rounded as ATen rounds it: mul_ is a plain fp32 product; add_ with alpha runs
+// `a + alpha * b` in fp32, which ROCm's build of torch contracts into one fma (checked on the MI355X against
+// avg.mul_(d).add_(p, alpha=1 - d): the fused form matches bit for bit, the unfused one does not).
+__device__ __forceinline__ float polyak1(float avg, float p, float decay, float alpha) {
+  return fmaf(alpha, p, __fmul_rn(avg, decay));
+}
+
+__global__ __launch_bounds__(256) void polyak_kernel(const int64_t* __restrict__ tensors,
+                                                     const int* __restrict__ chunks, float decay, float alpha) {
+  const int tid = threadIdx.x;
+  const int t = chunks[2 * blockIdx.x], off = chunks[2 * blockIdx.x + 1];
+  const int64_t* row = tensors + (int64_t)t * P_COLS;
+  const float* p = reinterpret_cast<const float*>(row[P_P]) + off;
+  float* a = reinterpret_cast<float*>(row[P_AVG]) + off;
+  int n = (int)(row[P_NUMEL] - off);
+  if (n > NASSEG_OPTIM_CHUNK) n = NASSEG_OPTIM_CHUNK;
+  if (row[P_FLAGS] & 1) {
+#pragma unroll
+    for (int j = 0; j < NASSEG_OPTIM_CHUNK / 1024; ++j) {
+      const int i = (j * 256 + tid) * 4;
+      if (i + 3 < n) {
+        const float4 pv = ld4(p + i);
+        float4 av = ld4(a + i);
+        av.x = polyak1(av.x, pv.x, decay, alpha);
+        av.y = polyak1(av.y, pv.y, decay, alpha);
+        av.z = polyak1(av.z, pv.z, decay, alpha);
+        av.w = polyak1(av.w, pv.w, decay, alpha);
+        st4(a + i, av);
+      } else {
+        for (int k = i; k < n; ++k) a[k] = polyak1(a[k], p[k], decay, alpha);
+      }
+    }
+  } else {
+    for (int k = tid; k < n; k += 256) a[k] = polyak1(a[k], p[k], decay, alpha);
+  }
+}
+
 }  // namespace
 
 extern "C" {
 
 int64_t nasseg_optim_chunk(void) { return NASSEG_OPTIM_CHUNK; }
+
+// avg <- avg * decay + alpha * param over every tensor of the table (see include/nasseg.h for its format).
+int nasseg_polyak(const int64_t* tensors, int n_tensors, const int* chunks, int n_chunks, float decay, float alpha,
+                  void* stream) {
+  NASSEG_REQUIRE(n_tensors >= 0 && n_chunks >= 0, "polyak: bad counts");
+  if (n_chunks == 0) return NASSEG_OK;
+  NASSEG_REQUIRE(tensors && chunks && n_tensors > 0, "polyak: null table");
+  hipLaunchKernelGGL(polyak_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, decay,
+                     alpha);
+  NASSEG_LAUNCH_CHECK("polyak");
+  return NASSEG_OK;
+}
 
 // One clip + optimiser step over every tensor of the table (see include/nasseg.h for the table formats).
 int nasseg_optim_step(const int64_t* tensors, int n_tensors, const int* chunks, int n_chunks, const double* hyper,

@@ -397,10 +397,13 @@ class GraphedTask0Step(_GraphedStep):
     graph launch.
 
     step(indices) -> device loss; ``indices``: int64 tensor / array of ``batch_size`` cache rows.
+    ``kd_coeff`` (not None): the loss has the distillation term kd_coeff * nn.MSELoss()(output, kd_y) of
+    src/engine/trainer.py:147-149, the teacher rows gathered from the cache's ``kd_y`` inside the graph too and
+    the term fused with the softmax/NLL (F.log_softmax_nll_mse).
     """
 
     def __init__(self, Xy_train, segmenter, optim_dec, batch_size, ignore_index=255, dec_grad_clip=0.0,
-                 aux_weight=0, capture_optimisers=False, warmup=2):
+                 aux_weight=0, capture_optimisers=False, warmup=2, kd_coeff=None):
         model = inner(segmenter)
         self.cache = Xy_train
         self.feat_keys = [k for k in Xy_train.keys() if k not in ("y", "kd_y", "out_size")]
@@ -408,6 +411,7 @@ class GraphedTask0Step(_GraphedStep):
         self.optim_dec = optim_dec
         self.ignore_index = ignore_index
         self.aux_weight = aux_weight
+        self.kd_coeff = kd_coeff
         self._trained = [model.decoder]
         self.groups = [(list(model.decoder.parameters()), dec_grad_clip, optim_dec)]
         self.decoder = model.decoder
@@ -423,7 +427,12 @@ class GraphedTask0Step(_GraphedStep):
         if isinstance(output, tuple):
             output, aux_outs = output
         output = F.bilinear_resize(output, self.out_size)
-        loss = F.log_softmax_nll(output, target, self.ignore_index)
+        if self.kd_coeff is not None:
+            loss, mse = F.log_softmax_nll_mse(output, target, F.gather_rows(self.cache["kd_y"], self.index),
+                                              self.ignore_index)
+            loss = loss + self.kd_coeff * mse
+        else:
+            loss = F.log_softmax_nll(output, target, self.ignore_index)
         if self.aux_weight > 0:
             for aux_out in aux_outs:
                 aux_out = F.bilinear_resize(aux_out, self.out_size)

@@ -405,3 +405,99 @@ def native_clip_and_step(groups):
         _CACHE[first] = (_CACHE[first][0], None)
         return False
     return True
+
+
+# -- Polyak averaging ------------------------------------------------------------------------------------------------
+_PCOLS = 4
+
+
+def polyak_tables(pairs, chunk):
+    """numpy tables of nasseg_polyak (include/nasseg.h) for pairs [(param address, average address, numel)]:
+    int64 [n][4] = {param, avg, numel, flags (bit 0: both 16-byte aligned)} and the int32 chunk list [k][2] =
+    {tensor, first element}, ``chunk`` elements each, tensors in order"""
+    import numpy as np
+
+    table = np.zeros((len(pairs), _PCOLS), dtype=np.int64)
+    chunks = []
+    for t, (pa, aa, numel) in enumerate(pairs):
+        table[t] = (pa, aa, numel, 1 if pa % 16 == 0 and aa % 16 == 0 else 0)
+        chunks.extend((t, off) for off in range(0, numel, chunk))
+    return table, np.array(chunks, dtype=np.int32).reshape(-1, 2)
+
+
+def polyak_eligible(params, avg_param):
+    """nasseg_polyak can take these pairs: as many averages as parameters, every pair fp32, dense, of one numel,
+    on one HIP device"""
+    if len(params) != len(avg_param) or not params:
+        return False
+    device = params[0].device
+    for p, a in zip(params, avg_param):
+        if not (torch.is_tensor(a) and p.dtype == torch.float32 and a.dtype == torch.float32 and p.is_cuda
+                and p.device == device and a.device == device and not p.is_sparse and not a.is_sparse
+                and p.is_contiguous() and a.is_contiguous() and p.numel() == a.numel()):
+            return False
+    return True
+
+
+class PolyakStep(object):
+    """``avg_p.mul_(decay).add_(p, alpha=1 - decay)`` for every (parameter, average) pair in ONE nasseg_polyak launch
+    (src/engine/trainer.py:167-169,270-272 make two ATen launches per tensor).  The device table of addresses is
+    built once; ``valid()`` is the cheap per-call check that it still describes the same tensors (the first and last
+    pair's addresses and the pair count - a module tree that changed is the owner's to notice: ``polyak_update``
+    keys it on TREE_VERSION).  Called between steps, outside any recorded graph; under a graph_dag Recorder the
+    call names what it reads and writes (its table is a ``const int64_t*``, which the recorder would take for a
+    read-only argument)."""
+
+    def __init__(self, params, avg_param):
+        params = list(params)
+        if not polyak_eligible(params, avg_param):
+            raise _Unsupported()
+        self.params = params
+        self.avg_param = avg_param
+        self._avg = list(avg_param)  # (the tensors the table points at stay alive)
+        self.chunk = int(F.lib.query("nasseg_optim_chunk"))
+        table, chunks = polyak_tables([(p.data_ptr(), a.data_ptr(), p.numel()) for p, a in zip(params, self._avg)],
+                                      self.chunk)
+        device = params[0].device
+        self._dev_t = torch.from_numpy(table).to(device)
+        self._dev_c = torch.from_numpy(chunks).to(device)
+        self.n_tensors, self.n_chunks = len(params), int(chunks.shape[0])
+        self._probe = (len(avg_param), params[0].data_ptr(), params[-1].data_ptr(), self._avg[0].data_ptr(),
+                       self._avg[-1].data_ptr())
+
+    def valid(self, avg_param):
+        """still the same pairs (a new list of averages, a re-allocated first / last tensor: rebuild)"""
+        return (avg_param is self.avg_param and len(avg_param) == self._probe[0]
+                and self.params[0].data_ptr() == self._probe[1] and self.params[-1].data_ptr() == self._probe[2]
+                and avg_param[0].data_ptr() == self._probe[3] and avg_param[-1].data_ptr() == self._probe[4])
+
+    def __call__(self, decay):
+        decay = float(decay)
+        rec = F.lib.recorder
+        if rec is not None:
+            rec.annotate(reads=self.params + self._avg, writes=self._avg)
+        F.lib.call("nasseg_polyak", self._dev_t.data_ptr(), self.n_tensors, self._dev_c.data_ptr(), self.n_chunks,
+                   decay, 1.0 - decay, F.current_stream())
+
+
+def polyak_update(module, params, avg_param, decay):
+    """Polyak averaging of ``module``'s parameters ``params`` (a callable returning them: walked only when the
+    table is (re)built) into ``avg_param`` by nasseg_polyak.  False when the pairs do not qualify (non-fp32, not
+    on a HIP device, numel differs ...) or NASSEG_NATIVE_OPTIM=0: the caller then runs torch's per-tensor ops."""
+    from ..nn.modules import TREE_VERSION
+
+    if not ENABLED or not avg_param:
+        return False
+    ent = getattr(module, "_nasseg_polyak", None)
+    if ent is None or ent[0] != TREE_VERSION[0] or (ent[1] is not None and not ent[1].valid(avg_param)) \
+            or (ent[1] is None and ent[2] is not avg_param):
+        try:
+            stepper = PolyakStep(params(), avg_param)
+        except _Unsupported:
+            stepper = None
+        ent = (TREE_VERSION[0], stepper, avg_param)
+        module._nasseg_polyak = ent
+    if ent[1] is None:
+        return False
+    ent[1](decay)
+    return True

@@ -10,6 +10,7 @@ to where the work runs: forward, backward and loss are nasseg HIP kernels;
 gradients of data-parallel replicas are all-reduced over RCCL before clipping.
 """
 import logging
+import os
 import time
 from collections import defaultdict
 
@@ -24,6 +25,10 @@ from .trainer_common import clip_and_step as _clip_and_step
 from .trainer_common import inner as _inner
 
 logger = logging.getLogger(__name__)
+
+# NASSEG_NATIVE_KD=0: the distillation term of the decoder-only step is always the caller's kd_crit, launched from the
+# host (A/B measurements); otherwise an nn.MSELoss() runs fused with the softmax/NLL (``native_kd``)
+NATIVE_KD = os.environ.get("NASSEG_NATIVE_KD", "1") != "0"
 
 
 def _set_stage(loader, stage):
@@ -70,6 +75,27 @@ def _polyak_update(params, avg_param, decay):
     with torch.no_grad():
         for p, avg_p in zip(params, avg_param):
             avg_p.mul_(decay).add_(p.data, alpha=1.0 - decay)
+
+
+def _polyak(module, avg_param, decay):
+    """Polyak averaging after a step: one nasseg_polyak launch for all of ``module``'s parameters
+    (engine/optim_native.py: polyak_update) where they qualify and NASSEG_NATIVE_OPTIM is not 0, else
+    ``_polyak_update``"""
+    from .optim_native import polyak_update
+
+    if not polyak_update(module, lambda: list(module.parameters()), avg_param, decay):
+        _polyak_update(module.parameters(), avg_param, decay)
+
+
+def native_kd(kd_crit, kd_y, out_size):
+    """Is the distillation term ``kd_crit(output, kd_y)`` of the decoder-only step computed by
+    F.log_softmax_nll_mse, fused with the softmax/NLL (and, with the step, replayed from a hipGraph)?  Only for
+    exactly ``nn.MSELoss(reduction="mean")`` - what src/main_search.py:455-458 makes - and an fp32 4-D teacher cache
+    of the logits' size that needs no gradient.  Anything else (another criterion, a subclass, a plain function,
+    another reduction) keeps being called as the caller wrote it."""
+    return (NATIVE_KD and type(kd_crit) is nn.MSELoss and kd_crit.reduction == "mean" and torch.is_tensor(kd_y)
+            and kd_y.dtype == torch.float32 and kd_y.dim() == 4 and tuple(kd_y.shape[2:]) == tuple(out_size)
+            and not kd_y.requires_grad)
 
 
 def _zero_grads(segmenter, optimisers):
@@ -212,13 +238,17 @@ def _cached_stepper(owner, slot, base_key, shape_key, build):
     return stepper
 
 
-def _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_clip, aux_weight, freeze_bn):
+def _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_clip, aux_weight, freeze_bn,
+                   kd_coeff=None):
+    """kd_coeff: None - no distillation term; else the coefficient of the fused nn.MSELoss term (``native_kd``)"""
     model = _inner(segmenter)
     base = (TREE_VERSION[0], id(optim_dec), ignore, dec_grad_clip, aux_weight, _bn_modes(model.decoder),
             _trainable_signature(list(model.decoder.parameters()), (optim_dec,)))
+    if kd_coeff is not None:
+        base = base + (("kd_mse", float(kd_coeff)),)
     shape = (batch_size, tuple((k, v.data_ptr(), tuple(v.shape)) for k, v in Xy_train.items() if k != "out_size"))
     return _cached_stepper(model, "_nasseg_task0_stepper", base, shape, lambda: _graphed().GraphedTask0Step(
-        Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_clip, aux_weight))
+        Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_clip, aux_weight, kd_coeff=kd_coeff))
 
 
 def _segmenter_stepper(segmenter, image, target, optim_enc, optim_dec, ignore, enc_grad_clip, dec_grad_clip,
@@ -297,10 +327,12 @@ def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255
     """step(batch_idx) -> device loss: one decoder-only training step on the cache rows
     ``batch_idx`` (a host array of ``batch_size`` indices).  Small batches are launch-bound, so the
     step is replayed from a hipGraph where that wins (engine/graphed.py: auto_graph; the stepper
-    lives with the model for as long as cache, decoder, BatchNorm modes and optimiser stay the
-    same); otherwise - and always with a distillation term or data parallel - it is launched from
-    the host: gather the batch (one kernel per cache entry), decoder forward, bilinear resize to
-    ``out_size``, softmax/NLL (+ aux heads), backward, [all-reduce], clip, optimiser."""
+    lives with the model for as long as cache, decoder, BatchNorm modes, optimiser and distillation
+    coefficient stay the same); otherwise - and always with a distillation criterion other than
+    ``nn.MSELoss()`` (``native_kd``), or data parallel - it is launched from the host: gather the
+    batch (one kernel per cache entry), decoder forward, bilinear resize to ``out_size``,
+    softmax/NLL [+ kd_coeff * MSE to the cached teacher logits, one fused kernel] (+ aux heads),
+    backward, [all-reduce], clip, optimiser."""
     decoder = _inner(segmenter).decoder
     feat_keys = [k for k in Xy_train.keys() if k not in ("y", "kd_y", "out_size")]
     out_size = tuple(Xy_train["out_size"])
@@ -309,9 +341,10 @@ def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255
     pack_memo = F.PackMemo()
     n_rows = int(Xy_train["y"].shape[0])
     n_pixels = batch_size * int(Xy_train[feat_keys[0]].shape[2]) * int(Xy_train[feat_keys[0]].shape[3]) * 16
-    if not do_kd and _replays(segmenter, device, n_pixels):
+    fused_kd = do_kd and native_kd(kd_crit, Xy_train.get("kd_y"), out_size)
+    if (not do_kd or fused_kd) and _replays(segmenter, device, n_pixels):
         stepper = _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore_index, dec_grad_clip,
-                                 aux_weight, freeze_bn)
+                                 aux_weight, freeze_bn, kd_coeff if fused_kd else None)
         if stepper is not None:
             return stepper.step
 
@@ -330,9 +363,15 @@ def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255
                 if isinstance(output, tuple):
                     output, aux_outs = output
                 output = F.bilinear_resize(output, out_size)
-                loss = F.log_softmax_nll(output, target, ignore_index)
-                if do_kd:
-                    loss = loss + kd_coeff * kd_crit(output, F.gather_rows(Xy_train["kd_y"], idx))
+                kd_y = F.gather_rows(Xy_train["kd_y"], idx) if fused_kd else None
+                if kd_y is not None and kd_y.shape == output.shape:
+                    loss, mse = F.log_softmax_nll_mse(output, target, kd_y, ignore_index)
+                    loss = loss + kd_coeff * mse
+                else:
+                    loss = F.log_softmax_nll(output, target, ignore_index)
+                    if do_kd:
+                        loss = loss + kd_coeff * kd_crit(output, kd_y if kd_y is not None
+                                                         else F.gather_rows(Xy_train["kd_y"], idx))
                 if aux_weight > 0:
                     for aux_out in aux_outs:
                         aux_out = F.bilinear_resize(aux_out, out_size)
@@ -384,7 +423,7 @@ def train_task0(Xy_train, segmenter, optim_dec, epoch, segm_crit, kd_crit, batch
         losses.update(_loss_value(segmenter, loss))
         batch_time.update(time.time() - start)
         if do_polyak:
-            _polyak_update(decoder.parameters(), avg_param, polyak_decay)
+            _polyak(decoder, avg_param, polyak_decay)
     _epoch_handshake(segmenter)
     logger.info(" Train epoch: {}\tAvg. Loss: {:.3f}\tAvg. Time: {:.3f}".format(
         epoch, losses.avg, batch_time.avg))
@@ -487,7 +526,7 @@ def train_segmenter(segmenter, train_loader, optim_enc, optim_dec, epoch, segm_c
                 loss = segmenter_step(segmenter, image, target, optim_enc, optim_dec, ignore,
                                       enc_grad_clip, dec_grad_clip, aux_weight)
             if do_polyak:
-                _polyak_update(segmenter.parameters(), avg_param, polyak_decay)
+                _polyak(segmenter, avg_param, polyak_decay)
         except Exception as e:
             _tell_peers(segmenter, e, syncs, n_steps is not None and i == n_steps - 1)
             raise _as_rank_failure(segmenter, e)

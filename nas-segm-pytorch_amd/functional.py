@@ -2526,6 +2526,54 @@ def log_softmax_nll(logits, target, ignore_index=255):
     return _LogSoftmaxNLL.apply(logits, target, ignore_index)
 
 
+class _LogSoftmaxNLLMSE(torch.autograd.Function):
+    """(nll, mse) from one nasseg_ce_mse_fwd; backward hands both upstream gradients to one nasseg_ce_mse_bwd.
+    The two outputs are scalars of their own, written by the kernel (not views of the statistics it saves):
+    the reference's ``loss += kd_coeff * mse`` may modify either one in place."""
+
+    @staticmethod
+    def forward(ctx, logits, target, teacher, ignore_index):
+        logits = _cl(logits)
+        B, C, H, W = logits.shape
+        target, esz = _label_tensor(target)
+        if tuple(target.shape) != (B, H, W):
+            raise NassegError("loss: target {} does not match logits {}".format(
+                tuple(target.shape), tuple(logits.shape)))
+        require_device(teacher)
+        if tuple(teacher.shape) != (B, C, H, W) or teacher.dtype != torch.float32:
+            raise NassegError("log_softmax_nll_mse: the teacher must be fp32 of the logits' shape {} (got {} {})"
+                              .format(tuple(logits.shape), teacher.dtype, tuple(teacher.shape)))
+        teacher = teacher.contiguous(memory_format=torch.channels_last)
+        nll = torch.empty((), device=logits.device, dtype=torch.float32)
+        mse = torch.empty((), device=logits.device, dtype=torch.float32)
+        stats = _vec(logits, 2)
+        ws = _ws(logits, lib.query("nasseg_ce_mse_workspace"))
+        lib.call(_k("nasseg_ce_mse_fwd", logits), ptr(logits), ptr(target), esz, ptr(teacher), B * H * W, C,
+                 int(ignore_index), ptr(nll), ptr(mse), ptr(stats), ptr(ws), current_stream())
+        ctx.save_for_backward(logits, target, teacher, stats)
+        ctx.cfg = (esz, int(ignore_index))
+        return nll, mse
+
+    @staticmethod
+    def backward(ctx, g_nll, g_mse):
+        logits, target, teacher, stats = ctx.saved_tensors
+        esz, ignore = ctx.cfg
+        B, C, H, W = logits.shape
+        g_nll = g_nll.to(torch.float32).contiguous().view(1)
+        g_mse = g_mse.to(torch.float32).contiguous().view(1)
+        d = torch.empty_like(logits)
+        lib.call(_k("nasseg_ce_mse_bwd", logits), ptr(logits), ptr(target), esz, ptr(teacher), ptr(stats),
+                 ptr(g_nll), ptr(g_mse), B * H * W, C, ignore, ptr(d), current_stream())
+        return d, None, None, None
+
+
+def log_softmax_nll_mse(logits, target, teacher, ignore_index=255):
+    """(nn.NLLLoss2d(ignore_index)(nn.LogSoftmax()(logits), target), nn.MSELoss()(logits, teacher)) -> two 0-dim
+    tensors, both differentiable: the decoder-only step's loss and its distillation term (src/engine/trainer.py:
+    144-149) from one pass over the logits.  ``teacher``: fp32, the logits' shape (the task0 cache's kd_y)."""
+    return _LogSoftmaxNLLMSE.apply(logits, target, teacher, ignore_index)
+
+
 class _BerHu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target):
