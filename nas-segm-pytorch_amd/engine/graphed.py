@@ -37,7 +37,7 @@ from torch import nn
 
 from .. import functional as F
 from . import graph_dag
-from .trainer_common import clip_and_step, inner
+from .trainer_common import check_cache_rows, clip_and_step, inner, task0_loss, task1_loss
 
 logger = logging.getLogger(__name__)
 
@@ -362,23 +362,10 @@ class GraphedSegmenterStep(_GraphedStep):
         self._init_common(segmenter, capture_optimisers, (optim_enc, optim_dec), warmup)
 
     def _forward_loss(self):
+        if self.loss_fn is None:
+            return task1_loss(self.segmenter, self.image, self.target, self.ignore_index, self.aux_weight)
         output = self.segmenter(self.image)
-        aux_outs = []
-        if isinstance(output, tuple):
-            output, aux_outs = output
-        if self.loss_fn is not None:
-            return self.loss_fn(output, self.target)
-        target = F.nearest_label_resize(self.target, output.size()[2:])
-        loss = F.log_softmax_nll(output, target, self.ignore_index)
-        if self.aux_weight > 0:
-            for aux_out in aux_outs:
-                aux_out = F.bilinear_resize(aux_out, target.size()[1:])
-                loss = loss + F.log_softmax_nll(aux_out, target, self.ignore_index) * self.aux_weight
-        return loss
-
-    def matches(self, image, target):
-        return (tuple(image.shape) == tuple(self.image.shape) and image.dtype == self.image.dtype
-                and tuple(target.shape) == tuple(self.target.shape) and target.dtype == self.target.dtype)
+        return self.loss_fn(output[0] if isinstance(output, tuple) else output, self.target)
 
     def step(self, image=None, target=None):
         if image is not None and image.data_ptr() != self.image.data_ptr():
@@ -406,8 +393,6 @@ class GraphedTask0Step(_GraphedStep):
                  aux_weight=0, capture_optimisers=False, warmup=2, kd_coeff=None):
         model = inner(segmenter)
         self.cache = Xy_train
-        self.feat_keys = [k for k in Xy_train.keys() if k not in ("y", "kd_y", "out_size")]
-        self.out_size = tuple(int(v) for v in Xy_train["out_size"])
         self.optim_dec = optim_dec
         self.ignore_index = ignore_index
         self.aux_weight = aux_weight
@@ -416,38 +401,17 @@ class GraphedTask0Step(_GraphedStep):
         self.groups = [(list(model.decoder.parameters()), dec_grad_clip, optim_dec)]
         self.decoder = model.decoder
         self.index = torch.arange(batch_size, device=Xy_train["y"].device, dtype=torch.int64)
-        self._cache_rows = int(Xy_train["y"].shape[0])
         self._init_common(segmenter, capture_optimisers, (optim_dec,), warmup)
 
     def _forward_loss(self):
-        feats = [F.gather_rows(self.cache[k], self.index) for k in self.feat_keys]
-        target = F.gather_rows(self.cache["y"], self.index)
-        output = self.decoder(feats)
-        aux_outs = []
-        if isinstance(output, tuple):
-            output, aux_outs = output
-        output = F.bilinear_resize(output, self.out_size)
-        if self.kd_coeff is not None:
-            loss, mse = F.log_softmax_nll_mse(output, target, F.gather_rows(self.cache["kd_y"], self.index),
-                                              self.ignore_index)
-            loss = loss + self.kd_coeff * mse
-        else:
-            loss = F.log_softmax_nll(output, target, self.ignore_index)
-        if self.aux_weight > 0:
-            for aux_out in aux_outs:
-                aux_out = F.bilinear_resize(aux_out, self.out_size)
-                loss = loss + F.log_softmax_nll(aux_out, target, self.ignore_index) * self.aux_weight
-        return loss
+        return task0_loss(self.cache, self.index, self.decoder, self.ignore_index, self.aux_weight, self.kd_coeff)
 
     def step(self, indices):
         idx = torch.as_tensor(indices, dtype=torch.int64)
         if tuple(idx.shape) != tuple(self.index.shape):
             raise F.NassegError("GraphedTask0Step: batches of {} indices (got {})".format(
                 self.index.numel(), tuple(idx.shape)))
-        if not idx.is_cuda and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self._cache_rows):
-            # the reference's Xy_train[k][train_idx] raises here (trainer.py:132-137); the kernel's
-            # clamp is a memory-safety net only
-            raise IndexError("GraphedTask0Step: cache row index out of range [0, {})".format(self._cache_rows))
+        check_cache_rows(idx, self.cache, "GraphedTask0Step")
         self.index.copy_(idx, non_blocking=True)
         return self._replay()
 

@@ -9,10 +9,10 @@ averaging, one host sync per step for the loss value.  Differences are confined
 to where the work runs: forward, backward and loss are nasseg HIP kernels;
 gradients of data-parallel replicas are all-reduced over RCCL before clipping.
 """
+import contextlib
 import logging
 import os
 import time
-from collections import defaultdict
 
 import numpy as np
 import torch
@@ -21,6 +21,8 @@ from torch import nn
 from .. import functional as F
 from ..helpers.utils import AverageMeter, try_except
 from ..nn.modules import TREE_VERSION
+from . import graphed
+from .trainer_common import cache_feature_keys, check_cache_rows, task0_loss, task1_loss
 from .trainer_common import clip_and_step as _clip_and_step
 from .trainer_common import inner as _inner
 
@@ -149,6 +151,19 @@ def _tell_peers(segmenter, exc, syncs_before=None, last_step=False):
     segmenter.sync_gradients(failed=True)
 
 
+@contextlib.contextmanager
+def _step_failure(segmenter):
+    """the inner step: a failure before this rank joined the step's gradient collective is told to the peers
+    waiting in it; a later one - clipping, the optimiser - is the caller's to announce (the epoch loop)"""
+    syncs = _syncs(segmenter)
+    try:
+        yield
+    except Exception as e:
+        if _syncs(segmenter) == syncs:
+            _tell_peers(segmenter, e)
+        raise
+
+
 def _as_rank_failure(segmenter, exc):
     """what the step loop re-raises: data parallel, an exception that ``try_except`` would let through (not
     a RuntimeError) becomes a RankFailure, so that this rank scores the candidate 0 like the peers it just
@@ -182,15 +197,9 @@ def _agreed_count(segmenter, n):
     return int(t.item())
 
 
-def _graphed():
-    from . import graphed  # (graphed imports this module's helpers)
-
-    return graphed
-
-
 def _replays(segmenter, device, n_pixels):
     """does this step run as a hipGraph replay?  (device memory only; engine/graphed.py: auto_graph)"""
-    return device.type == "cuda" and _graphed().auto_graph(segmenter, n_pixels)
+    return device.type == "cuda" and graphed.auto_graph(segmenter, n_pixels)
 
 
 def _bn_modes(module):
@@ -238,8 +247,7 @@ def _cached_stepper(owner, slot, base_key, shape_key, build):
     return stepper
 
 
-def _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_clip, aux_weight, freeze_bn,
-                   kd_coeff=None):
+def _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_clip, aux_weight, kd_coeff=None):
     """kd_coeff: None - no distillation term; else the coefficient of the fused nn.MSELoss term (``native_kd``)"""
     model = _inner(segmenter)
     base = (TREE_VERSION[0], id(optim_dec), ignore, dec_grad_clip, aux_weight, _bn_modes(model.decoder),
@@ -247,7 +255,7 @@ def _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_
     if kd_coeff is not None:
         base = base + (("kd_mse", float(kd_coeff)),)
     shape = (batch_size, tuple((k, v.data_ptr(), tuple(v.shape)) for k, v in Xy_train.items() if k != "out_size"))
-    return _cached_stepper(model, "_nasseg_task0_stepper", base, shape, lambda: _graphed().GraphedTask0Step(
+    return _cached_stepper(model, "_nasseg_task0_stepper", base, shape, lambda: graphed.GraphedTask0Step(
         Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_clip, aux_weight, kd_coeff=kd_coeff))
 
 
@@ -257,7 +265,7 @@ def _segmenter_stepper(segmenter, image, target, optim_enc, optim_dec, ignore, e
     base = (TREE_VERSION[0], id(optim_enc), id(optim_dec), ignore, enc_grad_clip, dec_grad_clip, aux_weight,
             _bn_modes(model), _trainable_signature(list(model.parameters()), (optim_enc, optim_dec)))
     shape = (tuple(image.shape), image.dtype, tuple(target.shape), target.dtype)
-    return _cached_stepper(model, "_nasseg_task1_stepper", base, shape, lambda: _graphed().GraphedSegmenterStep(
+    return _cached_stepper(model, "_nasseg_task1_stepper", base, shape, lambda: graphed.GraphedSegmenterStep(
         segmenter, image, target, optim_enc, optim_dec, ignore, enc_grad_clip, dec_grad_clip, aux_weight))
 
 
@@ -334,48 +342,27 @@ def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255
     softmax/NLL [+ kd_coeff * MSE to the cached teacher logits, one fused kernel] (+ aux heads),
     backward, [all-reduce], clip, optimiser."""
     decoder = _inner(segmenter).decoder
-    feat_keys = [k for k in Xy_train.keys() if k not in ("y", "kd_y", "out_size")]
+    feat = Xy_train[cache_feature_keys(Xy_train)[0]]
     out_size = tuple(Xy_train["out_size"])
     device = Xy_train["y"].device
     dec_params = list(decoder.parameters())
     pack_memo = F.PackMemo()
-    n_rows = int(Xy_train["y"].shape[0])
-    n_pixels = batch_size * int(Xy_train[feat_keys[0]].shape[2]) * int(Xy_train[feat_keys[0]].shape[3]) * 16
+    n_pixels = batch_size * int(feat.shape[2]) * int(feat.shape[3]) * 16
     fused_kd = do_kd and native_kd(kd_crit, Xy_train.get("kd_y"), out_size)
     if (not do_kd or fused_kd) and _replays(segmenter, device, n_pixels):
         stepper = _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore_index, dec_grad_clip,
-                                 aux_weight, freeze_bn, kd_coeff if fused_kd else None)
+                                 aux_weight, kd_coeff if fused_kd else None)
         if stepper is not None:
             return stepper.step
 
     def step(batch_idx):
-        syncs = _syncs(segmenter)
-        try:
+        with _step_failure(segmenter):
             idx = torch.as_tensor(batch_idx, dtype=torch.int64)
-            if not idx.is_cuda and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n_rows):
-                raise IndexError("train_task0: cache row index out of range [0, {})".format(n_rows))  # as Xy[k][idx]
+            check_cache_rows(idx, Xy_train, "train_task0")
             idx = idx.to(device, non_blocking=True)
             with F.packed_once(pack_memo):  # (one weight re-pack launch per step)
-                feats = [F.gather_rows(Xy_train[k], idx) for k in feat_keys]
-                target = F.gather_rows(Xy_train["y"], idx)
-                output = decoder(feats)
-                aux_outs = []
-                if isinstance(output, tuple):
-                    output, aux_outs = output
-                output = F.bilinear_resize(output, out_size)
-                kd_y = F.gather_rows(Xy_train["kd_y"], idx) if fused_kd else None
-                if kd_y is not None and kd_y.shape == output.shape:
-                    loss, mse = F.log_softmax_nll_mse(output, target, kd_y, ignore_index)
-                    loss = loss + kd_coeff * mse
-                else:
-                    loss = F.log_softmax_nll(output, target, ignore_index)
-                    if do_kd:
-                        loss = loss + kd_coeff * kd_crit(output, kd_y if kd_y is not None
-                                                         else F.gather_rows(Xy_train["kd_y"], idx))
-                if aux_weight > 0:
-                    for aux_out in aux_outs:
-                        aux_out = F.bilinear_resize(aux_out, out_size)
-                        loss = loss + F.log_softmax_nll(aux_out, target, ignore_index) * aux_weight
+                loss = task0_loss(Xy_train, idx, decoder, ignore_index, aux_weight, kd_coeff if do_kd else None,
+                                  kd_crit, fused_kd)
                 _zero_grads(segmenter, (optim_dec,))
                 with F.deferred_wgrad(params=dec_params, second_stream=False):  # (crops of the feature cache: launch-bound)
                     loss.backward()
@@ -384,10 +371,6 @@ def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255
                 # decoder gradients are averaged (the reference runs this stage on one GPU)
                 segmenter.sync_gradients()
             _clip_and_step([(dec_params, dec_grad_clip, optim_dec)])
-        except Exception as e:
-            if _syncs(segmenter) == syncs:
-                _tell_peers(segmenter, e)  # (the peers are waiting in this step's collective)
-            raise  # (a later failure - clipping, the optimiser - is the caller's to announce: train_task0)
         return loss
 
     return step
@@ -446,33 +429,19 @@ def segmenter_step(segmenter, image, target, optim_enc, optim_dec, ignore_index=
         model._nasseg_step_params = cached
         model._nasseg_pack_memo = F.PackMemo()
     groups = cached[1]
-    syncs = _syncs(segmenter)
-    # the parameters are constant until the optimiser steps below: all chains' weights are
-    # re-packed by one launch at the start of the step
-    try:
+    with _step_failure(segmenter):
+        # the parameters are constant until the optimiser steps below: all chains' weights are
+        # re-packed by one launch at the start of the step
         with F.packed_once(model._nasseg_pack_memo):
-            output = segmenter(image)
-            aux_outs = []
-            if isinstance(output, tuple):
-                output, aux_outs = output
-            target = F.nearest_label_resize(target, output.size()[2:])
-            loss = F.log_softmax_nll(output, target, ignore_index)
-            if aux_weight > 0:
-                for aux_out in aux_outs:
-                    aux_out = F.bilinear_resize(aux_out, target.size()[1:])
-                    loss = loss + F.log_softmax_nll(aux_out, target, ignore_index) * aux_weight
+            loss = task1_loss(segmenter, image, target, ignore_index, aux_weight)
             _zero_grads(segmenter, (optim_enc, optim_dec))
             # gradients were just cleared: the second stages of all weight-gradient reductions run
             # batched when backward is through
             # (a step small enough to be worth replaying from a hipGraph is launch-bound when it is not: no second stream)
-            side = image.shape[0] * image.shape[2] * image.shape[3] > _graphed().AUTO_GRAPH_MAX_PIXELS
+            side = image.shape[0] * image.shape[2] * image.shape[3] > graphed.AUTO_GRAPH_MAX_PIXELS
             with F.deferred_wgrad(params=groups[0] + groups[1], second_stream=side):
                 loss.backward()
         finish_step(segmenter, groups, optim_enc, optim_dec, enc_grad_clip, dec_grad_clip)
-    except Exception as e:
-        if _syncs(segmenter) == syncs:
-            _tell_peers(segmenter, e)  # (the peers are waiting in this step's collective)
-        raise  # (a later failure - clipping, the optimiser - is the caller's to announce: train_segmenter)
     return loss
 
 

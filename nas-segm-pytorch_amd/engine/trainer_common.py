@@ -1,5 +1,8 @@
-"""Helpers shared by the eager steps (trainer.py) and the hipGraph steppers (graphed.py)."""
+"""Helpers shared by the eager steps (trainer.py) and the hipGraph steppers (graphed.py): one forward + loss per
+step kind, so that a replayed step records exactly what a host-launched one launches."""
 from torch import nn
+
+from .. import functional as F
 
 
 def inner(segmenter):
@@ -27,3 +30,63 @@ def clip_and_step(groups, native=None):
     for _, _, optim in groups:
         if optim is not None:
             optim.step()
+
+
+def _heads(output):
+    """(logits, [auxiliary logits]) of a segmenter's or a decoder's output"""
+    return output if isinstance(output, tuple) else (output, [])
+
+
+def segmentation_loss(output, aux_outs, target, ignore_index, aux_weight, loss=None):
+    """LogSoftmax + NLL of the main head (``loss``: that term already computed, with the distillation term added)
+    + aux_weight * those of the auxiliary heads, each resized to the labels' size, when aux_weight > 0"""
+    if loss is None:
+        loss = F.log_softmax_nll(output, target, ignore_index)
+    if aux_weight > 0:
+        for aux_out in aux_outs:
+            aux_out = F.bilinear_resize(aux_out, target.size()[1:])
+            loss = loss + F.log_softmax_nll(aux_out, target, ignore_index) * aux_weight
+    return loss
+
+
+def task1_loss(segmenter, image, target, ignore_index, aux_weight):
+    """forward + loss of the end-to-end step: the labels nearest-resized to the logits' size"""
+    output, aux_outs = _heads(segmenter(image))
+    target = F.nearest_label_resize(target, output.size()[2:])
+    return segmentation_loss(output, aux_outs, target, ignore_index, aux_weight)
+
+
+def cache_feature_keys(cache):
+    """the encoder-feature entries of the task0 cache (engine/trainer.py: populate_task0)"""
+    return [k for k in cache.keys() if k not in ("y", "kd_y", "out_size")]
+
+
+def check_cache_rows(idx, cache, caller):
+    """the reference's Xy_train[k][train_idx] raises here (src/engine/trainer.py:132-137); the gather kernel's
+    clamp is a memory-safety net only"""
+    n_rows = int(cache["y"].shape[0])
+    if not idx.is_cuda and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n_rows):
+        raise IndexError("{}: cache row index out of range [0, {})".format(caller, n_rows))
+
+
+def task0_loss(cache, index, decoder, ignore_index, aux_weight, kd_coeff=None, kd_crit=None, fuse_kd=True):
+    """forward + loss of the decoder-only step on the cache rows ``index`` (an int64 device tensor): gather, decoder,
+    bilinear resize to ``out_size``, softmax/NLL, distillation term, aux heads.  kd_coeff None: no distillation term.
+    ``fuse_kd``: the teacher rows are gathered after the resize and kd_coeff * MSE runs fused with the softmax/NLL
+    (F.log_softmax_nll_mse refuses a teacher of another shape) - given a ``kd_crit``, only when the rows have the
+    logits' shape.  Otherwise kd_coeff * kd_crit(output, teacher rows) runs from the host."""
+    feats = [F.gather_rows(cache[k], index) for k in cache_feature_keys(cache)]
+    target = F.gather_rows(cache["y"], index)
+    output, aux_outs = _heads(decoder(feats))
+    output = F.bilinear_resize(output, cache["out_size"])
+    loss = None
+    if kd_coeff is not None:
+        kd_y = F.gather_rows(cache["kd_y"], index) if fuse_kd else None
+        if kd_y is not None and (kd_crit is None or kd_y.shape == output.shape):
+            loss, mse = F.log_softmax_nll_mse(output, target, kd_y, ignore_index)
+            loss = loss + kd_coeff * mse
+        else:
+            loss = F.log_softmax_nll(output, target, ignore_index)
+            kd_y = kd_y if kd_y is not None else F.gather_rows(cache["kd_y"], index)
+            loss = loss + kd_coeff * kd_crit(output, kd_y)
+    return segmentation_loss(output, aux_outs, target, ignore_index, aux_weight, loss)
