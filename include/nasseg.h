@@ -514,9 +514,23 @@ int nasseg_graph_run(int n_ops, const int64_t* ops, void* stream);
  * [B][9 (Ho + Wo)] = rows [Ho][4 indices, 4 coefficients], columns [Wo][4, 4] (OpenCV's 11-bit INTER_CUBIC
  * coefficients; index -1: a fill pixel), mask rows [Ho], mask columns [Wo] (nearest index, -1: fill), indices
  * into the window; lut [3][256]: output value of channel c for the uint8 result v.  Writes image [B][Ho][Wo][3]
- * (NHWC) and mask uint8 [B][Ho][Wo]. */
+ * (NHWC) and mask uint8 [B][Ho][Wo] (mask null: no mask is written). */
 int nasseg_augment(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps, const float* lut,
                    float* image, uint8_t* mask, int B, int Ho, int Wo, void* stream);
+
+/* ---- prediction post-processing: cv2.resize(logits, dsize, interpolation=INTER_CUBIC) (float branch) of the
+ * reference's inference notebooks, then argmax for segmentation (engine/predict.py) ------------------------------
+ * x: NHWC [B][h][w][C], any C >= 1.  taps int32 / coef float32 [4 (H + W)]: per output row, then per output
+ * column, the four clipped source indices and the four Keys weights (A = -0.75) of data/datasets._cubic_taps(n_src,
+ * n_dst, n_dst / n_src).  Horizontal pass over the four source rows, then vertical, each summed in tap order from
+ * zero without FMA contraction: bit-identical to that host restatement (datasets.resize_cubic_to).
+ *   nasseg_resize_cubic:        y fp32 NHWC [B][H][W][C];
+ *   nasseg_resize_cubic_argmax: labels uint8 [B][H][W] = argmax over C of the resized values (not stored), lowest
+ *                               index wins ties; C <= 256. */
+int nasseg_resize_cubic(const float* x, int B, int h, int w, int C, const int* taps, const float* coef, float* y,
+                        int H, int W, void* stream);
+int nasseg_resize_cubic_argmax(const float* x, int B, int h, int w, int C, const int* taps, const float* coef,
+                               uint8_t* labels, int H, int W, void* stream);
 
 /* ---- bfloat16 activation storage --------------------------------------------
  * Every entry point above that reads or writes ACTIVATIONS (feature maps and their gradients)
@@ -688,6 +702,10 @@ int nasseg_bf16_conv_wgrad(const nasseg_bf16_t* x, int ldx, const nasseg_bf16_t*
 int nasseg_bf16_augment(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
                         const nasseg_bf16_t* lut, nasseg_bf16_t* image, uint8_t* mask, int B, int Ho, int Wo,
                         void* stream);
+int nasseg_bf16_resize_cubic(const nasseg_bf16_t* x, int B, int h, int w, int C, const int* taps, const float* coef,
+                             float* y, int H, int W, void* stream);
+int nasseg_bf16_resize_cubic_argmax(const nasseg_bf16_t* x, int B, int h, int w, int C, const int* taps,
+                                    const float* coef, uint8_t* labels, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

@@ -87,6 +87,7 @@ __global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict_
   o[1] = slut[256 + v[1]];
   o[2] = slut[512 + v[2]];
 
+  if (!mask) return;  // (an image without a mask: F.prepare_image)
   int m = msk_fill & 255;
   if (my >= 0 && mx >= 0 && msk_ok) m = src[msk_off + (int64_t)min(my, h - 1) * msk_ld + min(mx, w - 1)];
   mask[(int64_t)b * npix + p] = (uint8_t)m;

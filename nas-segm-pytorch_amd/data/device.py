@@ -115,6 +115,17 @@ def normalise_table(op):
     return np.ascontiguousarray(out[:, 0, :].T)
 
 
+# the reference's prepare_img (src/utils/helpers.py): what its inference path feeds a network
+IMG_SCALE = 1.0 / 255
+IMG_MEAN = np.array([0.485, 0.456, 0.406]).reshape((1, 1, 3))
+IMG_STD = np.array([0.229, 0.224, 0.225]).reshape((1, 1, 3))
+
+
+def prepare_img_table():
+    """float64 [3][256]: prepare_img of the uint8 value v in channel c (functional.prepare_image's table)"""
+    return normalise_table(D.Normalise(IMG_SCALE, IMG_MEAN, IMG_STD))
+
+
 def _plan_normalise(op, plan):
     plan.lut = normalise_table(op)
 

@@ -14,6 +14,7 @@ import torch
 from .. import functional as F
 from ..helpers.miou_utils import compute_iu, compute_ius_accs
 from ..helpers.utils import try_except
+from .predict import Predictor  # noqa: F401  (the reference's inference notebooks, on the device)
 
 logger = logging.getLogger(__name__)
 

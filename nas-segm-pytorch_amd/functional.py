@@ -2702,6 +2702,139 @@ def argmax_confusion(logits, gt, n_classes, cm=None, out_size=None, return_preds
     return (cm, preds) if return_preds else cm
 
 
+# ---------------------------------------------------------------------------
+# prediction: image preparation and the notebooks' post-processing (engine/predict.py)
+# ---------------------------------------------------------------------------
+_TABLES_KEPT = 256  # device tables of each kind kept for reuse (least recently used first out)
+_CUBIC_TABLES = collections.OrderedDict()
+_PREPARE_PLANS = collections.OrderedDict()
+
+
+def _lru(cache, key, make):
+    hit = cache.get(key)
+    if hit is None:
+        hit = cache[key] = make()
+        while len(cache) > _TABLES_KEPT:
+            cache.popitem(last=False)
+    else:
+        cache.move_to_end(key)
+    return hit
+
+
+def cubic_tables_host(h, w, H, W):
+    """(taps int32 [4 (H + W)], coef float32 [4 (H + W)]) of an h x w -> H x W INTER_CUBIC resize in cv2's dsize
+    form: data/datasets._cubic_taps per axis, rows then columns (include/nasseg.h: nasseg_resize_cubic)."""
+    import numpy as np
+
+    from .data.datasets import _cubic_taps
+
+    iy, wy = _cubic_taps(h, H, H / h)
+    ix, wx = _cubic_taps(w, W, W / w)
+    return (np.concatenate([iy.ravel(), ix.ravel()]).astype(np.int32),
+            np.concatenate([wy.ravel(), wx.ravel()]).astype(np.float32))
+
+
+def cubic_tables(device, h, w, H, W):
+    """``cubic_tables_host`` uploaded to ``device``, cached per (device, h, w, H, W).  A caller that records the
+    resize into a hipGraph holds on to the pair it passes (``tables=``): the cache may drop it later."""
+    def make():
+        taps, coef = cubic_tables_host(h, w, H, W)
+        return torch.from_numpy(taps).to(device), torch.from_numpy(coef).to(device)
+
+    return _lru(_CUBIC_TABLES, (torch.device(device), int(h), int(w), int(H), int(W)), make)
+
+
+def _resize_args(name, x, size, tables):
+    x = _cl(x.detach())
+    B, C, h, w = x.shape
+    try:
+        H, W = (int(s) for s in size)
+        ok = H > 0 and W > 0 and (H, W) == tuple(size)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise NassegError("{}: size must be two positive integers (got {!r})".format(name, size))
+    if min(B, C, h, w) == 0:
+        raise NassegError("{}: empty input {}".format(name, tuple(x.shape)))
+    taps, coef = tables if tables is not None else cubic_tables(x.device, h, w, H, W)
+    if (taps.dtype != torch.int32 or coef.dtype != torch.float32 or taps.numel() != 4 * (H + W)
+            or coef.numel() != 4 * (H + W) or taps.device != x.device or coef.device != x.device):
+        raise NassegError("{}: tables do not match a resize to {}x{}".format(name, H, W))
+    return x, B, C, h, w, H, W, taps, coef
+
+
+def resize_cubic(x, size, tables=None):
+    """cv2.resize(logits, (W, H), interpolation=INTER_CUBIC) per channel: x B x C x h x w (channels_last, fp32 or
+    bf16) -> fp32 B x C x H x W channels_last, bit-identical to data/datasets.resize_cubic_to; one
+    nasseg_resize_cubic launch.  ``tables``: the pair ``cubic_tables`` returns for this resize."""
+    x, B, C, h, w, H, W, taps, coef = _resize_args("resize_cubic", x, size, tables)
+    y = torch.empty((B, C, H, W), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
+    lib.call(_k("nasseg_resize_cubic", x), ptr(x), B, h, w, C, ptr(taps), ptr(coef), ptr(y), H, W, current_stream())
+    return y
+
+
+def resize_cubic_argmax(x, size, tables=None):
+    """argmax over C of ``resize_cubic(x, size)`` -> uint8 B x H x W (lowest index wins ties), the resized values
+    never stored; at most 256 channels.  One nasseg_resize_cubic_argmax launch."""
+    x, B, C, h, w, H, W, taps, coef = _resize_args("resize_cubic_argmax", x, size, tables)
+    if C > 256:
+        raise NassegError("resize_cubic_argmax: {} channels do not fit uint8 labels".format(C))
+    labels = torch.empty((B, H, W), device=x.device, dtype=torch.uint8)
+    lib.call(_k("nasseg_resize_cubic_argmax", x), ptr(x), B, h, w, C, ptr(taps), ptr(coef), ptr(labels), H, W,
+             current_stream())
+    return labels
+
+
+def prepare_plan(device, B, H, W, dtype=torch.float32):
+    """(desc, taps, lut) of ``prepare_image`` for B images of H x W on ``device``: nasseg_augment's descriptor and
+    tables with an identity plan - one tap per row and column, coefficients (0, 2048, 0, 0), so the fixed-point
+    resize gives every uint8 value back - and the table of the reference's prepare_img (data/device.py).  Cached
+    per (device, B, H, W, dtype); a caller recording the launch into a hipGraph holds on to what it passes."""
+    import numpy as np
+
+    from .data import device as ddev
+
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise NassegError("prepare_image: images are float32 or bfloat16 (got {})".format(dtype))
+
+    def make():
+        axes = []
+        for n in (H, W):
+            c = np.arange(n, dtype=np.int64)
+            axes.append((np.concatenate([np.repeat(c[:, None], 4, axis=1),
+                                         np.broadcast_to(ddev._IDENTITY_COEF, (n, 4))], 1), c))
+        (ty, my), (tx, mx) = axes
+        taps = np.concatenate([ty.ravel(), tx.ravel(), my, mx]).astype(np.int32)
+        desc = np.zeros((B, ddev.DESC_FIELDS), np.int64)
+        desc[:, 0] = np.arange(B, dtype=np.int64) * (H * W * 3)
+        desc[:, 2:6] = (H, W, 3 * W, W)
+        lut = torch.from_numpy(ddev.prepare_img_table()).float().to(dtype)
+        return (torch.from_numpy(desc).to(device), torch.from_numpy(np.tile(taps, (B, 1))).to(device),
+                lut.to(device))
+
+    return _lru(_PREPARE_PLANS, (torch.device(device), int(B), int(H), int(W), dtype), make)
+
+
+def prepare_image(img, dtype=torch.float32, plan=None):
+    """The reference's ``torch.tensor(prepare_img(img).transpose(2, 0, 1)[None]).float()`` on the device, bit for
+    bit: uint8 B x H x W x 3 (device) -> B x 3 x H x W channels_last ``dtype`` (fp32, or bf16 = that tensor
+    rounded), one nasseg_augment launch without a mask.  ``plan``: what ``prepare_plan`` returns for it."""
+    require_device(img)
+    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3 or img.numel() == 0:
+        raise NassegError("prepare_image: expected a uint8 B x H x W x 3 image (got {} {})".format(
+            img.dtype, tuple(img.shape)))
+    B, H, W, _ = img.shape
+    img = img.contiguous()
+    desc, taps, lut = plan if plan is not None else prepare_plan(img.device, B, H, W, dtype)
+    if (lut.dtype != dtype or tuple(desc.shape) != (B, 8) or tuple(taps.shape) != (B, 9 * (H + W))
+            or desc.device != img.device):
+        raise NassegError("prepare_image: the plan does not match a {} batch of {}x{}".format(B, H, W))
+    image = torch.empty((B, 3, H, W), device=img.device, dtype=dtype, memory_format=torch.channels_last)
+    lib.call(_k("nasseg_augment", image), ptr(img), img.numel(), ptr(desc), ptr(taps), ptr(lut), ptr(image), None,
+             B, H, W, current_stream())
+    return image
+
+
 def _apply_library_knobs():
     if _PW_MIN_PIXELS is not None:
         lib.query("nasseg_conv_pw_min_pixels", int(_PW_MIN_PIXELS))
