@@ -7,10 +7,13 @@ synthetic 2048x1024 images, 4 images per GPU, fp32 - BASELINE.json `metric`.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events on
-the launch stream (LaunchProfiler) in extra, untimed steps after the timed
-region; `cpu_baseline` times the CPU oracle (oracle/, the restatement of the
-reference's torch graph) on the host cores of the same box, rank 0, N=1 only.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps,
+writes --dump-outputs and prints the line; `roofline`, `cpu_baseline` and
+`secondary` are null.  With --full it also measures them after the timed region:
+`roofline` live with HIP events on the launch stream (LaunchProfiler) in extra,
+untimed steps (+ the HBM traffic of rocprofv3 PMC passes); `cpu_baseline` times
+the CPU oracle (oracle/, the restatement of the reference's torch graph) on the
+host cores of the same box, rank 0, N=1 only; `secondary` is BASELINE config 2.
 """
 import argparse
 import json
@@ -169,26 +172,13 @@ def algorithmic_flops(name, a):
     return 0
 
 
-def bench_teacher(args, device):
-    """--workload teacher: images/s of the teacher's inference forward and, for the kernel family with the largest
-    share of its time, the achieved fp32 MFMA rate against the 157.3 TFLOP/s peak (MI355X_MICROARCH.md): the
-    teacher's 256-2048-channel 1x1 / 3x3 convs are the one place on this path where the matrix pipe is the roofline."""
+def teacher_roofline(net, x):
+    """For the kernel family with the largest share of the teacher's forward, the achieved fp32 MFMA rate against
+    the 157.3 TFLOP/s peak (MI355X_MICROARCH.md): the teacher's 256-2048-channel 1x1 / 3x3 convs are the one place
+    on this path where the matrix pipe is the roofline.  Two extra forwards with HIP events around every launch."""
     from nas_segm_amd._lib import LaunchProfiler, lib
-    from nas_segm_amd.kd.rf_lw import rf_lw152
 
-    torch.manual_seed(0)
-    net = rf_lw152(pretrained=False, num_classes=21).to(device).eval()
-    x = torch.randn(args.batch, 3, args.height, args.width, device=device).contiguous(memory_format=torch.channels_last)
     with torch.no_grad():
-        for _ in range(args.warmup):
-            net(x)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            out = net(x)
-        torch.cuda.synchronize()
-        elapsed = time.perf_counter() - t0
-        outputs = {"logits": out.cpu()} if args.dump_outputs else None
         lib.profiler = LaunchProfiler()
         net(x)
         net(x)
@@ -216,6 +206,28 @@ def bench_teacher(args, device):
             "families": sorted(((k, v[0], round(v[1], 3), round(v[2] / 1e12 / (v[1] / 1e3), 1) if v[1] > 0 else 0.0)
                                 for k, v in fam.items()), key=lambda r: -r[2])[:6],
             "nasseg_calls_per_step": per}
+    return roof
+
+
+def bench_teacher(args, device):
+    """--workload teacher: images/s of the teacher's inference forward and, with --full, its roofline
+    (teacher_roofline)."""
+    from nas_segm_amd.kd.rf_lw import rf_lw152
+
+    torch.manual_seed(0)
+    net = rf_lw152(pretrained=False, num_classes=21).to(device).eval()
+    x = torch.randn(args.batch, 3, args.height, args.width, device=device).contiguous(memory_format=torch.channels_last)
+    with torch.no_grad():
+        for _ in range(args.warmup):
+            net(x)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            out = net(x)
+        torch.cuda.synchronize()
+        elapsed = time.perf_counter() - t0
+        outputs = {"logits": out.cpu()} if args.dump_outputs else None
+    roof = teacher_roofline(net, x) if args.full else None
     return {"metric": "images/sec (inference forward) KD teacher rf_lw152 {}x{} bs={}".format(
                 args.width, args.height, args.batch),
             "value": args.batch * args.steps / elapsed, "unit": "images/sec", "n_gpus": 1, "rccl_ranks": 1,
@@ -699,18 +711,23 @@ def main():
                          "parameters and parameter gradients are fp32 either way); the BASELINE metric is f32")
     ap.add_argument("--fused-optim", type=int, default=0, choices=(0, 1),
                     help="torch.optim fused=True implementations of SGD / Adam")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: the roofline "
+                         "(extra untimed steps, PMC passes), the CPU baseline, BASELINE config 2 (\"secondary\"), the "
+                         "search713 reward; the options below select among them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--secondary", type=int, default=-1, choices=(-1, 0, 1),
-                    help="also time BASELINE config 2 (CVPR arch0 16x3x321x321, replayed) after the headline and "
-                         "report it as \"secondary\": 1 = yes, 0 = no, -1 = yes for the default 1-GPU headline run")
+                    help="with --full: also time BASELINE config 2 (CVPR arch0 16x3x321x321, replayed) after the "
+                         "headline and report it as \"secondary\": 1 = yes, 0 = no, -1 = yes for the default 1-GPU "
+                         "headline run")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel table to stderr")
+    ap.add_argument("--breakdown", action="store_true", help="with --full: print the per-kernel table to stderr")
     ap.add_argument("--shapes", type=int, default=0,
                     help="with --breakdown: also print the N most expensive (entry point, shape) rows")
     ap.add_argument("--pmc", type=int, default=-1, choices=(-1, 0, 1),
-                    help="HBM traffic of the step from rocprofv3 PMC counters, collected in two extra untimed "
-                         "passes of this command: 1 = yes, 0 = no (the committed profiles/ summary is used while "
-                         "it matches the library), -1 = yes for the default 1-GPU headline run")
+                    help="with --full: HBM traffic of the step from rocprofv3 PMC counters, collected in two extra "
+                         "untimed passes of this command: 1 = yes, 0 = no (the committed profiles/ summary is used "
+                         "while it matches the library), -1 = yes for the default 1-GPU headline run")
     ap.add_argument("--step-times", action="store_true",
                     help="debug: every rank prints the host time of each timed step to stderr")
     ap.add_argument("--sync-each-step", action="store_true",
@@ -728,6 +745,8 @@ def main():
         raise SystemExit("bench.py: --gpus must be >= 1")
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.breakdown or args.shapes or args.pmc == 1 or args.secondary == 1):
+        raise SystemExit("bench.py: --breakdown, --shapes, --pmc 1 and --secondary 1 need --full")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started bare: become the launcher of N ranks (one per GPU) and pass rank 0's line through
         if not args.launch_selftest and not args.same_device:
@@ -920,7 +939,7 @@ def main():
     loss_value = float(loss.item())
     peak_gib = torch.cuda.max_memory_allocated(device) / 2.0 ** 30  # (warm-up + timed steps; before the roofline passes)
     reward = None
-    if args.workload == "search713":
+    if args.full and args.workload == "search713":
         # the candidate's reward on one batch: fused upsample -> argmax -> confusion matrix on the GPU,
         # IoU arithmetic of the Cython module on the host (engine/inference.py)
         from nas_segm_amd.engine.inference import validate
@@ -930,7 +949,7 @@ def main():
 
     roof = None
     rows = []
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # two extra untimed steps with per-launch HIP events; every rank takes them (the step
         # contains the gradient all-reduce), only rank 0 records
         if rank == 0:
@@ -1011,7 +1030,7 @@ def main():
         fence()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "headline":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "headline":
         cpu = cpu_baseline(args.height, args.width)
         # the GPU's inference forward at the same 1x3xHxW, beside the CPU's fwd_only figure
         segmenter.eval()
@@ -1039,9 +1058,9 @@ def main():
         segmenter.train()
 
     secondary = None
-    if rank == 0 and (args.secondary == 1 or (args.secondary == -1 and world == 1 and args.workload == "headline"
-                                              and args.batch == wl[3] and (graph_auto or not args.graph)
-                                              and args.dtype == "f32")):
+    if args.full and rank == 0 and (args.secondary == 1 or (
+            args.secondary == -1 and world == 1 and args.workload == "headline" and args.batch == wl[3]
+            and (graph_auto or not args.graph) and args.dtype == "f32")):
         # (after everything the headline needs: its timed region, roofline passes and CPU baseline are done)
         del segmenter, net, optim_enc, optim_dec
         secondary = secondary_cvpr321(device, rank)

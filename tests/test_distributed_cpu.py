@@ -597,6 +597,14 @@ def test_bench_refuses_a_world_that_is_not_what_was_asked():
         assert out.returncode != 0 and "HIP device" in (out.stderr + out.stdout)
 
 
+def test_bench_refuses_extra_measurements_without_full():
+    # a plain run measures the headline figure only: asking it for one of the --full measurements is refused,
+    # not silently ignored
+    for extra in (["--breakdown"], ["--shapes", "5"], ["--pmc", "1"], ["--secondary", "1"]):
+        out = _run_bench(["--steps", "1"] + extra)
+        assert out.returncode != 0 and "need --full" in (out.stderr + out.stdout), extra
+
+
 def test_bench_dump_outputs_samples_large_outputs_the_same_way_every_time(tmp_path, monkeypatch):
     """bench.py --dump-outputs on the host: float32 .npy files (float64 for float64 and integer arrays), whole while
     they fit the budget, else the same seeded elements of every array in every run; --steps below 1 is refused"""

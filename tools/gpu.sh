@@ -44,7 +44,7 @@ PY
 }
 bench() {  # name args... -> $OUT/name.json, one line
   local n=$1; shift
-  timeout 400 python bench.py --no-cpu-baseline --pmc 0 --secondary 0 "$@" > $OUT/$n.json 2> $OUT/$n.err
+  timeout 400 python bench.py --full --no-cpu-baseline --pmc 0 --secondary 0 "$@" > $OUT/$n.json 2> $OUT/$n.err
   line "$n" $OUT/$n.json | tee -a $SUM
 }
 
@@ -72,7 +72,7 @@ ab)
   VAR=$1; VALS=$2; shift 2
   for rep in 1 2; do for v in $VALS; do
     n="${VAR}_${v}_$(echo "$*" | tr -c 'a-zA-Z0-9' '_')"
-    env $VAR=$v timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --pmc 0 --secondary 0 "$@" > $OUT/$n.json 2> $OUT/$n.err
+    env $VAR=$v timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --pmc 0 --secondary 0 "$@" > $OUT/$n.json 2> $OUT/$n.err
     line "$VAR=$v $*" $OUT/$n.json | tee -a $SUM
   done; done ;;
 workloads)

@@ -23,7 +23,7 @@ if [[ "$WHAT" == "all" || "$WHAT" == "smoke" ]]; then
   echo "smoke exit $?" >> $OUT/summary.log
 fi
 if [[ "$WHAT" == "all" || "$WHAT" == "bench" ]]; then
-  timeout 600 python bench.py --steps 20 --warmup 5 --breakdown --shapes 60 > $OUT/bench.json 2> $OUT/bench.err
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --breakdown --shapes 60 > $OUT/bench.json 2> $OUT/bench.err
   echo "bench exit $?" >> $OUT/summary.log
   cat $OUT/bench.json >> $OUT/summary.log
 fi
@@ -33,24 +33,24 @@ if [[ "$WHAT" == "all" || "$WHAT" == "graph" ]]; then
     echo "bench --graph $g exit $?" >> $OUT/summary.log; cat $OUT/bench_graph$g.json >> $OUT/summary.log
   done
   for wl in depth480; do
-    timeout 300 python bench.py --workload $wl --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 > $OUT/bench_${wl}_g0.json 2> $OUT/bench_${wl}_g0.err
+    timeout 300 python bench.py --full --workload $wl --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 > $OUT/bench_${wl}_g0.json 2> $OUT/bench_${wl}_g0.err
     echo "bench $wl exit $?" >> $OUT/summary.log; cat $OUT/bench_${wl}_g0.json >> $OUT/summary.log
   done
-  timeout 300 python bench.py --workload depth480 --dtype bf16 --graph 2 --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 > $OUT/bench_depth480_bf16_g2.json 2> $OUT/bench_depth480_bf16_g2.err
+  timeout 300 python bench.py --full --workload depth480 --dtype bf16 --graph 2 --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 > $OUT/bench_depth480_bf16_g2.json 2> $OUT/bench_depth480_bf16_g2.err
   echo "bench depth480 bf16 --graph 2 exit $?" >> $OUT/summary.log; cat $OUT/bench_depth480_bf16_g2.json >> $OUT/summary.log
   for wl in headline depth480; do
-    timeout 300 python bench.py --workload $wl --dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 > $OUT/bench_${wl}_bf16.json 2> $OUT/bench_${wl}_bf16.err
+    timeout 300 python bench.py --full --workload $wl --dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 > $OUT/bench_${wl}_bf16.json 2> $OUT/bench_${wl}_bf16.err
     echo "bench $wl bf16 exit $?" >> $OUT/summary.log; cat $OUT/bench_${wl}_bf16.json >> $OUT/summary.log
   done
-  timeout 300 python bench.py --workload task0 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_task0_auto.json 2> $OUT/bench_task0_auto.err
+  timeout 300 python bench.py --full --workload task0 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_task0_auto.json 2> $OUT/bench_task0_auto.err
   echo "bench task0 (auto graph) exit $?" >> $OUT/summary.log; cat $OUT/bench_task0_auto.json >> $OUT/summary.log
-  timeout 300 python bench.py --workload task0 --graph 0 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_task0_g0.json 2> $OUT/bench_task0_g0.err
+  timeout 300 python bench.py --full --workload task0 --graph 0 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_task0_g0.json 2> $OUT/bench_task0_g0.err
   echo "bench task0 --graph 0 exit $?" >> $OUT/summary.log; cat $OUT/bench_task0_g0.json >> $OUT/summary.log
-  timeout 300 python bench.py --workload teacher --steps 8 --warmup 2 > $OUT/bench_teacher.json 2> $OUT/bench_teacher.err
+  timeout 300 python bench.py --full --workload teacher --steps 8 --warmup 2 > $OUT/bench_teacher.json 2> $OUT/bench_teacher.err
   echo "bench teacher exit $?" >> $OUT/summary.log; cat $OUT/bench_teacher.json >> $OUT/summary.log
   for wl in arch1 cvpr321 search713; do
     for g in 0 2; do
-      timeout 300 python bench.py --workload $wl --steps 20 --warmup 5 --graph $g --no-cpu-baseline --secondary 0 > $OUT/bench_${wl}_g$g.json 2> $OUT/bench_${wl}_g$g.err
+      timeout 300 python bench.py --full --workload $wl --steps 20 --warmup 5 --graph $g --no-cpu-baseline --secondary 0 > $OUT/bench_${wl}_g$g.json 2> $OUT/bench_${wl}_g$g.err
       echo "bench $wl --graph $g exit $?" >> $OUT/summary.log; cat $OUT/bench_${wl}_g$g.json >> $OUT/summary.log
     done
   done
