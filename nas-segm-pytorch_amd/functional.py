@@ -72,9 +72,57 @@ def _vec(like, n):
     return torch.empty((int(n),), device=like.device, dtype=torch.float32)
 
 
+def _rows_ws(like, n, C):
+    """Partial rows of a per-channel pair of sums: n rows of 2 C floats, plus 64 rows that nasseg_rows_sum /
+    nasseg_bn_finalize use as the scratch of their two-level reduction (include/nasseg.h, csrc/reduce.hip)"""
+    return _ws(like, (n + 64) * 2 * C)
+
+
 def _bn_parts(stats, n):
     """(mean, invstd, scale, shift): the views of a statistics vector mean | invstd | scale | shift of n channels"""
     return stats[0:n], stats[n:2 * n], stats[2 * n:3 * n], stats[3 * n:]
+
+
+def _scale_shift(stats, n):
+    """(scale, shift) of a statistics vector - (None, None) without one: nothing to apply on load"""
+    return (None, None) if stats is None else (stats[2 * n:3 * n], stats[3 * n:])
+
+
+def _bn_alloc(like, C, training, M, shape):
+    """First half of the forward BatchNorm head: torch's check (same condition, exception class and text as
+    torch.nn.functional.batch_norm), then (stats, its views (mean, invstd, scale, shift)), still to be filled"""
+    if training and M <= 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(
+            tuple(shape)))
+    stats = _vec(like, 4 * C)
+    return stats, _bn_parts(stats, C)
+
+
+def _bn_fill(parts, C, M, bn, training, momentum, eps, x=None, rows=None):
+    """Second half: fill ``parts`` = (mean, invstd, scale, shift) - views of C channels, of a wider vector too - from
+    what the caller has.  Training: the statistics of the M x C tensor ``x`` by a reduction over it, or of the partial
+    rows an epilogue left, ``rows`` = (buffer, count); both move the running buffers of bn = (gamma, beta,
+    running_mean, running_var, num_batches_tracked).  Otherwise the running statistics."""
+    gamma, beta, rm, rv, nbt = bn
+    mean, invstd, scale, shift = parts
+    s = current_stream()
+    if not training:
+        lib.call("nasseg_bn_eval_params", C, float(eps), ptr(gamma), ptr(beta), ptr(rm), ptr(rv), ptr(mean),
+                 ptr(invstd), ptr(scale), ptr(shift), s)
+    elif rows is not None:
+        lib.call("nasseg_bn_finalize", ptr(rows[0]), rows[1], M, C, float(eps), float(momentum), ptr(gamma),
+                 ptr(beta), ptr(mean), ptr(invstd), ptr(scale), ptr(shift), ptr(rm), ptr(rv), ptr(nbt), s)
+    else:
+        ws = _ws(x, lib.query("nasseg_colred_workspace", 1, M, C))
+        lib.call(_k("nasseg_bn_stats", x), ptr(x), C, M, C, float(eps), float(momentum), ptr(gamma), ptr(beta),
+                 ptr(mean), ptr(invstd), ptr(scale), ptr(shift), ptr(rm), ptr(rv), ptr(nbt), ptr(ws), s)
+
+
+def _bn_head(like, C, M, shape, bn, training, momentum, eps, x=None, rows=None):
+    """The forward BatchNorm head in one step: (stats, mean, invstd, scale, shift) of C channels over M pixels"""
+    stats, parts = _bn_alloc(like, C, training, M, shape)
+    _bn_fill(parts, C, M, bn, training, momentum, eps, x, rows)
+    return (stats,) + parts
 
 
 # BatchNorm backward whose apply kernel adds up the partial rows of its sums itself (nasseg_bn_bwd_apply_rows): on the
@@ -784,7 +832,7 @@ def _dw_backward_data(dz, wt, K, x_shape, stride, pad, dil, bn=None):
         nb = lib.query("nasseg_dwconv_bwd_data_bn_blocks", B, C, H, W, K, geom[7], geom[8], dil, geom[10])
         if nb > 0:
             z, scale, shift, mean, invstd, act = bn
-            part = _ws(dz, (nb + 64) * 2 * C)
+            part = _rows_ws(dz, nb, C)
             lib.call(_k("nasseg_dwconv_bwd_data_bn", dz), ptr(dz), ptr(wt), ptr(dx), ptr(z), ptr(scale),
                      ptr(shift), ptr(mean), ptr(invstd), act, *geom, ptr(part), s)
             return dx, (part, nb)
@@ -976,7 +1024,6 @@ class _ChainForward(object):
         BatchNorm with the expanded map never stored (csrc/irdw.hip).  Returns (cur, pend, stats) after op i + 1."""
         op, op2 = self.cfg.ops[i], self.cfg.ops[i + 1]
         _, gamma, beta, rm, rv, nbt = self.prm[i]
-        _, gamma2, beta2, rm2, rv2, nbt2 = self.prm[i + 1]
         w = self.w[i]
         B, K, H, W = cur.shape
         N = w.shape[0]
@@ -990,15 +1037,12 @@ class _ChainForward(object):
         self.keep(i, OP_IR_PW, cur, pend, None, st1)
         Ho, Wo = conv_out_size(H, 3, op2.stride, 1, 1), conv_out_size(W, 3, op2.stride, 1, 1)
         z2 = _new(cur, B, N, Ho, Wo)
-        st2 = _vec(cur, 4 * N)
         rows2 = lib.query("nasseg_irdw_rows", B, H, W, K, N, op2.stride, 0)
-        part2 = _ws(cur, (rows2 + 64) * 2 * N)
+        part2 = _rows_ws(cur, rows2, N)
         lib.call(_k("nasseg_irdw_fwd", cur), ptr(cur), ptr(w), ptr(self.wp[i + 1]), ptr(z2), ptr(psc), ptr(psh),
                  pact, ptr(scale1), ptr(shift1), op.act, B, H, W, K, N, Ho, Wo, op2.stride, ptr(part2), self.s)
-        mean2, invstd2, scale2, shift2 = _bn_parts(st2, N)
-        lib.call("nasseg_bn_finalize", ptr(part2), rows2, B * Ho * Wo, N, float(op2.eps), float(op2.momentum),
-                 ptr(gamma2), ptr(beta2), ptr(mean2), ptr(invstd2), ptr(scale2), ptr(shift2), ptr(rm2), ptr(rv2),
-                 ptr(nbt2), self.s)
+        st2, _, _, scale2, shift2 = _bn_head(cur, N, B * Ho * Wo, z2.shape, self.prm[i + 1][1:], op2.training,
+                                             op2.momentum, op2.eps, rows=(part2, rows2))
         # (its input None: the depthwise conv's input does not exist - backward rebuilds it from op i's)
         self.keep(i + 1, OP_IR_DW, None, (scale1, shift1, op.act), z2, st2)
         return z2, (scale2, shift2, op2.act), st2
@@ -1008,7 +1052,6 @@ class _ChainForward(object):
         i - 1, a SepConv stage's pointwise half (csrc/sepconv.hip; cur, pend: the depthwise half's).
         Returns cur, pend, stats, res."""
         op, w = self.cfg.ops[i], self.w[i]
-        _, gamma, beta, rm, rv, nbt = self.prm[i]
         B, K, H, W = cur.shape
         last = i == len(self.cfg.ops) - 1
         dpend = None
@@ -1041,15 +1084,11 @@ class _ChainForward(object):
         fold = (op.has_bn and not op.training and not self.needs_grad
                 and not (op.kind == "dw" and last and res is not None))
         stats, part, nblk = None, None, 0
-        if op.has_bn:
-            if op.training and M <= 1:
-                raise ValueError("Expected more than 1 value per channel when training, got input "
-                                 "size {}".format((B, N, Ho, Wo)))
-            stats = _vec(cur, 4 * N)
-            mean, invstd, scale, shift = _bn_parts(stats, N)
+        if op.has_bn:  # (eval parameters before the conv, whose epilogue may fold them; statistics after it)
+            stats, parts = _bn_alloc(cur, N, op.training, M, z.shape)
+            scale, shift = parts[2:]
             if not op.training:
-                lib.call("nasseg_bn_eval_params", N, float(op.eps), ptr(gamma), ptr(beta), ptr(rm),
-                         ptr(rv), ptr(mean), ptr(invstd), ptr(scale), ptr(shift), self.s)
+                _bn_fill(parts, N, M, self.prm[i][1:], False, op.momentum, op.eps)
             elif stats_ok:
                 if stage is not None:
                     nblk = lib.query("nasseg_sepconv_blocks", B, K, Ho, Wo, N, dk, dop.stride, dop.dil)
@@ -1057,7 +1096,7 @@ class _ChainForward(object):
                     nblk = lib.query("nasseg_dwconv_stats_blocks", B, N, Ho, Wo, kh, op.stride, op.dil)
                 else:
                     nblk = lib.query("nasseg_conv_fwd_stats_rows", B, Ho, Wo, N, K, kh, kw, op.stride, op.pad, op.dil)
-                part = _ws(cur, (nblk + 64) * 2 * N)
+                part = _rows_ws(cur, nblk, N)
         # inference: BatchNorm (+ act, + residual) folded into the conv's epilogue
         o_sc, o_sh, o_act = (scale, shift, op.act) if fold else (None, None, ACT_NONE)
         o_res = res if (fold and last) else None
@@ -1079,15 +1118,9 @@ class _ChainForward(object):
         self.keep(i, OP_PLAIN, cur, pend, z, stats)
         if fold or not op.has_bn:
             return z, None, stats, (None if (fold and last) else res)
-        if op.training and part is not None:
-            lib.call("nasseg_bn_finalize", ptr(part), nblk, M, N, float(op.eps), float(op.momentum),
-                     ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(scale), ptr(shift),
-                     ptr(rm), ptr(rv), ptr(nbt), self.s)
-        elif op.training:
-            ws = _ws(z, lib.query("nasseg_colred_workspace", 1, M, N))
-            lib.call(_k("nasseg_bn_stats", z), ptr(z), N, M, N, float(op.eps), float(op.momentum),
-                     ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(scale), ptr(shift),
-                     ptr(rm), ptr(rv), ptr(nbt), ptr(ws), self.s)
+        if op.training:
+            _bn_fill(parts, N, M, self.prm[i][1:], True, op.momentum, op.eps, z,
+                     (part, nblk) if part is not None else None)
         return z, (scale, shift, op.act), stats, res
 
     def tail(self, cur, pend, stats, res):
@@ -1199,7 +1232,7 @@ class _ChainBackward(collections.namedtuple("_ChainBackward", "ops recs meta nee
         rows = lib.query("nasseg_irdw_rows", Bc, H, W, K1, K, op.stride, 1)
         dwt = torch.empty_like(r.w)
         ws = _ws(fl.g, rows * 9 * K)
-        part = _ws(fl.g, (rows + 64) * 2 * K)
+        part = _rows_ws(fl.g, rows, K)
         g_in = _new(fl.g, Bc, K, H, W)
         lib.call(_k("nasseg_irdw_bwd", x_in), ptr(x_in), ptr(w1), ptr(fl.g), ptr(r.z), ptr(r.wb), int(op.stride == 1),
                  ptr(g_in), _finish_wgrad(ws, dwt, 9, K, 1, 0), ptr(ws), ptr(xpsc), ptr(xpsh), self.meta[i - 1][1],
@@ -1217,7 +1250,7 @@ class _ChainBackward(collections.namedtuple("_ChainBackward", "ops recs meta nee
         zp, psc_, psh_, pmu_, pis_, pact_ = self.producer_bn(i, K)
         dwt = torch.empty_like(r.w)
         ws = _ws(r.x, rows * 9 * K)
-        part = _ws(r.x, (rows + 64) * 2 * K)
+        part = _rows_ws(r.x, rows, K)
         g_in = _new(r.x, Bc, K, H, W)
         lib.call(_k("nasseg_dwconv_bwd_bn", r.x), ptr(r.x), ptr(fl.g), ptr(r.z), ptr(r.wb), int(op.stride == 1),
                  ptr(g_in), _finish_wgrad(ws, dwt, 9, K, 1, 0), ptr(ws), ptr(psc_), ptr(psh_), ptr(pmu_),
@@ -1256,7 +1289,7 @@ class _ChainBackward(collections.namedtuple("_ChainBackward", "ops recs meta nee
         skip_g = fl.dres if (self.fuse_res and i == 0 and K % 4 == 0) else None  # (x is also the block's skip)
         if behind_bn and K <= 64:
             pmu_, pis_ = _bn_parts(self.recs[i - 1].stats, K)[:2]
-            part = _ws(r.x, (nsl + 64) * 2 * K)
+            part = _rows_ws(r.x, nsl, K)
         # (z only where the kernel loads it: where it rebuilds z = W x the argument is NULL - an explicit
         #  contract instead of a pointer the kernel ignores, and NULL is also what says "never stored")
         z_arg = r.z if (r.z is not None and lib.query("nasseg_conv_pw_bwd_reads_z", Bc, H, W, K, N)) else None
@@ -1293,7 +1326,7 @@ class _ChainBackward(collections.namedtuple("_ChainBackward", "ops recs meta nee
             zp, psc_, psh_, pmu_, pis_, pact_ = bn_prev
             pw1 = kh == 1 and kw == 1 and op.stride == 1 and op.pad == 0
             nb = lib.query("nasseg_conv_fwd_stats_blocks", Bc, H, W, K, N, 2 * int(pw1)) if pmu_ is not None else 0
-            part = _ws(r.x, (nb + 64) * 2 * K) if nb else None
+            part = _rows_ws(r.x, nb, K) if nb else None
             lib.call(_k("nasseg_conv_bwd_data_bn", dz), ptr(dz), N, ptr(r.wb), ptr(g), K, ptr(zp), K,
                      ptr(psc_), ptr(psh_), ptr(pmu_), ptr(pis_), pact_, Bc, Ho, Wo, N, H, W,
                      K, kh, kw, op.stride, op.pad, op.dil, ptr(part), self.s)
@@ -1351,8 +1384,7 @@ class _ConvChain(torch.autograd.Function):
         if cfg.in_pact is not None:
             # the input is another chain's Pending: its BatchNorm + activation are op 0's prologue; backward returns
             # the gradient w.r.t. the ACTIVATED input - exactly what a plain backward-data of op 0 computes
-            _, _, scale, shift = _bn_parts(tensors[-1], x.shape[1])
-            pend = (scale, shift, cfg.in_pact)
+            pend = _scale_shift(tensors[-1], x.shape[1]) + (cfg.in_pact,)
         f = _ChainForward(cfg, x, tensors, needs_grad, ctx.needs_input_grad[1])
         ops, n = cfg.ops, len(cfg.ops)
         cur, stats, i = x, None, 0
@@ -1433,7 +1465,7 @@ def _pool_backward(pool, fl, last, pool_idx, pool_fused):
                  g.shape[2], g.shape[3], pk, ps, pp, s)
         return fl._replace(g=g_full)
     mean, invstd = _bn_parts(last.stats, Np)[:2]
-    part = _ws(g, (nb + 64) * 2 * Np)
+    part = _rows_ws(g, nb, Np)
     lib.call(_k("nasseg_maxpool_bn_bwd", g), ptr(g), ptr(pool_idx), ptr(last.z), ptr(mean), ptr(invstd),
              ptr(g_full), ptr(part), Bp, Hz, Wz, Np, g.shape[2], g.shape[3], ps, pp, s)
     return fl._replace(g=g_full, rows=(part, nb))
@@ -1480,8 +1512,8 @@ class Pending(object):
         self.z, self.stats, self.act = z, stats, int(act)  # stats: mean | invstd | scale | shift, C each
         self._mat = None
 
-    scale = property(lambda self: _bn_parts(self.stats, self.z.shape[1])[2])
-    shift = property(lambda self: _bn_parts(self.stats, self.z.shape[1])[3])
+    scale = property(lambda self: _scale_shift(self.stats, self.z.shape[1])[0])
+    shift = property(lambda self: _scale_shift(self.stats, self.z.shape[1])[1])
     shape = property(lambda self: self.z.shape)
     dtype = property(lambda self: self.z.dtype)
     device = property(lambda self: self.z.device)
@@ -1541,7 +1573,7 @@ class _Junction(torch.autograd.Function):
         C = z.shape[1]
         fin = None
         if n_fin:
-            fin = z if stats is None else _affine_act(z, *_bn_parts(stats, C)[2:], None, act)
+            fin = z if stats is None else _affine_act(z, *_scale_shift(stats, C), None, act)
         outs = [z.view_as(z) for _ in range(n_raw)] + [fin.view_as(fin) for _ in range(n_fin)]
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(z if stats is not None else None, stats)
@@ -1574,7 +1606,7 @@ class _Junction(torch.autograd.Function):
             live.insert(0, part_sum)
         # (a pending node whose only gradient came from one consumer: the mask and the rows alone, n = 1)
         out = torch.empty(shape, device=device, dtype=dtype, memory_format=torch.channels_last)
-        rows = _ws(out, (nrows + 64) * 2 * C) if (stats is not None and FUSE_TAIL_ROWS) else None
+        rows = _rows_ws(out, nrows, C) if (stats is not None and FUSE_TAIL_ROWS) else None
         args = [ptr(g) for g in live] + [None] * (_JUNCTION_MAX - len(live))
         lib.call(_k("nasseg_grad_junction", out), *(args + [len(live), ptr(z) if stats is not None else None,
                  ptr(stats), act, ptr(out), ptr(rows), B, H, W, C, s]))
@@ -1647,24 +1679,8 @@ class _BatchNormAct(torch.autograd.Function):
                 residual):
         x = _cl(x)
         B, C, H, W = x.shape
-        M = B * H * W
-        s = current_stream()
-        stats = _vec(x, 4 * C)  # mean | invstd | scale | shift
-        mean, invstd, scale, shift = _bn_parts(stats, C)
-        if training:
-            if M <= 1:
-                # same condition and exception class as torch.nn.functional.batch_norm
-                raise ValueError(
-                    "Expected more than 1 value per channel when training, got input size {}".format(
-                        tuple(x.shape)))
-            ws = _ws(x, lib.query("nasseg_colred_workspace", 1, M, C))
-            lib.call(_k("nasseg_bn_stats", x), ptr(x), C, M, C, float(eps), float(momentum), ptr(gamma),
-                     ptr(beta), ptr(mean), ptr(invstd), ptr(scale), ptr(shift), ptr(running_mean),
-                     ptr(running_var), ptr(nbt), ptr(ws), s)
-        else:
-            lib.call("nasseg_bn_eval_params", C, float(eps), ptr(gamma), ptr(beta),
-                     ptr(running_mean), ptr(running_var), ptr(mean), ptr(invstd), ptr(scale),
-                     ptr(shift), s)
+        stats, _, _, scale, shift = _bn_head(x, C, B * H * W, x.shape, (gamma, beta, running_mean, running_var, nbt),
+                                             training, momentum, eps, x)
         res = _cl(residual) if residual is not None else None
         y = _affine_act(x, scale, shift, res, act)
         ctx.save_for_backward(x, stats)
@@ -1842,6 +1858,43 @@ def concat_resize(tensors, size, relu=False):
     return _ConcatResize.apply(int(size[0]), int(size[1]), ACT_RELU if relu else ACT_NONE, *tensors)
 
 
+def _bn_relu_pw_forward(x, scale, shift, wp, N, res=None):
+    """conv1x1(relu(scale * x + shift)) (+ res) with the BatchNorm + ReLU applied as the conv loads x (the normalised
+    map is never written); wp: the (N, C, 1, 1) weight packed for the forward (_pack_dense mode 0)"""
+    B, C, H, W = x.shape
+    out = _new(x, B, N, H, W)
+    lib.call(_k("nasseg_conv_fwd", x), ptr(x), C, ptr(wp), ptr(out), N, ptr(scale), ptr(shift), ACT_RELU, None, None,
+             ACT_NONE, ptr(res), N if res is not None else 0, B, H, W, C, H, W, N, 1, 1, 1, 0, 1, 0, None,
+             current_stream())
+    return out
+
+
+def _bn_relu_pw_backward(dout, x, parts, wb):
+    """Backward of _bn_relu_pw_forward up to the BatchNorm: the backward-data kernel (wb: the weight packed mode 1)
+    leaves g = relu'(bn(x)) * backward_data(dout) with the rows of the BatchNorm-backward sums {sum g, sum g * xhat} -
+    no reduction pass over gradient and x.  Returns (g, sums); parts = (mean, invstd, scale, shift)."""
+    mean, invstd, scale, shift = parts
+    B, C, H, W = x.shape
+    N = dout.shape[1]
+    s = current_stream()
+    nb = lib.query("nasseg_conv_fwd_stats_blocks", B, H, W, C, N, 2)
+    g = _new(x, B, C, H, W)
+    part = _rows_ws(x, nb, C)
+    lib.call(_k("nasseg_conv_bwd_data_bn", dout), ptr(dout), N, ptr(wb), ptr(g), C, ptr(x), C, ptr(scale), ptr(shift),
+             ptr(mean), ptr(invstd), ACT_RELU, B, H, W, N, H, W, C, 1, 1, 1, 0, 1, ptr(part), s)
+    sums = _vec(x, 2 * C)
+    lib.call("nasseg_rows_sum", ptr(part), nb, 2 * C, ptr(sums), s)
+    return g, sums
+
+
+def _bn_relu_pw_dx(g, x, parts, sums, training):
+    """dx of the plain BatchNorm backward from what _bn_relu_pw_backward left (g arrived masked: ACT_NONE, the rule of
+    _ChainBackward.bn_head)"""
+    mean, invstd, scale, shift = parts
+    B, C, H, W = x.shape
+    return _bn_bwd_apply(g, x, scale, shift, mean, invstd, sums, B * H * W, C, training, ACT_NONE, torch.empty_like(x))
+
+
 class _CatBNReluConv(torch.autograd.Function):
     """ConcatReduce's tail, cat(x, y) -> BatchNorm(2C) -> ReLU -> 1x1 conv (2C -> N)
     (src/nn/layer_factory.py:369-382), WITHOUT the concatenation: BatchNorm is per channel and
@@ -1849,10 +1902,9 @@ class _CatBNReluConv(torch.autograd.Function):
 
         out = W[:, :C] . relu(bn_lo(x)) + W[:, C:] . relu(bn_hi(y))
 
-    Two pointwise convs, each applying its half of the BatchNorm on load (the second adds the
+    Two pointwise convs (_bn_relu_pw_*), each over its half of the BatchNorm (the second adds the
     first's output in its epilogue); neither the 2C-channel slab nor its normalised copy is ever
-    written, and the backward needs no slicing: each half's backward-data kernel emits the
-    masked gradient with its BatchNorm-backward sums.  Used for large maps (a few more, smaller
+    written, and the backward needs no slicing.  Used for large maps (a few more, smaller
     launches than the slab path)."""
 
     @staticmethod
@@ -1865,35 +1917,22 @@ class _CatBNReluConv(torch.autograd.Function):
             raise NassegError("cat_bn_relu_conv: shapes {} {} {}".format(
                 tuple(x.shape), tuple(y.shape), tuple(w.shape)))
         M = B * H * W
-        s = current_stream()
         needs_grad = grad_mode and any(ctx.needs_input_grad)  # (grad_mode: the caller's, see _ConvChain)
-        stats = _vec(x, 8 * C)  # [mean | invstd | scale | shift] x [2C]
-        mean, invstd, scale, shift = _bn_parts(stats, 2 * C)
+        stats, parts = _bn_alloc(x, 2 * C, training, M, (B, 2 * C, H, W))  # [mean | invstd | scale | shift] x [2C]
         if training:
-            if M <= 1:
-                raise ValueError("Expected more than 1 value per channel when training, got input "
-                                 "size {}".format((B, 2 * C, H, W)))
-            ws = _ws(x, lib.query("nasseg_colred_workspace", 1, M, C))
-            for h, t in enumerate((x, y)):
-                lo, hi = h * C, (h + 1) * C
-                lib.call(_k("nasseg_bn_stats", t), ptr(t), C, M, C, float(eps), float(momentum), ptr(gamma[lo:hi]),
-                         ptr(beta[lo:hi]), ptr(mean[lo:hi]), ptr(invstd[lo:hi]), ptr(scale[lo:hi]),
-                         ptr(shift[lo:hi]), ptr(rm[lo:hi]) if rm is not None else None,
-                         ptr(rv[lo:hi]) if rv is not None else None,
-                         ptr(nbt) if (nbt is not None and h == 0) else None, ptr(ws), s)
+            # each half's statistics into its columns of the 2C vector; num_batches_tracked moves once, with the first
+            for lo, t, n in ((0, x, nbt), (C, y, None)):
+                cols = [None if v is None else v[lo:lo + C] for v in (gamma, beta, rm, rv)] + [n]
+                _bn_fill([v[lo:lo + C] for v in parts], C, M, cols, True, momentum, eps, t)
         else:
-            lib.call("nasseg_bn_eval_params", 2 * C, float(eps), ptr(gamma), ptr(beta), ptr(rm), ptr(rv),
-                     ptr(mean), ptr(invstd), ptr(scale), ptr(shift), s)
+            _bn_fill(parts, 2 * C, M, (gamma, beta, rm, rv, nbt), False, momentum, eps)
+        scale, shift = parts[2:]
         items = [(w, 0, 0, C), (w, 0, C, C)]
         if needs_grad:
             items += [(w, 1, 0, C), (w, 1, C, C)]
         packed = _pack_many(x, items)
-        y1 = _new(x, B, N, H, W)
-        lib.call(_k("nasseg_conv_fwd", x), ptr(x), C, ptr(packed[0]), ptr(y1), N, ptr(scale[0:C]), ptr(shift[0:C]),
-                 ACT_RELU, None, None, ACT_NONE, None, 0, B, H, W, C, H, W, N, 1, 1, 1, 0, 1, 0, None, s)
-        out = _new(x, B, N, H, W)
-        lib.call(_k("nasseg_conv_fwd", y), ptr(y), C, ptr(packed[1]), ptr(out), N, ptr(scale[C:]), ptr(shift[C:]),
-                 ACT_RELU, None, None, ACT_NONE, ptr(y1), N, B, H, W, C, H, W, N, 1, 1, 1, 0, 1, 0, None, s)
+        y1 = _bn_relu_pw_forward(x, scale[0:C], shift[0:C], packed[0], N)
+        out = _bn_relu_pw_forward(y, scale[C:], shift[C:], packed[1], N, y1)
         if needs_grad:
             ctx.save_for_backward(x, y, stats, packed[2], packed[3])
             ctx.cfg = (bool(training), N)
@@ -1905,40 +1944,30 @@ class _CatBNReluConv(torch.autograd.Function):
         training, N = ctx.cfg
         dout = _cl(dout)
         B, C, H, W = x.shape
-        M = B * H * W
         s = current_stream()
-        mean, invstd, scale, shift = _bn_parts(stats, 2 * C)
+        parts = _bn_parts(stats, 2 * C)
         need_w = ctx.needs_input_grad[7]
         need_bn = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
         dbn = _vec(x, 4 * C) if need_bn else None  # [dbeta(2C) | dgamma(2C)]
         dw = torch.empty((N, 2 * C, 1, 1), device=x.device, dtype=torch.float32) if need_w else None
-        nb = lib.query("nasseg_conv_fwd_stats_blocks", B, H, W, C, N, 2)
         grads_in = [None, None]
         for h, (t, wb) in enumerate(((x, wb_lo), (y, wb_hi))):
-            lo, hi = h * C, (h + 1) * C
-            need_dx = ctx.needs_input_grad[h]
-            sc, sh, mu, isd = scale[lo:hi], shift[lo:hi], mean[lo:hi], invstd[lo:hi]
-            if need_dx or need_bn:
-                g = _new(x, B, C, H, W)
-                part = _ws(x, (nb + 64) * 2 * C)
-                lib.call(_k("nasseg_conv_bwd_data_bn", dout), ptr(dout), N, ptr(wb), ptr(g), C, ptr(t), C, ptr(sc),
-                         ptr(sh), ptr(mu), ptr(isd), ACT_RELU, B, H, W, N, H, W, C, 1, 1, 1, 0, 1,
-                         ptr(part), s)
-                sums = _vec(x, 2 * C)
-                lib.call("nasseg_rows_sum", ptr(part), nb, 2 * C, ptr(sums), s)
-                if need_bn:  # sums = [sum g | sum g*xhat] -> rows (dbeta, dgamma) of dbn at columns lo..hi
+            lo = h * C
+            half = [v[lo:lo + C] for v in parts]
+            if ctx.needs_input_grad[h] or need_bn:
+                g, sums = _bn_relu_pw_backward(dout, t, half, wb)
+                if need_bn:  # sums = [sum g | sum g*xhat] -> rows (dbeta, dgamma) of dbn at columns lo..lo + C
                     lib.call(_k("nasseg_chan_copy", sums), ptr(sums), C, 0, ptr(dbn), 2 * C, lo, None, 0, 0, 2, C,
                              ACT_NONE, ACT_NONE, s)
-                if need_dx:
-                    dz = torch.empty_like(t)
-                    lib.call(_k("nasseg_bn_bwd_apply", g), ptr(g), ptr(t), ptr(sc), ptr(sh), ptr(mu), ptr(isd),
-                             ptr(sums), M, C, int(training), ACT_RELU, ptr(dz), s)
-                    grads_in[h] = dz
+                if ctx.needs_input_grad[h]:
+                    grads_in[h] = _bn_relu_pw_dx(g, t, half, sums, training)
             if need_w:
+                # (launched here and not through _dense_wgrad: a half's gradient is gathered into dw's columns by the
+                #  copy below, which a finalisation deferred to the end of backward - deferred_wgrad - would come after)
                 dwh = _vec(x, N * C)
                 ws = _ws(x, lib.query("nasseg_conv_wgrad_workspace", B, H, W, N, C, 1, 1))
-                lib.call(_k("nasseg_conv_wgrad", t), ptr(t), C, ptr(dout), N, ptr(dwh), ptr(ws), ptr(sc), ptr(sh),
-                         ACT_RELU, B, H, W, C, H, W, N, 1, 1, 1, 0, 1, s)
+                lib.call(_k("nasseg_conv_wgrad", t), ptr(t), C, ptr(dout), N, ptr(dwh), ptr(ws), ptr(half[2]),
+                         ptr(half[3]), ACT_RELU, B, H, W, C, H, W, N, 1, 1, 1, 0, 1, s)
                 lib.call(_k("nasseg_chan_copy", dwh), ptr(dwh), C, 0, ptr(dw), 2 * C, lo, None, 0, 0, N, C, ACT_NONE,
                          ACT_NONE, s)
         dgamma = dbn[2 * C:4 * C] if ctx.needs_input_grad[2] else None
@@ -1955,10 +1984,8 @@ def cat_bn_relu_conv(x, y, gamma, beta, running_mean, running_var, num_batches_t
 
 class _BNReluConv(torch.autograd.Function):
     """BatchNorm -> ReLU -> 1x1 conv over ONE tensor (ConcatReduce's tail on its concat slab,
-    src/nn/layer_factory.py:369-382, below the size where the slab is avoided altogether): the conv applies
-    the BatchNorm on load, so the normalised slab is never written; backward, the backward-data kernel emits
-    the masked gradient with the BatchNorm-backward sums (no reduction pass over gradient and slab).  The
-    single-input form of _CatBNReluConv."""
+    src/nn/layer_factory.py:369-382, below the size where the slab is avoided altogether): _bn_relu_pw_* over
+    the tensor's own statistics.  The single-input form of _CatBNReluConv."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, rm, rv, nbt, weight, training, momentum, eps, grad_mode):
@@ -1968,28 +1995,11 @@ class _BNReluConv(torch.autograd.Function):
         w = weight.contiguous()
         if tuple(w.shape) != (N, C, 1, 1):
             raise NassegError("bn_relu_conv: shapes {} {}".format(tuple(x.shape), tuple(w.shape)))
-        M = B * H * W
-        s = current_stream()
         needs_grad = grad_mode and any(ctx.needs_input_grad)
-        stats = _vec(x, 4 * C)  # mean | invstd | scale | shift
-        mean, invstd, scale, shift = _bn_parts(stats, C)
-        if training:
-            if M <= 1:
-                raise ValueError("Expected more than 1 value per channel when training, got input "
-                                 "size {}".format((B, C, H, W)))
-            ws = _ws(x, lib.query("nasseg_colred_workspace", 1, M, C))
-            lib.call(_k("nasseg_bn_stats", x), ptr(x), C, M, C, float(eps), float(momentum), ptr(gamma), ptr(beta),
-                     ptr(mean), ptr(invstd), ptr(scale), ptr(shift), ptr(rm), ptr(rv), ptr(nbt), ptr(ws), s)
-        else:
-            lib.call("nasseg_bn_eval_params", C, float(eps), ptr(gamma), ptr(beta), ptr(rm), ptr(rv),
-                     ptr(mean), ptr(invstd), ptr(scale), ptr(shift), s)
-        items = [(w, 0)]
-        if needs_grad:
-            items.append((w, 1))
-        packed = _pack_many(x, items)
-        out = _new(x, B, N, H, W)
-        lib.call(_k("nasseg_conv_fwd", x), ptr(x), C, ptr(packed[0]), ptr(out), N, ptr(scale), ptr(shift),
-                 ACT_RELU, None, None, ACT_NONE, None, 0, B, H, W, C, H, W, N, 1, 1, 1, 0, 1, 0, None, s)
+        stats, _, _, scale, shift = _bn_head(x, C, B * H * W, x.shape, (gamma, beta, rm, rv, nbt), training, momentum,
+                                             eps, x)
+        packed = _pack_many(x, [(w, 0), (w, 1)] if needs_grad else [(w, 0)])
+        out = _bn_relu_pw_forward(x, scale, shift, packed[0], N)
         if needs_grad:
             ctx.save_for_backward(x, stats, packed[1], w)
             ctx.cfg = (bool(training), N)
@@ -2001,30 +2011,16 @@ class _BNReluConv(torch.autograd.Function):
         training, N = ctx.cfg
         dout = _cl(dout)
         B, C, H, W = x.shape
-        M = B * H * W
-        s = current_stream()
-        mean, invstd, scale, shift = _bn_parts(stats, C)
-        need_dx = ctx.needs_input_grad[0]
-        need_bn = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        parts = _bn_parts(stats, C)
         dx = dgamma = dbeta = dw = None
-        if need_dx or need_bn:
-            nb = lib.query("nasseg_conv_fwd_stats_blocks", B, H, W, C, N, 2)
-            g = _new(x, B, C, H, W)
-            part = _ws(x, (nb + 64) * 2 * C)
-            lib.call(_k("nasseg_conv_bwd_data_bn", dout), ptr(dout), N, ptr(wb), ptr(g), C, ptr(x), C, ptr(scale),
-                     ptr(shift), ptr(mean), ptr(invstd), ACT_RELU, B, H, W, N, H, W, C, 1, 1, 1, 0, 1, ptr(part), s)
-            sums = _vec(x, 2 * C)
-            lib.call("nasseg_rows_sum", ptr(part), nb, 2 * C, ptr(sums), s)
-            if ctx.needs_input_grad[1]:
-                dgamma = sums[C:2 * C]
-            if ctx.needs_input_grad[2]:
-                dbeta = sums[0:C]
-            if need_dx:
-                dx = torch.empty_like(x)
-                lib.call(_k("nasseg_bn_bwd_apply", g), ptr(g), ptr(x), ptr(scale), ptr(shift), ptr(mean), ptr(invstd),
-                         ptr(sums), M, C, int(training), ACT_NONE, ptr(dx), s)
+        if any(ctx.needs_input_grad[0:3]):
+            g, sums = _bn_relu_pw_backward(dout, x, parts, wb)
+            dgamma = sums[C:2 * C] if ctx.needs_input_grad[1] else None
+            dbeta = sums[0:C] if ctx.needs_input_grad[2] else None
+            if ctx.needs_input_grad[0]:
+                dx = _bn_relu_pw_dx(g, x, parts, sums, training)
         if ctx.needs_input_grad[6]:
-            dw = _dense_wgrad(x, dout, w, scale, shift, ACT_RELU, (B, H, W, C, H, W, N, 1, 1, 1, 0, 1))
+            dw = _dense_wgrad(x, dout, w, parts[2], parts[3], ACT_RELU, (B, H, W, C, H, W, N, 1, 1, 1, 0, 1))
         return dx, dgamma, dbeta, None, None, None, dw, None, None, None, None
 
 
@@ -2033,9 +2029,9 @@ class _CatReduce(torch.autograd.Function):
     cat(x, y) -> BatchNorm(2C) -> ReLU -> 1x1 conv.  Each input is written into its half of the slab by one
     launch (nasseg_cat_src_fwd) that resizes it when its size differs, applies the producer's pending
     BatchNorm + activation on load (Pending: the producers' normalised outputs are never written) and emits
-    the slab's BatchNorm statistics as partial rows - no pass over the slab for them; the conv applies the
-    slab's BatchNorm + ReLU on load (_BNReluConv).  Backward: the backward-data kernel leaves the masked
-    gradient + the slab BatchNorm's sums; nasseg_cat_src_bwd then applies that BatchNorm's backward per input
+    the slab's BatchNorm statistics as partial rows - no pass over the slab for them; the conv is
+    _bn_relu_pw_forward over the slab.  Backward: _bn_relu_pw_backward leaves the masked gradient + the slab
+    BatchNorm's sums; nasseg_cat_src_bwd then applies that BatchNorm's backward per input
     slice (no full-width slab gradient), and for a pending input of the slab's size also masks with its
     activation's derivative and emits the producer's BatchNorm-backward sums (_TAIL_ROWS).  The gradient
     returned for a Pending input is the one w.r.t. its activated output (the producer chain's backward takes
@@ -2057,31 +2053,17 @@ class _CatReduce(torch.autograd.Function):
         M = B * Ho * Wo
         s = current_stream()
         needs_grad = grad_mode and any(ctx.needs_input_grad)
-        stats = _vec(x, 4 * Ct)  # mean | invstd | scale | shift
-        mean, invstd, scale, shift = _bn_parts(stats, Ct)
-        if training and M <= 1:
-            raise ValueError("Expected more than 1 value per channel when training, got input "
-                             "size {}".format((B, Ct, Ho, Wo)))
+        stats, parts = _bn_alloc(x, Ct, training, M, (B, Ct, Ho, Wo))
         slab = _new(x, B, Ct, Ho, Wo)
         nblk = lib.query("nasseg_cat_src_blocks", B, Ho, Wo, C)
-        part = _ws(x, (nblk + 64) * 2 * Ct) if training else None
+        part = _rows_ws(x, nblk, Ct) if training else None
         for off, (t, st, act) in enumerate(((x, xst, act_x), (y, yst, act_y))):
-            sc, sh = _bn_parts(st, C)[2:] if st is not None else (None, None)
+            sc, sh = _scale_shift(st, C)
             lib.call(_k("nasseg_cat_src_fwd", t), ptr(t), ptr(sc), ptr(sh), act if st is not None else ACT_NONE,
                      ptr(slab), Ct, off * C, ptr(part), B, t.shape[2], t.shape[3], C, Ho, Wo, s)
-        if training:
-            lib.call("nasseg_bn_finalize", ptr(part), nblk, M, Ct, float(eps), float(momentum), ptr(gamma),
-                     ptr(beta), ptr(mean), ptr(invstd), ptr(scale), ptr(shift), ptr(rm), ptr(rv), ptr(nbt), s)
-        else:
-            lib.call("nasseg_bn_eval_params", Ct, float(eps), ptr(gamma), ptr(beta), ptr(rm), ptr(rv),
-                     ptr(mean), ptr(invstd), ptr(scale), ptr(shift), s)
-        items = [(w, 0)]
-        if needs_grad:
-            items.append((w, 1))
-        packed = _pack_many(x, items)
-        out = _new(x, B, N, Ho, Wo)
-        lib.call(_k("nasseg_conv_fwd", slab), ptr(slab), Ct, ptr(packed[0]), ptr(out), N, ptr(scale), ptr(shift),
-                 ACT_RELU, None, None, ACT_NONE, None, 0, B, Ho, Wo, Ct, Ho, Wo, N, 1, 1, 1, 0, 1, 0, None, s)
+        _bn_fill(parts, Ct, M, (gamma, beta, rm, rv, nbt), training, momentum, eps, rows=(part, nblk))
+        packed = _pack_many(x, [(w, 0), (w, 1)] if needs_grad else [(w, 0)])
+        out = _bn_relu_pw_forward(slab, parts[2], parts[3], packed[0], N)
         if needs_grad:
             # (x / y: the producers' raw outputs - they hold them for their own backward anyway)
             ctx.save_for_backward(slab, stats, packed[1], w, x if xst is not None else None,
@@ -2098,23 +2080,14 @@ class _CatReduce(torch.autograd.Function):
         B, Ct, Ho, Wo = slab.shape
         C = Ct // 2
         s = current_stream()
-        mean, invstd, scale, shift = _bn_parts(stats, Ct)
+        mean, invstd, scale, shift = parts = _bn_parts(stats, Ct)
         need_in = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         need_bn = ctx.needs_input_grad[5] or ctx.needs_input_grad[6]
         dx = dy = dgamma = dbeta = dw = None
         if need_in or need_bn:
-            nb = lib.query("nasseg_conv_fwd_stats_blocks", B, Ho, Wo, Ct, N, 2)
-            g = _new(slab, B, Ct, Ho, Wo)
-            part = _ws(slab, (nb + 64) * 2 * Ct)
-            lib.call(_k("nasseg_conv_bwd_data_bn", dout), ptr(dout), N, ptr(wb), ptr(g), Ct, ptr(slab), Ct,
-                     ptr(scale), ptr(shift), ptr(mean), ptr(invstd), ACT_RELU, B, Ho, Wo, N, Ho, Wo, Ct, 1, 1, 1, 0,
-                     1, ptr(part), s)
-            sums = _vec(slab, 2 * Ct)
-            lib.call("nasseg_rows_sum", ptr(part), nb, 2 * Ct, ptr(sums), s)
-            if ctx.needs_input_grad[5]:
-                dgamma = sums[Ct:2 * Ct]
-            if ctx.needs_input_grad[6]:
-                dbeta = sums[0:Ct]
+            g, sums = _bn_relu_pw_backward(dout, slab, parts, wb)
+            dgamma = sums[Ct:2 * Ct] if ctx.needs_input_grad[5] else None
+            dbeta = sums[0:Ct] if ctx.needs_input_grad[6] else None
             if need_in:
                 nrows = lib.query("nasseg_cat_src_blocks", B, Ho, Wo, C)
                 grads = []
@@ -2130,7 +2103,7 @@ class _CatReduce(torch.autograd.Function):
                     # mask and nasseg_bilinear_bwd_act masks the gradient it transposes
                     # (a producer SMALLER than the slab keeps its own reduction pass: over its few pixels that is
                     #  cheaper than four taps of z per slab pixel - 3 launches of the headline step, +15 us each)
-                    rows = (_ws(slab, (nrows + 64) * 2 * C)
+                    rows = (_rows_ws(slab, nrows, C)
                             if (st is not None and FUSE_TAIL_ROWS and H * W >= Ho * Wo) else None)
                     d = _new(slab, B, C, Ho, Wo)
                     lib.call(_k("nasseg_cat_src_bwd", g), ptr(g), ptr(slab), Ct, off * C, ptr(scale), ptr(mean),
@@ -2142,7 +2115,7 @@ class _CatReduce(torch.autograd.Function):
                         nws = lib.query("nasseg_bilinear_bwd_workspace", B, H, W, C, Ho, Wo)
                         ws = ptr(_ws(d, nws)) if nws else None
                         if rows is not None:
-                            _, _, sc, sh = _bn_parts(st, C)
+                            sc, sh = _scale_shift(st, C)
                             lib.call(_k("nasseg_bilinear_bwd_act", d), ptr(d), C, 0, ptr(z), ptr(sc), ptr(sh), act,
                                      ptr(full), B, H, W, C, Ho, Wo, ws, s)
                         else:
@@ -2201,6 +2174,19 @@ class _Add(torch.autograd.Function):
         return dy, dy
 
 
+def _add_act2(who, za, sta, act_a, a, zb, stb, act_b, b):
+    """a[c] * act_a(bn_a(za)) + b[c] * act_b(bn_b(zb)) in one launch: the BatchNorms of the statistics vectors sta /
+    stb (None: a finished map) are applied as the raw conv outputs are loaded; a / b None: unit coefficients"""
+    if za.shape != zb.shape:
+        raise NassegError("{}: shapes {} and {} differ".format(who, tuple(za.shape), tuple(zb.shape)))
+    C = za.shape[1]
+    y = torch.empty_like(za)
+    (sa, ha), (sb, hb) = _scale_shift(sta, C), _scale_shift(stb, C)
+    lib.call(_k("nasseg_add_act2", za), ptr(za), ptr(sa), ptr(ha), act_a, ptr(a), ptr(zb), ptr(sb), ptr(hb), act_b,
+             ptr(b), ptr(y), za.numel(), C, current_stream())
+    return y
+
+
 class _AddPending(torch.autograd.Function):
     """a + b where one or both are conv-chain outputs with a pending BatchNorm + activation (Pending): the tails
     are applied as the raw conv outputs are loaded (nasseg_add_act2) - one launch and three tensor passes instead
@@ -2212,19 +2198,7 @@ class _AddPending(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, za, zb, sta, stb, act_a, act_b):
-        za, zb = _cl(za), _cl(zb)
-        if za.shape != zb.shape:
-            raise NassegError("add: shapes {} and {} differ".format(tuple(za.shape), tuple(zb.shape)))
-        C = za.shape[1]
-        y = torch.empty_like(za)
-
-        def vecs(st):
-            return (None, None) if st is None else _bn_parts(st, C)[2:]
-
-        (sa, ha), (sb, hb) = vecs(sta), vecs(stb)
-        lib.call(_k("nasseg_add_act2", za), ptr(za), ptr(sa), ptr(ha), act_a, None, ptr(zb), ptr(sb), ptr(hb), act_b,
-                 None, ptr(y), za.numel(), C, current_stream())
-        return y
+        return _add_act2("add", _cl(za), sta, act_a, None, _cl(zb), stb, act_b, None)
 
     @staticmethod
     def backward(ctx, dy):
@@ -2297,19 +2271,8 @@ class _ParamSumPending(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, za, zb, sta, stb, a, b, act_a, act_b):
-        za, zb = _cl(za), _cl(zb)
-        if za.shape != zb.shape:
-            raise NassegError("psum: shapes {} and {} differ".format(tuple(za.shape), tuple(zb.shape)))
-        C = za.shape[1]
-        a, b = a.contiguous(), b.contiguous()
-        y = torch.empty_like(za)
-
-        def vecs(st):
-            return (None, None) if st is None else _bn_parts(st, C)[2:]
-
-        (sa, ha), (sb, hb) = vecs(sta), vecs(stb)
-        lib.call(_k("nasseg_add_act2", za), ptr(za), ptr(sa), ptr(ha), act_a, ptr(a), ptr(zb), ptr(sb), ptr(hb), act_b,
-                 ptr(b), ptr(y), za.numel(), C, current_stream())
+        za, zb, a, b = _cl(za), _cl(zb), a.contiguous(), b.contiguous()
+        y = _add_act2("psum", za, sta, act_a, a, zb, stb, act_b, b)
         ctx.save_for_backward(za, zb, sta, stb, a, b)
         ctx.acts = (act_a, act_b)
         return y
@@ -2325,9 +2288,9 @@ class _ParamSumPending(torch.autograd.Function):
         nrows = lib.query("nasseg_cat_src_blocks", B, H, W, C)
         ga = torch.empty_like(za) if ctx.needs_input_grad[0] else None
         gb = torch.empty_like(zb) if ctx.needs_input_grad[1] else None
-        rows_a = _ws(za, (nrows + 64) * 2 * C) if (sta is not None and ga is not None and FUSE_TAIL_ROWS) else None
-        rows_b = _ws(zb, (nrows + 64) * 2 * C) if (stb is not None and gb is not None and FUSE_TAIL_ROWS) else None
-        cpart = _ws(za, (nrows + 64) * 2 * C)
+        rows_a = _rows_ws(za, nrows, C) if (sta is not None and ga is not None and FUSE_TAIL_ROWS) else None
+        rows_b = _rows_ws(zb, nrows, C) if (stb is not None and gb is not None and FUSE_TAIL_ROWS) else None
+        cpart = _rows_ws(za, nrows, C)
         if (sta is not None and rows_a is None and ga is not None) or (stb is not None and rows_b is None and gb is not None):
             raise NassegError("psum: pending operands need NASSEG_FUSE_TAIL_ROWS")
         lib.call(_k("nasseg_psum_bwd", dy), ptr(dy), ptr(za), ptr(sta), act_a, ptr(a), ptr(ga), ptr(rows_a), ptr(zb),
