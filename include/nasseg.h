@@ -437,6 +437,21 @@ int nasseg_berhu_fwd(const float* pred, const float* target, int64_t n, float* o
 int nasseg_berhu_bwd(const float* pred, const float* target, const float* stats,
                      const float* gscale, int64_t n, float* dpred, void* stream);
 
+/* masked berHu of the depth head against a FULL-SIZE target with holes (absent from the reference - its depth
+ * networks are inference only; "parity unpinned").  pred: dense one-channel map [B][h][w]; target: fp32 [B][H][W]
+ * in both builds; prediction pixel (y, x) is compared with target[b][sy][sx], (sy, sx) = the source index of
+ * F.interpolate(mode="nearest") - the resized target is never written.  A pixel is valid iff its target t is finite
+ * and valid_min < t <= valid_max.  d = |pred - t| over valid pixels, c = 0.2 * max d, loss = sum B(d) / n_valid,
+ * B(d) = d if d <= c else (d*d + c*c) / (2c); out = {loss, c, n_valid}; no valid pixel: loss 0, gradient 0.
+ * Backward (c constant): dpred = gscale / n_valid * (sign(diff) if d <= c else diff / c), exactly 0 on invalid
+ * pixels.  ws: nasseg_berhu_masked_workspace() floats.  No host synchronisation. */
+int64_t nasseg_berhu_masked_workspace(void);
+int nasseg_berhu_masked_fwd(const float* pred, const float* target, int B, int h, int w, int H, int W,
+                            float valid_min, float valid_max, float* out, float* ws, void* stream);
+int nasseg_berhu_masked_bwd(const float* pred, const float* target, const float* stats, const float* gscale,
+                            int B, int h, int w, int H, int W, float valid_min, float valid_max, float* dpred,
+                            void* stream);
+
 /* ---- mean-IoU reward: helpers/miou_utils.pyx fast_cm :7-30, compute_iu :32-57,
  * compute_ius_accs :59-90; argmax + up-sampling of engine/inference.py:58-66 ------ */
 int nasseg_fast_cm(const uint8_t* preds, const uint8_t* gt, int64_t P, int n, int64_t* cm,
@@ -445,6 +460,18 @@ int nasseg_argmax_cm(const float* logits, const uint8_t* gt, uint8_t* preds, int
                      int C, int H, int W, int n, int64_t* cm, void* stream);
 /* host-side (cm, iu, n_pixels, accs are HOST pointers) */
 int nasseg_compute_ius_accs(const int64_t* cm, int n, double* iu, int64_t* n_pixels, double* accs);
+
+/* ---- depth metrics: the depth counterpart of nasseg_argmax_cm (absent from the reference, "parity unpinned").
+ * Channel 0 of the NHWC prediction [B][h][w] (pixel stride ldp elements) is up-sampled bilinearly
+ * (align_corners=False, fp32) to the ground truth's (H, W); pixels whose gt is finite and in
+ * (min_depth, max_depth] are kept, the prediction is clamped to [min_depth, max_depth] (min_depth > 0 required);
+ * from the fp32 p and g, in double, acc[0..10] += n, sum|p-g|, sum(p-g)^2, sum|p-g|/g, sum(p-g)^2/g,
+ * sum|log10 p - log10 g|, sum(ln p - ln g), sum(ln p - ln g)^2, #{max(p/g, g/p) < 1.25, 1.25^2, 1.25^3};
+ * acc[11] is reserved and left untouched.  acc: 12 doubles on the device, ACCUMULATED into; ws:
+ * nasseg_depth_metrics_workspace(B, H, W) doubles.  Fixed-order sums: the same inputs give the same bits. */
+int64_t nasseg_depth_metrics_workspace(int B, int H, int W);
+int nasseg_depth_metrics(const float* pred, int64_t ldp, int B, int h, int w, const float* gt, int H, int W,
+                         float min_depth, float max_depth, double* acc, double* ws, void* stream);
 
 
 /* ---- clip_grad_norm_ + optimiser steps: src/engine/trainer.py:163-166,258-268 on the torch.optim.SGD /
@@ -645,6 +672,13 @@ int nasseg_bf16_berhu_fwd(const nasseg_bf16_t* pred, const nasseg_bf16_t* target
                      void* stream);
 int nasseg_bf16_berhu_bwd(const nasseg_bf16_t* pred, const nasseg_bf16_t* target, const float* stats,
                      const float* gscale, int64_t n, nasseg_bf16_t* dpred, void* stream);
+int nasseg_bf16_berhu_masked_fwd(const nasseg_bf16_t* pred, const float* target, int B, int h, int w, int H, int W,
+                                 float valid_min, float valid_max, float* out, float* ws, void* stream);
+int nasseg_bf16_berhu_masked_bwd(const nasseg_bf16_t* pred, const float* target, const float* stats,
+                                 const float* gscale, int B, int h, int w, int H, int W, float valid_min,
+                                 float valid_max, nasseg_bf16_t* dpred, void* stream);
+int nasseg_bf16_depth_metrics(const nasseg_bf16_t* pred, int64_t ldp, int B, int h, int w, const float* gt, int H,
+                              int W, float min_depth, float max_depth, double* acc, double* ws, void* stream);
 int nasseg_bf16_colred(int mode, const nasseg_bf16_t* a, int64_t lda, const nasseg_bf16_t* b, int64_t ldb,
                   const nasseg_bf16_t* c, int64_t ldc, float* out, float* ws, int S, int64_t R, int C,
                   float mul, void* stream);

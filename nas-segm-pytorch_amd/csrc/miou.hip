@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "resize_index.h"
 
 namespace {
 
@@ -45,29 +46,6 @@ __global__ __launch_bounds__(256) void cm_u8_kernel(const uint8_t* __restrict__ 
     for (int i = threadIdx.x; i < nn; i += 256)
       if (bins[i]) atomicAdd(&cm[i], (unsigned long long)bins[i]);
   }
-}
-
-struct Lin {
-  int i0, i1;
-  float l0, l1;
-};
-__device__ __forceinline__ Lin lin_coeff(int dst, float scale, int in_size, int out_size) {
-  Lin r;
-  if (in_size == out_size) {
-    r.i0 = r.i1 = dst;
-    r.l0 = 1.f;
-    r.l1 = 0.f;
-    return r;
-  }
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  r.i0 = (int)src;
-  if (r.i0 > in_size - 1) r.i0 = in_size - 1;
-  r.i1 = r.i0 + ((r.i0 < in_size - 1) ? 1 : 0);
-  float l1 = fminf(fmaxf(src - (float)r.i0, 0.f), 1.f);
-  r.l1 = l1;
-  r.l0 = 1.f - l1;
-  return r;
 }
 
 // logits [B][h][w][C] -> bilinear to (H,W) -> argmax (lowest index wins ties,

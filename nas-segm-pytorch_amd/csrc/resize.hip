@@ -15,32 +15,9 @@
 // (deterministic; no atomics).
 #include "common.h"
 #include "dw_common.h"
+#include "resize_index.h"
 
 namespace {
-
-struct Lin {
-  int i0, i1;
-  float l0, l1;
-};
-__device__ __forceinline__ Lin lin_coeff(int dst, float scale, int in_size, int out_size) {
-  Lin r;
-  if (in_size == out_size) {
-    r.i0 = r.i1 = dst;
-    r.l0 = 1.f;
-    r.l1 = 0.f;
-    return r;
-  }
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  r.i0 = (int)src;
-  if (r.i0 > in_size - 1) r.i0 = in_size - 1;
-  r.i1 = r.i0 + ((r.i0 < in_size - 1) ? 1 : 0);
-  float l1 = src - (float)r.i0;
-  l1 = fminf(fmaxf(l1, 0.f), 1.f);
-  r.l1 = l1;
-  r.l0 = 1.f - l1;
-  return r;
-}
 
 // align_corners=True (the KD teacher's up-sampling, src/kd/rf_lw/model_lw_v2.py:258,266,274): torch's
 // area_pixel_compute_source_index with align_corners: src = dst * (in-1)/(out-1) (scale 0 when out == 1)
@@ -656,7 +633,7 @@ __global__ __launch_bounds__(256) void bilinear_bwd_axis_kernel(const TS* __rest
   }
 }
 
-// nearest resize of integer label maps (torch 'nearest': src = min(floor(dst*in/out), in-1))
+// nearest resize of integer label maps (torch 'nearest': nearest_src, resize_index.h)
 template <typename TI>
 __global__ __launch_bounds__(256) void nearest_label_kernel(const TI* __restrict__ x,
                                                             int64_t* __restrict__ y, int B, int Hi,
@@ -668,10 +645,8 @@ __global__ __launch_bounds__(256) void nearest_label_kernel(const TI* __restrict
     const int64_t t = i / Wo;
     const int oy = (int)(t % Ho);
     const int b = (int)(t / Ho);
-    int iy = (int)floorf((float)oy * sh);
-    int ix = (int)floorf((float)ox * sw);
-    if (iy > Hi - 1) iy = Hi - 1;
-    if (ix > Wi - 1) ix = Wi - 1;
+    const int iy = nearest_src(oy, sh, Hi);
+    const int ix = nearest_src(ox, sw, Wi);
     y[i] = (int64_t)x[((int64_t)b * Hi + iy) * Wi + ix];
   }
 }

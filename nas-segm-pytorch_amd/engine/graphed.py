@@ -37,7 +37,7 @@ from torch import nn
 
 from .. import functional as F
 from . import graph_dag
-from .trainer_common import check_cache_rows, clip_and_step, inner, task0_loss, task1_loss
+from .trainer_common import check_cache_rows, clip_and_step, inner, task0_loss, task1_depth_loss, task1_loss
 
 logger = logging.getLogger(__name__)
 
@@ -343,15 +343,18 @@ class GraphedSegmenterStep(_GraphedStep):
 
     def __init__(self, segmenter, image, target, optim_enc, optim_dec, ignore_index=255,
                  enc_grad_clip=0.0, dec_grad_clip=0.0, aux_weight=-1, capture_optimisers=False,
-                 warmup=2, loss_fn=None):
+                 warmup=2, loss_fn=None, depth_crit=None):
         """loss_fn(output, target) -> scalar replaces the softmax/NLL (+ aux heads) of the
         segmentation step, e.g. ``F.berhu_loss`` for a depth head; it must be capturable (device
-        tensors in, device scalar out, no host synchronisation)."""
+        tensors in, device scalar out, no host synchronisation).
+        depth_crit (an ``nn.BerHuLoss``): the depth step of ``train_segmenter`` - ``target`` is the fp32 (B, H, W)
+        depth map at the image's size, the loss is ``task1_depth_loss`` (auxiliary heads included)."""
         model = inner(segmenter)
         self.optim_enc, self.optim_dec = optim_enc, optim_dec
         self.ignore_index = ignore_index
         self.aux_weight = aux_weight
         self.loss_fn = loss_fn
+        self.depth_crit = depth_crit
         self._trained = [model.encoder, model.decoder]
         self.groups = [
             (list(model.encoder.parameters()), enc_grad_clip, optim_enc),
@@ -362,6 +365,8 @@ class GraphedSegmenterStep(_GraphedStep):
         self._init_common(segmenter, capture_optimisers, (optim_enc, optim_dec), warmup)
 
     def _forward_loss(self):
+        if self.depth_crit is not None:
+            return task1_depth_loss(self.segmenter, self.image, self.target, self.depth_crit, self.aux_weight)
         if self.loss_fn is None:
             return task1_loss(self.segmenter, self.image, self.target, self.ignore_index, self.aux_weight)
         output = self.segmenter(self.image)

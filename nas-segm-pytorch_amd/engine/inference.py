@@ -35,6 +35,89 @@ def reward_from_cm(cm, omit_classes=(0,)):
     return reward, miou, macc, mfwiou
 
 
+def _set_val_stage(val_loader):
+    ds = getattr(val_loader, "dataset", None)
+    if ds is not None:
+        try:
+            ds.set_stage("val")
+        except AttributeError:
+            sub = getattr(ds, "dataset", None)
+            if sub is not None and hasattr(sub, "set_stage"):
+                sub.set_stage("val")
+
+
+def depth_scores(acc):
+    """The scores of a depth network from the 12 sums of ``F.depth_metrics`` (a tensor or an array; host arithmetic):
+    n, abs_rel = mean |p-g|/g, sq_rel = mean (p-g)^2/g, rmse, rmse_log = sqrt(mean l^2), log10 = mean |log10 p -
+    log10 g|, silog = sqrt(mean l^2 - mean(l)^2) with l = ln p - ln g, and d1 / d2 / d3 = the fractions of pixels
+    with max(p/g, g/p) < 1.25, 1.25^2, 1.25^3.  Every score is 0.0 for n == 0."""
+    a = acc.detach().cpu().numpy() if torch.is_tensor(acc) else np.asarray(acc)
+    a = a.astype(np.float64).reshape(-1)
+    n = float(a[0])
+    names = ("abs_rel", "sq_rel", "rmse", "rmse_log", "log10", "silog", "d1", "d2", "d3")
+    if n <= 0:
+        return dict({"n": 0.0}, **{k: 0.0 for k in names})
+    mean_l, mean_l2 = a[6] / n, a[7] / n
+    return {
+        "n": n,
+        "abs_rel": float(a[3] / n),
+        "sq_rel": float(a[4] / n),
+        "rmse": float(np.sqrt(a[2] / n)),
+        "rmse_log": float(np.sqrt(mean_l2)),
+        "log10": float(a[5] / n),
+        "silog": float(np.sqrt(max(mean_l2 - mean_l * mean_l, 0.0))),
+        "d1": float(a[8] / n),
+        "d2": float(a[9] / n),
+        "d3": float(a[10] / n),
+    }
+
+
+def depth_reward(scores):
+    """geometric mean of the three threshold accuracies (in [0, 1], higher is better): combined the way
+    ``reward_from_cm`` combines its three segmentation scores"""
+    return float((scores["d1"] * scores["d2"] * scores["d3"]) ** (1.0 / 3.0))
+
+
+@try_except
+def validate_depth(segmenter, val_loader, epoch, epoch2, min_depth=1e-3, max_depth=10.0, print_every=10,
+                   reward_fn=None):
+    """Evaluate a depth candidate; returns the scalar reward (``reward_fn(scores)``, default ``depth_reward``).
+    ``validate`` for a one-channel head: the up-sampling to the ground truth's size, the validity mask and every sum
+    of the scores are one HIP kernel (F.depth_metrics); only the 12 doubles leave the device."""
+    _set_val_stage(val_loader)
+    segmenter.eval()
+    model = segmenter.module if hasattr(segmenter, "module") else segmenter
+    device = next(model.parameters()).device
+    acc = torch.zeros((12,), device=device, dtype=torch.float64)
+    try:
+        with torch.no_grad():
+            for i, sample in enumerate(val_loader):
+                image = sample["image"]
+                image = image.to(device=device, dtype=torch.bfloat16 if image.dtype == torch.bfloat16
+                                 else torch.float32).contiguous(memory_format=torch.channels_last)
+                gt = sample["mask"].to(device=device, dtype=torch.float32)
+                output = segmenter(image)
+                if isinstance(output, tuple):
+                    output, _ = output
+                F.depth_metrics(output, gt, min_depth, max_depth, acc=acc)
+                if i % print_every == 0:
+                    logger.info(" Val epoch: {} [{}/{}]\tRMSE: {:.3f}".format(
+                        epoch, i, len(val_loader), depth_scores(acc)["rmse"]))
+    except Exception:  # (as in validate: the peers wait in the all-reduce of the sums)
+        if hasattr(segmenter, "reduce_sums"):
+            segmenter.reduce_sums(acc, failed=True)
+        raise
+    if hasattr(segmenter, "reduce_sums"):
+        segmenter.reduce_sums(acc)
+    scores = depth_scores(acc)
+    reward = float(reward_fn(scores)) if reward_fn is not None else depth_reward(scores)
+    logger.info((" Val epoch: {}/{}\tabs rel: {:.4f}\tRMSE: {:.4f}\tlog10: {:.4f}\tsilog: {:.4f}\t"
+                 "d1/d2/d3: {:.3f}/{:.3f}/{:.3f}\tReward: {:.3f}").format(
+                     epoch, epoch2, scores["abs_rel"], scores["rmse"], scores["log10"], scores["silog"],
+                     scores["d1"], scores["d2"], scores["d3"], reward))
+    return reward
+
+
 @try_except
 def validate(segmenter, val_loader, epoch, epoch2, num_classes=-1, print_every=10,
              omit_classes=[0]):

@@ -14,7 +14,8 @@ from ..helpers.utils import compute_params
 from ..nn.encoders import create_encoder
 from ..nn.micro_decoders import MicroDecoder, TemplateDecoder
 from .graphed import GraphedSegmenterStep
-from .inference import validate
+from ..nn.losses import BerHuLoss
+from .inference import validate, validate_depth
 from .segmenter import RankParallel, Segmenter
 from .trainer import train_segmenter
 
@@ -23,10 +24,19 @@ class _Crit(object):
     ignore_index = 255
 
 
+def _task(task):
+    if task not in ("segm", "depth"):
+        raise ValueError("task must be 'segm' or 'depth' (got {!r})".format(task))
+    return task
+
+
 def build_candidate(config, ctrl_version="wacv", num_classes=19, agg_size=48, aux_cell=True,
-                    repeats=1, device="cuda"):
+                    repeats=1, device="cuda", task="segm"):
     """Encoder + decoder for one sampled genotype (create_segmenter, main_search.py:490-513).
-    The encoder's ``out_sizes`` list is copied: MicroDecoder overwrites its argument."""
+    The encoder's ``out_sizes`` list is copied: MicroDecoder overwrites its argument.
+    task="depth": the decoder's heads have ONE output channel, whatever ``num_classes`` says."""
+    if _task(task) == "depth":
+        num_classes = 1
     encoder = create_encoder(pretrained=False, ctrl_version=ctrl_version)
     Decoder = MicroDecoder if ctrl_version == "cvpr" else TemplateDecoder
     decoder = Decoder(inp_sizes=list(encoder.out_sizes), num_classes=num_classes, config=config,
@@ -36,9 +46,16 @@ def build_candidate(config, ctrl_version="wacv", num_classes=19, agg_size=48, au
 
 def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", num_classes=19,
                        agg_size=48, aux_cell=True, repeats=1, epochs=1, aux_weight=0.15,
-                       omit_classes=(0,), device="cuda", stats=None, graphed=False):
+                       omit_classes=(0,), device="cuda", stats=None, graphed=False, task="segm",
+                       min_depth=1e-3, max_depth=10.0):
     """Train the candidate on ``train_batches`` (lists of {"image", "mask"}) for ``epochs``
-    passes and return its validation reward; failures score 0 like in the reference."""
+    passes and return its validation reward; failures score 0 like in the reference.
+    task="depth": the masks are fp32 depth maps at the image's size (holes: 0 / NaN / inf), the decoder has one
+    output channel, the loss is BerHuLoss(valid_min=0) and the reward comes from ``validate_depth``
+    (``min_depth`` / ``max_depth``: its valid range)."""
+    if _task(task) == "depth":
+        return _evaluate_depth_candidate(config, train_batches, val_batches, ctrl_version, agg_size, aux_cell,
+                                         repeats, epochs, aux_weight, device, stats, graphed, min_depth, max_depth)
     try:
         segmenter = build_candidate(config, ctrl_version, num_classes, agg_size, aux_cell, repeats,
                                     device)
@@ -71,6 +88,47 @@ def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", 
                 return 0.0
     reward = validate(segmenter, val_batches, 0, 0, num_classes=num_classes, print_every=10 ** 9,
                       omit_classes=list(omit_classes))
+    if stats is not None:
+        stats["params"] = compute_params(segmenter)[1]
+    return float(reward)
+
+
+def _evaluate_depth_candidate(config, train_batches, val_batches, ctrl_version, agg_size, aux_cell, repeats, epochs,
+                              aux_weight, device, stats, graphed, min_depth, max_depth):
+    """``evaluate_candidate`` for task="depth": the same optimisers, clip norms and eager / replayed paths, with the
+    depth step and the depth reward"""
+    try:
+        segmenter = build_candidate(config, ctrl_version, 1, agg_size, aux_cell, repeats, device, task="depth")
+    except RuntimeError:
+        return 0.0
+    model = segmenter.module
+    optim_enc = torch.optim.SGD(model.encoder.parameters(), lr=1e-3, momentum=0.9, weight_decay=1e-5)
+    optim_dec = torch.optim.Adam(model.decoder.parameters(), lr=3e-3, weight_decay=1e-5)
+    aux = aux_weight if ctrl_version == "cvpr" else -1
+    crit = BerHuLoss(valid_min=0.0)
+
+    def on_device(sample):
+        return (sample["image"].to(device=device, dtype=torch.float32).contiguous(memory_format=torch.channels_last),
+                sample["mask"].to(device=device, dtype=torch.float32))
+
+    if graphed:
+        try:
+            image, depth = on_device(train_batches[0])
+            stepper = GraphedSegmenterStep(segmenter, image, depth, optim_enc, optim_dec, 255, 3.0, 3.0, aux,
+                                           depth_crit=crit)
+            for epoch in range(epochs):
+                for sample in train_batches:
+                    stepper.step(*on_device(sample))
+        except RuntimeError:  # scored 0, as the reference's try_except does
+            return 0.0
+    else:
+        for epoch in range(epochs):
+            ret = train_segmenter(segmenter, train_batches, optim_enc, optim_dec, epoch, crit, False, 3.0, 3.0,
+                                  False, print_every=10 ** 9, aux_weight=aux)
+            if ret == 0:  # try_except: RuntimeError inside the step
+                return 0.0
+    reward = validate_depth(segmenter, val_batches, 0, 0, min_depth=min_depth, max_depth=max_depth,
+                            print_every=10 ** 9)
     if stats is not None:
         stats["params"] = compute_params(segmenter)[1]
     return float(reward)

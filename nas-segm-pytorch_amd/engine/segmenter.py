@@ -203,3 +203,20 @@ class RankParallel(nn.Module):
                 raise PeerFailure("a data-parallel peer failed during validation: candidate abandoned")
             cm.copy_(buf[:-1].view_as(cm))
         return cm
+
+    def reduce_sums(self, acc, failed=False):
+        """``reduce_confusion`` for a float64 vector of sums (validate_depth's accumulator): summed over the ranks
+        in place, one extra element carries the failure status."""
+        if self.world_size > 1:
+            buf = torch.zeros(acc.numel() + 1, device=acc.device, dtype=torch.float64)
+            if failed:
+                buf[-1] = 1
+            else:
+                buf[:-1].copy_(acc.reshape(-1))
+            dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.process_group)
+            if failed:
+                return acc
+            if float(buf[-1]) != 0:
+                raise PeerFailure("a data-parallel peer failed during validation: candidate abandoned")
+            acc.copy_(buf[:-1].view_as(acc))
+        return acc

@@ -20,9 +20,10 @@ from torch import nn
 
 from .. import functional as F
 from ..helpers.utils import AverageMeter, try_except
+from ..nn.losses import BerHuLoss
 from ..nn.modules import TREE_VERSION
 from . import graphed
-from .trainer_common import cache_feature_keys, check_cache_rows, task0_loss, task1_loss
+from .trainer_common import cache_feature_keys, check_cache_rows, task0_loss, task1_depth_loss, task1_loss
 from .trainer_common import clip_and_step as _clip_and_step
 from .trainer_common import inner as _inner
 
@@ -71,6 +72,17 @@ def _labels(mask, device):
     if mask.dtype not in (torch.uint8, torch.int64):
         mask = mask.to(torch.int64)
     return mask.to(device, non_blocking=True)
+
+
+def _depth_crit(segm_crit):
+    """the criterion itself when it selects the depth step (an nn.BerHuLoss: fp32 full-size targets, masked berHu),
+    else None: softmax/NLL on class labels, as ever"""
+    return segm_crit if isinstance(segm_crit, BerHuLoss) else None
+
+
+def _depth_target(mask, device):
+    """a depth map goes to the device as it is - fp32 (B, H, W), holes (0 / NaN / inf) included"""
+    return mask.to(device=device, dtype=torch.float32, non_blocking=True)
 
 
 def _polyak_update(params, avg_param, decay):
@@ -260,13 +272,17 @@ def _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_
 
 
 def _segmenter_stepper(segmenter, image, target, optim_enc, optim_dec, ignore, enc_grad_clip, dec_grad_clip,
-                       aux_weight):
+                       aux_weight, depth_crit=None):
     model = _inner(segmenter)
     base = (TREE_VERSION[0], id(optim_enc), id(optim_dec), ignore, enc_grad_clip, dec_grad_clip, aux_weight,
             _bn_modes(model), _trainable_signature(list(model.parameters()), (optim_enc, optim_dec)))
+    extra = {}
+    if depth_crit is not None:  # (the loss kind, and what the recorded launches carry by value)
+        base = base + (("berhu", id(depth_crit), depth_crit.valid_min, depth_crit.valid_max),)
+        extra["depth_crit"] = depth_crit
     shape = (tuple(image.shape), image.dtype, tuple(target.shape), target.dtype)
     return _cached_stepper(model, "_nasseg_task1_stepper", base, shape, lambda: graphed.GraphedSegmenterStep(
-        segmenter, image, target, optim_enc, optim_dec, ignore, enc_grad_clip, dec_grad_clip, aux_weight))
+        segmenter, image, target, optim_enc, optim_dec, ignore, enc_grad_clip, dec_grad_clip, aux_weight, **extra))
 
 
 @try_except
@@ -381,6 +397,9 @@ def train_task0(Xy_train, segmenter, optim_dec, epoch, segm_crit, kd_crit, batch
                 do_kd, kd_coeff, dec_grad_clip, do_polyak, avg_param=None, polyak_decay=0.9,
                 aux_weight=0):
     """Decoder-only epoch over the cached encoder features (trainer.py:78-175)."""
+    if _depth_crit(segm_crit) is not None:
+        raise ValueError("train_task0: depth candidates are trained end to end only (train_segmenter) - the task0 "
+                         "cache holds class labels, not depth maps")
     decoder = _inner(segmenter).decoder
     # (data parallel the cache is sharded: every rank must issue the same number of gradient
     #  all-reduces, so the shards agree on the smallest of their sizes first)
@@ -413,12 +432,14 @@ def train_task0(Xy_train, segmenter, optim_dec, epoch, segm_crit, kd_crit, batch
 
 
 def segmenter_step(segmenter, image, target, optim_enc, optim_dec, ignore_index=255,
-                   enc_grad_clip=0.0, dec_grad_clip=0.0, aux_weight=-1):
+                   enc_grad_clip=0.0, dec_grad_clip=0.0, aux_weight=-1, depth_crit=None):
     """One end-to-end training step on device tensors; returns the (device) loss.
 
     forward -> nearest-resize labels to the logits' size -> fused log-softmax/NLL
     (+ weighted aux heads) -> backward -> gradient all-reduce (if data parallel)
     -> per-sub-module norm clipping -> optimiser steps.
+    ``depth_crit`` (an nn.BerHuLoss): the depth step instead - ``target`` is the fp32 (B, H, W) depth map and the
+    loss is the masked berHu of every head against it (trainer_common.task1_depth_loss).
     """
     model = _inner(segmenter)
     cached = getattr(model, "_nasseg_step_params", None)
@@ -433,7 +454,10 @@ def segmenter_step(segmenter, image, target, optim_enc, optim_dec, ignore_index=
         # the parameters are constant until the optimiser steps below: all chains' weights are
         # re-packed by one launch at the start of the step
         with F.packed_once(model._nasseg_pack_memo):
-            loss = task1_loss(segmenter, image, target, ignore_index, aux_weight)
+            if depth_crit is not None:
+                loss = task1_depth_loss(segmenter, image, target, depth_crit, aux_weight)
+            else:
+                loss = task1_loss(segmenter, image, target, ignore_index, aux_weight)
             _zero_grads(segmenter, (optim_enc, optim_dec))
             # gradients were just cleared: the second stages of all weight-gradient reductions run
             # batched when backward is through
@@ -466,6 +490,8 @@ def train_segmenter(segmenter, train_loader, optim_enc, optim_dec, epoch, segm_c
         _freeze_bn(segmenter)
     batch_time, losses = AverageMeter(), AverageMeter()
     ignore = _ignore_index(segm_crit)
+    depth_crit = _depth_crit(segm_crit)
+    extra = {} if depth_crit is None else {"depth_crit": depth_crit}  # (any other criterion: exactly as ever)
     device = _model_device(_inner(segmenter))
     # data parallel: the ranks agree on the number of steps (loaders of unequal length would leave
     # the longer ones waiting in an all-reduce), and a rank that fails ANYWHERE in its step - the
@@ -482,18 +508,18 @@ def train_segmenter(segmenter, train_loader, optim_enc, optim_dec, epoch, segm_c
             except StopIteration:
                 break
             image = _to_device_image(sample["image"], device)
-            target = _labels(sample["mask"], device)
+            target = _labels(sample["mask"], device) if depth_crit is None else _depth_target(sample["mask"], device)
             stepper = None
             if _replays(segmenter, device, image.shape[0] * image.shape[2] * image.shape[3]):
                 # launch-bound sizes: forward + loss + backward replayed from a hipGraph captured on
                 # this candidate's first batch (bit-identical to the eager step)
                 stepper = _segmenter_stepper(segmenter, image, target, optim_enc, optim_dec, ignore,
-                                             enc_grad_clip, dec_grad_clip, aux_weight)
+                                             enc_grad_clip, dec_grad_clip, aux_weight, **extra)
             if stepper is not None:
                 loss = stepper.step(image, target)
             else:
                 loss = segmenter_step(segmenter, image, target, optim_enc, optim_dec, ignore,
-                                      enc_grad_clip, dec_grad_clip, aux_weight)
+                                      enc_grad_clip, dec_grad_clip, aux_weight, **extra)
             if do_polyak:
                 _polyak(segmenter, avg_param, polyak_decay)
         except Exception as e:

@@ -56,6 +56,23 @@ def task1_loss(segmenter, image, target, ignore_index, aux_weight):
     return segmentation_loss(output, aux_outs, target, ignore_index, aux_weight)
 
 
+def depth_loss(output, aux_outs, target, crit, aux_weight):
+    """``crit`` (nn.BerHuLoss: the masked berHu) of the main head + aux_weight * that of every auxiliary head when
+    aux_weight > 0.  Every head is compared with the SAME full-size target: the kernel samples it at the head's own
+    size, so nothing is resized (src/engine/trainer.py:245-250 resizes each head to the target instead)."""
+    loss = crit(output, target)
+    if aux_weight > 0:
+        for aux_out in aux_outs:
+            loss = loss + crit(aux_out, target) * aux_weight
+    return loss
+
+
+def task1_depth_loss(segmenter, image, target, crit, aux_weight):
+    """forward + loss of the end-to-end DEPTH step: target fp32 (B, H, W) at the image's size, holes included"""
+    output, aux_outs = _heads(segmenter(image))
+    return depth_loss(output, aux_outs, target, crit, aux_weight)
+
+
 def cache_feature_keys(cache):
     """the encoder-feature entries of the task0 cache (engine/trainer.py: populate_task0)"""
     return [k for k in cache.keys() if k not in ("y", "kd_y", "out_size")]

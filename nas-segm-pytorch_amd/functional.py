@@ -2567,6 +2567,83 @@ def berhu_loss(pred, target):
     return _BerHu.apply(pred, target)
 
 
+class _BerHuMasked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, valid_min, valid_max):
+        require_device(pred, target)
+        if pred.dtype not in (torch.float32, torch.bfloat16) or pred.dim() != 4 or pred.shape[1] != 1:
+            raise NassegError("berhu_loss_masked: the prediction must be fp32 or bf16 of shape (B, 1, h, w) (got {} {})"
+                              .format(pred.dtype, tuple(pred.shape)))
+        if target.dtype != torch.float32 or target.dim() != 3 or target.shape[0] != pred.shape[0]:
+            raise NassegError("berhu_loss_masked: the target must be fp32 of shape (B, H, W) (got {} {})".format(
+                target.dtype, tuple(target.shape)))
+        p, t = pred.contiguous(), target.contiguous()  # (one channel: NCHW and NHWC are the same memory)
+        B, _, h, w = p.shape
+        H, W = t.shape[1], t.shape[2]
+        cfg = (B, h, w, H, W, float(valid_min), float(valid_max))
+        out = _vec(p, 3)
+        ws = _ws(p, lib.query("nasseg_berhu_masked_workspace"))
+        lib.call(_k("nasseg_berhu_masked_fwd", p), ptr(p), ptr(t), *cfg, ptr(out), ptr(ws), current_stream())
+        ctx.save_for_backward(p, t, out)
+        ctx.cfg = cfg
+        # The loss is out[0] under a tensor of its own, not a view of ``out``: a caller may update it in place
+        # (``loss += aux_weight * aux_loss``, the reference's idiom) - autograd refuses that on a view made inside a
+        # Function - and nothing is copied (a 4-byte copy node in a recorded step cannot be re-created, graph_dag.py).
+        # backward reads c and n_valid (out[1], out[2]) only.
+        return torch.empty(0, device=p.device, dtype=torch.float32).set_(out.untyped_storage(), out.storage_offset(),
+                                                                          (), ())
+
+    @staticmethod
+    def backward(ctx, g):
+        p, t, out = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous().view(1)
+        d = torch.empty_like(p)
+        lib.call(_k("nasseg_berhu_masked_bwd", p), ptr(p), ptr(t), ptr(out), ptr(g), *ctx.cfg, ptr(d),
+                 current_stream())
+        return d, None, None, None
+
+
+def berhu_loss_masked(pred, target, valid_min=0.0, valid_max=float("inf")):
+    """Reverse-Huber loss of a depth head against a full-size target with holes (absent from the reference).
+
+    pred (B, 1, h, w) fp32 or bf16, target (B, H, W) fp32 at ANY size: prediction pixel (y, x) is compared with the
+    target pixel ``F.interpolate(mode="nearest")`` would put there (never written anywhere).  A pixel counts iff its
+    target t is finite and ``valid_min < t <= valid_max``; d = |pred - t|, c = 0.2 * max d (a constant in backward),
+    loss = mean over valid pixels of (d if d <= c else (d^2 + c^2) / (2c)); no valid pixel: loss 0, gradient 0.
+    Returns a 0-dim tensor that may be updated in place.  No host synchronisation: capturable."""
+    return _BerHuMasked.apply(pred, target, valid_min, valid_max)
+
+
+def depth_metrics(pred, gt, min_depth=1e-3, max_depth=10.0, acc=None):
+    """Fused bilinear up-sampling -> validity mask -> clamp -> sums of the depth scores: the depth counterpart of
+    ``argmax_confusion``.
+
+    pred (B, C, h, w) fp32 or bf16 on the device (channel 0 is the depth; more channels need no copy), gt (B, H, W)
+    fp32 on the device.  Pixels whose gt is finite and in (min_depth, max_depth] count; the up-sampled prediction is
+    clamped to [min_depth, max_depth].  ``acc`` is a float64 (12,) device tensor that is accumulated into (created
+    zeroed when None): n, sum|p-g|, sum(p-g)^2, sum|p-g|/g, sum(p-g)^2/g, sum|log10 p - log10 g|, sum(ln p - ln g),
+    sum(ln p - ln g)^2, #{max(p/g, g/p) < 1.25, 1.25^2, 1.25^3}, one reserved slot.
+    engine.inference.depth_scores turns it into the scores."""
+    pred = _cl(pred.detach())
+    require_device(gt)
+    B, C, h, w = pred.shape
+    if gt.dtype != torch.float32 or gt.dim() != 3 or gt.shape[0] != B:
+        raise NassegError("depth_metrics: gt must be fp32 of shape (B, H, W) (got {} {})".format(
+            gt.dtype, tuple(gt.shape)))
+    gt = gt.contiguous()
+    H, W = gt.shape[1], gt.shape[2]
+    if acc is None:
+        acc = torch.zeros((12,), device=pred.device, dtype=torch.float64)
+    elif (tuple(acc.shape) != (12,) or acc.dtype != torch.float64 or not acc.is_contiguous()
+          or acc.device != pred.device):
+        raise NassegError("depth_metrics: acc must be a contiguous float64 (12,) tensor on the prediction's device")
+    ws = torch.empty((max(lib.query("nasseg_depth_metrics_workspace", B, H, W), 1),), device=pred.device,
+                     dtype=torch.float64)
+    lib.call(_k("nasseg_depth_metrics", pred), ptr(pred), C, B, h, w, ptr(gt), H, W, float(min_depth),
+             float(max_depth), ptr(acc), ptr(ws), current_stream())
+    return acc
+
+
 def nearest_label_resize(target, size, out=None):
     """F.interpolate(target[:, None].float(), size, mode='nearest').long()[:, 0]; ``out``: a
     contiguous int64 (B, Ho, Wo) tensor to write into (a slice of the task0 label cache)."""
