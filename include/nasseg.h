@@ -565,8 +565,13 @@ int nasseg_resize_cubic_argmax(const float* x, int B, int h, int w, int C, const
  * bfloat16 (BASELINE config 5).  Only storage changes: values are widened to fp32 on load and
  * rounded to nearest-even on store; arithmetic, MFMA accumulation, BatchNorm statistics,
  * parameters, parameter gradients, workspaces and every per-channel vector stay fp32, and the
- * size / workspace queries are shared with the fp32 entry points. */
-typedef uint16_t nasseg_bf16_t;
+ * size / workspace queries are shared with the fp32 entry points.
+ * nasseg_bf16_t is one stored value: the upper 16 bits of the IEEE-754 binary32 it stands for, in a struct
+ * with the size and alignment of uint16_t (2 bytes, no padding), so that an array of them is an array of
+ * uint16_t in memory and a stored value is never taken for a number by accident. */
+typedef struct nasseg_bf16_t {
+  uint16_t v;
+} nasseg_bf16_t;
 /* fp32 -> bf16 (round to nearest even) / bf16 -> fp32 of n values: the (B, C, 1, 1) maps on either side of
  * GAPConv1x1's fp32 island (layer_factory.py:181-195) in a bf16-storage network */
 int nasseg_to_bf16(const float* x, nasseg_bf16_t* y, int64_t n, void* stream);

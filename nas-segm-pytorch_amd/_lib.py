@@ -1,6 +1,7 @@
 """ctypes binding of libnasseg_hip.so (the C ABI declared in include/nasseg.h).
 
-Prototypes are parsed from the header so the header stays the single source of
+Prototypes are parsed from the header (ffi_gen.prototypes, the one parser), and
+the library is compiled against it, so the header is the single source of
 truth.  Every call that returns a negative status raises RuntimeError - the
 error class the reference's ``try_except`` wrapper (src/helpers/utils.py:172-187)
 converts into reward 0.  There is no CPU fallback: if the shared library is
@@ -8,7 +9,8 @@ missing, loading fails loudly.
 """
 import ctypes
 import os
-import re
+
+from . import ffi_gen
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (NASSEG_LIB: another build of the same ABI, for A/B measurements of two libraries on one box)
@@ -20,49 +22,23 @@ _CTYPE = {
     "int64_t": ctypes.c_int64,
     "float": ctypes.c_float,
     "double": ctypes.c_double,
+    "const char*": ctypes.c_char_p,
 }
-_PROTO = re.compile(r"^\s*(const char\*|int64_t|int)\s+(nasseg_\w+)\s*\(([^)]*)\)\s*;", re.M | re.S)
 
 
 def parse_header(path=HEADER_PATH):
     """Return {symbol: (restype, [argtypes])} for every prototype in the header."""
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    protos = {}
-    for ret, name, args in _PROTO.findall(text):
-        args = " ".join(args.split())
-        argtypes = []
-        if args and args != "void":
-            for a in args.split(","):
-                a = a.strip()
-                if "*" in a:
-                    argtypes.append(ctypes.c_void_p)
-                else:
-                    base = a.replace("const ", "").split()[0]
-                    argtypes.append(_CTYPE[base])
-        restype = {"const char*": ctypes.c_char_p, "int64_t": ctypes.c_int64, "int": ctypes.c_int}[ret]
-        protos[name] = (restype, argtypes)
-    return protos
+    return {p.name: (_CTYPE[p.ret], [ctypes.c_void_p if a.levels else _CTYPE[a.ctype] for a in p.args])
+            for p in ffi_gen.prototypes(path)}
 
 
 def pointer_access(path=HEADER_PATH):
     """{symbol: [(argument index, "r" | "w" | "t")]} for the pointer arguments of every prototype except `stream`:
     the header's const-ness IS the contract - a `const T*` is only read, a `T*` may be written (engine/graph_dag.py
     derives the dependencies between the launches of a recorded step from it); "t": a table of pointers."""
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    out = {}
-    for _, name, args in _PROTO.findall(text):
-        args = " ".join(args.split())
-        acc = []
-        if args and args != "void":
-            for i, a in enumerate(args.split(",")):
-                a = a.strip()
-                if "*" not in a or a[a.rindex("*") + 1:].strip() == "stream":
-                    continue
-                acc.append((i, "t" if a.count("*") > 1 else ("r" if a.startswith("const ") else "w")))
-        out[name] = acc
-    return out
+    return {p.name: [(i, "t" if a.levels > 1 else ("r" if a.const else "w"))
+                     for i, a in enumerate(p.args) if a.levels and a.name != "stream"]
+            for p in ffi_gen.prototypes(path)}
 
 
 def _address_of(obj):
@@ -177,8 +153,6 @@ class _Library(object):
             from . import _nasseg_ffi as ffi
         except ImportError:
             return None
-        from . import ffi_gen
-
         if not hasattr(ffi, "abi") or ffi.abi() != ffi_gen.abi_hash(HEADER_PATH):
             return None  # (generated from another header: its argument lists may not match the library's)
         ffi.set_addr_of(_address_of)

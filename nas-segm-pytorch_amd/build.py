@@ -11,11 +11,14 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")  # nasseg.h, the C ABI: csrc/common.h includes it
 OBJ_DIR = os.path.join(CSRC, "build")
 LIB_PATH = os.path.join(HERE, "libnasseg_hip.so")
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall", "-Wno-unused-function"]
+# -Werror=missing-prototypes: a function with external linkage that nasseg.h does not declare fails the build
+FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-I", INCLUDE, "-Wall", "-Wno-unused-function",
+         "-Werror=missing-prototypes"]
 # experiments only (tools/kbench_*.py variants): extra -D flags; objects are rebuilt by mtime, so touch
 # the source that reads the macro
 FLAGS += os.environ.get("NASSEG_EXTRA_FLAGS", "").split()
@@ -35,15 +38,15 @@ def _stale(target, deps):
 
 
 def _headers_of(path, seen=None):
-    """the csrc/*.h files a source includes, directly or through another header"""
+    """the csrc/*.h and include/*.h files a source includes, directly or through another header"""
     import re
 
     seen = set() if seen is None else seen
     for name in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), flags=re.M):
-        h = os.path.join(CSRC, name)
-        if os.path.exists(h) and h not in seen:
-            seen.add(h)
-            _headers_of(h, seen)
+        for h in (os.path.join(CSRC, name), os.path.join(INCLUDE, name)):
+            if os.path.exists(h) and h not in seen:
+                seen.add(h)
+                _headers_of(h, seen)
     return seen
 
 
@@ -95,7 +98,7 @@ def build_ffi(force=False, verbose=False):
     spec = importlib.util.spec_from_file_location("_nasseg_ffi_gen", os.path.join(HERE, "ffi_gen.py"))
     gen = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(gen)
-    header = os.path.join(os.path.dirname(HERE), "include", "nasseg.h")
+    header = os.path.join(INCLUDE, "nasseg.h")
     try:
         path = gen.build(header, HERE, OBJ_DIR, force=force)
     except (RuntimeError, OSError) as e:  # (no compiler / headers: ctypes stays)

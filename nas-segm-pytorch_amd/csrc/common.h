@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "nasseg.h"  // the C ABI: every entry point is defined against its declaration there
+
 #define NASSEG_OK 0
 #define NASSEG_ERR_ARG (-1)
 #define NASSEG_ERR_LAUNCH (-2)
@@ -89,11 +91,10 @@ __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<floa
 // the twin nasseg_bf16_<op> with identical arguments.  Only storage changes: values are
 // widened to fp32 on load and rounded to nearest-even on store; all arithmetic, the MFMA
 // accumulation, statistics, parameters, parameter gradients and workspaces stay fp32.
-// bf16_t is a struct so that an activation can never be read as a number by accident.
+// bf16_t is the header's nasseg_bf16_t: a struct, so that an activation can never be read as a number by
+// accident.
 // ---------------------------------------------------------------------------
-struct bf16_t {
-  uint16_t v;
-};
+typedef nasseg_bf16_t bf16_t;
 #ifdef NASSEG_BF16
 typedef bf16_t act_t;
 #define NASSEG_FN(name) nasseg_bf16_##name

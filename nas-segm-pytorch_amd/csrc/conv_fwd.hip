@@ -33,12 +33,6 @@
 #include <cstdio>
 #include <cstdlib>
 
-// Which pointwise calls take the persistent kernel (conv_pw_kernel).  Default (-2): where it measured
-// faster (pw_fwd_plan).  v >= 0: every call it supports over at least v output pixels (0: all of them - what
-// the parity tests use; a huge value: none); v == -1 only queries.  Returns the previous setting.
-// Process-wide; outputs do not depend on it, BatchNorm statistics only in the rounding of their partial sums.
-extern "C" int64_t nasseg_conv_pw_min_pixels(int64_t v);
-
 #if NASSEG_FP32_ONLY
 std::atomic<int> g_conv_deep_k{1};
 #else
@@ -1514,6 +1508,10 @@ int nasseg_pack_weights(int count, const float* const* w, float* const* wp, cons
 #endif  // NASSEG_FP32_ONLY
 
 #if NASSEG_FP32_ONLY
+// Which pointwise calls take the persistent kernel (conv_pw_kernel).  Default (-2): where it measured
+// faster (pw_fwd_plan).  v >= 0: every call it supports over at least v output pixels (0: all of them - what
+// the parity tests use; a huge value: none); v == -1 only queries.  Returns the previous setting.
+// Process-wide; outputs do not depend on it, BatchNorm statistics only in the rounding of their partial sums.
 int64_t nasseg_conv_pw_min_pixels(int64_t v) {
   return v == -1 ? g_pw_min_pixels.load() : g_pw_min_pixels.exchange(v < 0 ? -2 : v);
 }

@@ -25,9 +25,6 @@
 
 #include "conv_common.h"
 
-extern "C" int nasseg_wgrad_finalize_many(int count, const float* const* partial, float* const* dw,
-                                          const int* dims, void* stream);
-
 #if NASSEG_FP32_ONLY
 // pixels from which the narrow kernel rebuilds z instead of loading it (nasseg_conv_pw_bwd_rz_min_pixels)
 std::atomic<int64_t> g_pw_rz_min_pixels{1 << 18};

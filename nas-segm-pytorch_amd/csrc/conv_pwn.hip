@@ -43,8 +43,6 @@
 #include <atomic>
 #include <type_traits>
 
-extern "C" int nasseg_conv_pwn_mode(int v);
-
 namespace {
 
 constexpr int kTP = 64;     // pixels per tile

@@ -1131,10 +1131,6 @@ int nasseg_dw_pack_weight(const float* w, float* wt, int C, int K, int flip, voi
 }
 #endif  // NASSEG_FP32_ONLY
 
-int64_t nasseg_dwconv_stats_blocks(int B, int C, int Ho, int Wo, int K, int stride, int dil);
-int64_t nasseg_dwconv_bwd_data_bn_blocks(int B, int C, int Ho, int Wo, int K, int stride, int pad,
-                                         int dil, int transposed);
-
 // grid of the stride-2 backward-data kernel; with the statistics epilogue it is capped (a
 // grid-stride loop does the rest) and made a multiple of C4 / gcd(C4, 256)
 static int s2_blocks(int B, int Hd, int Wd, int C4, bool bst) {
@@ -1559,7 +1555,6 @@ int NASSEG_FN(dwconv_wgrad_many)(int count, const int64_t* desc, void* stream) {
   return NASSEG_OK;
 }
 
-#if NASSEG_FP32_ONLY
 // grid of nasseg_dwconv_bwd_bn: {columns of workgroups, rows of workgroups}; 0 rows: unsupported
 static void dw_bwd_grid(int B, int C, int H, int W, int stride, int* gx, int* gy, int* rpi) {
   const int C4 = C / 4;
@@ -1572,6 +1567,7 @@ static void dw_bwd_grid(int B, int C, int H, int W, int stride, int* gx, int* gy
   if (y < 1) y = 1;
   *gy = (int)y;
 }
+#if NASSEG_FP32_ONLY
 // workgroups (= partial rows of the weight gradient [9][C] and of the statistics [2][C]) of
 // nasseg_dwconv_bwd_bn; 0: geometry not served (3x3, pad 1, dilation 1, stride 1 or 2, C % 4 == 0,
 // C <= 256)
@@ -1582,19 +1578,6 @@ int64_t nasseg_dwconv_bwd_bn_rows(int B, int C, int H, int W, int K, int stride,
   int gx, gy, rpi;
   dw_bwd_grid(B, C, H, W, stride, &gx, &gy, &rpi);
   return (int64_t)gx * gy;
-}
-#else
-int64_t nasseg_dwconv_bwd_bn_rows(int B, int C, int H, int W, int K, int stride, int pad, int dil);
-static void dw_bwd_grid(int B, int C, int H, int W, int stride, int* gx, int* gy, int* rpi) {
-  const int C4 = C / 4;
-  const int Wq = stride == 1 ? W : (W + 1) / 2, Hq = stride == 1 ? H : (H + 1) / 2;
-  *gx = cdiv(Wq * C4, 256);
-  *rpi = stride == 1 ? 16 : 8;
-  const int64_t items = (int64_t)B * cdiv(Hq, *rpi);
-  int64_t y = 1024 / *gx;
-  if (y > items) y = items;
-  if (y < 1) y = 1;
-  *gy = (int)y;
 }
 #endif  // NASSEG_FP32_ONLY
 

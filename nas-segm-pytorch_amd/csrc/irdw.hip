@@ -30,10 +30,6 @@
 // the backward kernel below what it needs: 168 VGPRs and 143 spilled at twelve waves).
 #include "dw_common.h"
 
-extern "C" int nasseg_wgrad_finalize_many(int count, const float* const* partial, float* const* dw, const int* dims,
-                                           void* stream);
-extern "C" int nasseg_rows_sum(float* partial, int nblk, int cols, float* out, void* stream);
-
 namespace {
 
 #ifndef NASSEG_IR_BWD_MINB
@@ -732,8 +728,6 @@ int64_t nasseg_irdw_rows(int B, int H, int W, int K, int C, int stride, int back
   const IrPlan p = ir_plan(B, H, W, K, C, stride, backward != 0);
   return p.ok ? p.grid : 0;
 }
-#else
-int64_t nasseg_irdw_rows(int B, int H, int W, int K, int C, int stride, int backward);
 #endif
 
 #if NASSEG_FP32_ONLY

@@ -470,7 +470,6 @@ struct PoolBnGrid {
 // gather per element (A/B switch)
 std::atomic<int> g_pool_strip{1};
 #endif
-extern "C" int nasseg_pool_strip(int v);
 
 inline int pool_strip_rows(int mode) { return mode == 1 ? 4 : (mode == 2 ? 2 : 1); }
 inline PoolBnGrid pool_bn_grid(int B, int H, int W, int C, int strip = 0) {
@@ -503,8 +502,6 @@ int nasseg_pool_strip(int v) {
   if (v < 0) return g_pool_strip.load();
   return g_pool_strip.exchange(v > 2 ? 1 : v);
 }
-#else
-int64_t nasseg_maxpool_bn_bwd_blocks(int B, int H, int W, int C, int K, int stride, int pad);
 #endif
 
 // y = maxpool3x3(scale*z + shift) (padding 1, stride 1 or 2; scale / shift null = identity); idx: uint8 winner

@@ -695,8 +695,6 @@ int64_t nasseg_cat_src_blocks(int B, int Ho, int Wo, int C) {
   const CatGrid g = cat_grid(B, Ho, Wo, C);
   return (int64_t)g.gx * g.gy;
 }
-#else
-int64_t nasseg_cat_src_blocks(int B, int Ho, int Wo, int C);
 #endif
 
 // one input x [B][Hi][Wi][C] of a concatenation -> y[b,oy,ox, yoff:yoff+C] (row stride ldy), resized when

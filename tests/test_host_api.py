@@ -29,6 +29,26 @@ def test_library_exports_every_declared_symbol():
     assert isinstance(lib.last_error(), str)
 
 
+def test_every_bf16_twin_mirrors_its_fp32_entry_point():
+    """functional._k swaps nasseg_<op> for nasseg_bf16_<op> and passes the same arguments: a twin has its fp32 entry
+    point's return type, argument count and argument types, except that some `float*` became `nasseg_bf16_t*` -
+    with the same const-ness"""
+    from nas_segm_amd._lib import HEADER_PATH
+    from nas_segm_amd.ffi_gen import prototypes
+
+    protos = {p.name: p for p in prototypes(HEADER_PATH)}
+    twins = [n for n in protos if n.startswith("nasseg_bf16_")]
+    assert len(twins) >= 54
+    for name in twins:
+        twin, base = protos[name], protos.get("nasseg_" + name[len("nasseg_bf16_"):])
+        assert base is not None, name
+        assert twin.ret == base.ret and len(twin.args) == len(base.args), name
+        for t, b in zip(twin.args, base.args):
+            if t.ctype != b.ctype:
+                assert t.ctype == b.ctype.replace("float", "nasseg_bf16_t") and "float*" in b.ctype, (name, t, b)
+            assert (t.levels, t.const) == (b.levels, b.const), (name, t, b)
+
+
 def test_workspace_queries_are_pure_host_calls():
     from nas_segm_amd import lib
 

@@ -1,12 +1,12 @@
 """Host side of the fused distillation loss and the multi-tensor Polyak update (no GPU needed): which kd_crit the
 decoder-only step fuses (engine/trainer.py: native_kd), the nasseg_polyak tables (engine/optim_native.py:
 polyak_tables) and the new prototypes of include/nasseg.h."""
-import re
 
 import numpy as np
 import torch
 
 from nas_segm_amd._lib import HEADER_PATH, parse_header, pointer_access
+from nas_segm_amd.ffi_gen import prototypes
 from nas_segm_amd.engine import trainer
 from nas_segm_amd.engine.optim_native import polyak_eligible, polyak_tables
 
@@ -92,8 +92,7 @@ def test_header_entries_and_constness():
                                              (10, "w")], prefix
     # the Polyak table is a const int64_t* (a "read" to the recorder: its caller annotates the writes behind it)
     assert acc["nasseg_polyak"] == [(0, "r"), (2, "r")]
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER_PATH).read(), flags=re.S)
-    proto = re.search(r"\bnasseg_polyak\s*\(([^)]*)\)", text).group(1)
-    assert [a.split()[0] for a in proto.split(",")][4:6] == ["float", "float"]
-    fwd = re.search(r"\bnasseg_bf16_ce_mse_fwd\s*\(([^)]*)\)", text).group(1)
-    assert "const nasseg_bf16_t* logits" in fwd and "const float* teacher" in fwd
+    args = {p.name: p.args for p in prototypes(HEADER_PATH)}
+    assert [a.ctype for a in args["nasseg_polyak"]][4:6] == ["float", "float"]
+    fwd = [(a.ctype, a.name) for a in args["nasseg_bf16_ce_mse_fwd"]]
+    assert ("const nasseg_bf16_t*", "logits") in fwd and ("const float*", "teacher") in fwd
