@@ -558,6 +558,30 @@ int nasseg_resize_cubic(const float* x, int B, int h, int w, int C, const int* t
                         int H, int W, void* stream);
 int nasseg_resize_cubic_argmax(const float* x, int B, int h, int w, int C, const int* taps, const float* coef,
                                uint8_t* labels, int H, int W, void* stream);
+/* Test-time ensemble over scales and mirroring: what a user of the notebooks' pipeline (examples/inference/) or of
+ * validate() (src/engine/inference.py:58-66) does by hand on the host - run the network on resized and mirrored
+ * images, bring every result back to the image's size, soft-max, average, argmax - without a full-resolution
+ * tensor per view.
+ *   nasseg_view_image: x NHWC [B][Hi][Wi][C] (any C >= 1) -> y [B][Ho][Wo][C], resized bilinearly with
+ *     align_corners=False (the arithmetic of nasseg_bilinear_fwd) and, mirror != 0, with its columns reversed.
+ *   nasseg_fuse_views: n_views <= 16 logit maps views[v] (HOST array of device addresses), NHWC [B][h_v][w_v][C];
+ *     dims (HOST) [n_views][3] = {h_v, w_v, offset of the view's block in taps / coef}.  The arrays are copied into
+ *     the kernel's arguments: a recorded call reads no device-side table of them.  taps int32 / coef float32
+ *     (device): per view a block of n_taps (H + W) entries, n_taps = 4 (the cubic tables above) or 2 (bilinear,
+ *     align_corners=False) - per output row, then per output column, n_taps source indices and weights; a mirrored
+ *     view is un-mirrored by its column indices (t -> w_v - 1 - t), the kernel has no mirror logic.  Per output
+ *     pixel and view: r_v[c] = the horizontal pass over the n_taps source rows, then the vertical pass, each summed
+ *     in tap order from zero without FMA contraction (n_taps = 4, un-mirrored: nasseg_resize_cubic bit for bit);
+ *     p_v = softmax_c(r_v) in fp32 with the maximum subtracted; P = sum_v p_v in view order.  Outputs, each may be
+ *     null: labels uint8 [B][H][W] = argmax_c P (lowest index wins ties, so does the first NaN); probs fp32 NHWC
+ *     [B][H][W][C] = P / n_views; cm int64 [n][n] += the histogram of (gt, label) over pixels with gt < n, as
+ *     nasseg_argmax_cm (gt uint8 [B][H][W]; integer atomics: exact and reproducible); mean fp32 NHWC [B][H][W][C]
+ *     = (sum_v r_v) / n_views, no softmax (depth).  labels / probs / cm need C <= 64; n <= 256. */
+int nasseg_view_image(const float* x, float* y, int B, int Hi, int Wi, int C, int Ho, int Wo, int mirror,
+                      void* stream);
+int nasseg_fuse_views(int n_views, const float* const* views, const int* dims, const int* taps, const float* coef,
+                      int n_taps, int B, int C, int H, int W, const uint8_t* gt, int n, uint8_t* labels, float* probs,
+                      int64_t* cm, float* mean, void* stream);
 
 /* ---- bfloat16 activation storage --------------------------------------------
  * Every entry point above that reads or writes ACTIVATIONS (feature maps and their gradients)
@@ -745,6 +769,11 @@ int nasseg_bf16_resize_cubic(const nasseg_bf16_t* x, int B, int h, int w, int C,
                              float* y, int H, int W, void* stream);
 int nasseg_bf16_resize_cubic_argmax(const nasseg_bf16_t* x, int B, int h, int w, int C, const int* taps,
                                     const float* coef, uint8_t* labels, int H, int W, void* stream);
+int nasseg_bf16_view_image(const nasseg_bf16_t* x, nasseg_bf16_t* y, int B, int Hi, int Wi, int C, int Ho, int Wo,
+                           int mirror, void* stream);
+int nasseg_bf16_fuse_views(int n_views, const nasseg_bf16_t* const* views, const int* dims, const int* taps,
+                           const float* coef, int n_taps, int B, int C, int H, int W, const uint8_t* gt, int n,
+                           uint8_t* labels, float* probs, int64_t* cm, float* mean, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,7 @@ from .. import functional as F
 from ..helpers.miou_utils import compute_iu, compute_ius_accs
 from ..helpers.utils import try_except
 from .predict import Predictor  # noqa: F401  (the reference's inference notebooks, on the device)
+from .predict import ensemble_views, view_inputs
 
 logger = logging.getLogger(__name__)
 
@@ -120,8 +121,16 @@ def validate_depth(segmenter, val_loader, epoch, epoch2, min_depth=1e-3, max_dep
 
 @try_except
 def validate(segmenter, val_loader, epoch, epoch2, num_classes=-1, print_every=10,
-             omit_classes=[0]):
-    """Evaluate the candidate; returns the scalar reward."""
+             omit_classes=[0], scales=None, flip=False):
+    """Evaluate the candidate; returns the scalar reward.
+
+    ``scales`` (None: one forward per batch, as the reference) / ``flip``: score the test-time ensemble instead -
+    per batch one forward per view (engine/predict.ensemble_views: the image resized bilinearly to each scale, and
+    mirrored) and ONE F.fuse_views launch that up-samples every view bilinearly to the ground truth's size,
+    averages the class probabilities, takes the argmax and updates the confusion matrix."""
+    views = None if scales is None else ensemble_views(scales, flip, "validate")
+    if scales is None and flip is not False:
+        raise ValueError("validate: flip needs scales (scales=(1.0,) for the mirrored pair alone)")
     ds = getattr(val_loader, "dataset", None)
     if ds is not None:
         try:
@@ -140,10 +149,16 @@ def validate(segmenter, val_loader, epoch, epoch2, num_classes=-1, print_every=1
                 image = sample["image"].to(device=device, dtype=torch.float32).contiguous(
                     memory_format=torch.channels_last)
                 gt = sample["mask"].to(device).to(torch.uint8)  # astype(np.uint8) in the reference
-                output = segmenter(image)
-                if isinstance(output, tuple):
-                    output, _ = output
-                F.argmax_confusion(output, gt, num_classes, cm=cm)
+                if views is not None:
+                    outputs = [segmenter(x) for x in view_inputs(image, views)]
+                    outputs = [o[0] if isinstance(o, tuple) else o for o in outputs]
+                    F.fuse_views(outputs, gt.shape[1:], [m for _, m in views], mode="bilinear", gt=gt,
+                                 n_classes=num_classes, cm=cm)
+                else:
+                    output = segmenter(image)
+                    if isinstance(output, tuple):
+                        output, _ = output
+                    F.argmax_confusion(output, gt, num_classes, cm=cm)
                 if i % print_every == 0:
                     logger.info(" Val epoch: {} [{}/{}]\tMean IoU: {:.3f}".format(
                         epoch, i, len(val_loader),

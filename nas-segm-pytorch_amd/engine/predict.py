@@ -8,6 +8,11 @@ identity plan), the eval forward, ``F.resize_cubic_argmax`` / ``F.resize_cubic``
 against that host pipeline restated in numpy (data/datasets.resize_cubic_to); only the uint8 image goes to the
 device and only the labels (or the depth map) come back.
 
+Test-time ensemble (``scales=``, ``flip=``): the network runs on the image at several scales and on the mirrored
+image (``F.view_image``), and ONE launch (``F.fuse_views``, csrc/ensemble.hip) brings every result back to the
+output size, soft-maxes it, averages and takes the argmax - no view is stored at full resolution.  The default,
+``scales=(1.0,), flip=False``, is the single forward above, unchanged.
+
 At batch 1 an eval forward is several hundred small launches, so a shape seen twice is recorded into a hipGraph
 (``torch.cuda.CUDAGraph``, as engine/graphed.py records training steps) and replayed: one host-to-device copy into
 the capture's static uint8 buffer, one replay, one clone of the output.  Replayed and host-launched calls run the
@@ -29,6 +34,38 @@ TASKS = ("segm", "depth")
 DTYPES = (torch.float32, torch.bfloat16)
 MAX_CAPTURES = 4  # hipGraphs one Predictor keeps (least recently used first out); each owns a private memory pool
 _SEEN_KEPT = 64   # shapes whose calls `graph="auto"` counts
+
+
+def ensemble_views(scales, flip, who="Predictor"):
+    """The views (scale, mirrored) of a test-time ensemble, in the order their probabilities are added: per scale
+    the plain view, then (``flip``) the mirrored one.  Scales: a non-empty sequence of positive finite numbers
+    without duplicates; at most F.MAX_VIEWS views."""
+    import math
+
+    if not isinstance(flip, (bool, np.bool_)):
+        raise ValueError("{}: flip must be True or False (got {!r})".format(who, flip))
+    try:
+        scales = tuple(float(s) for s in scales)
+    except (TypeError, ValueError):
+        raise ValueError("{}: scales must be a sequence of numbers (got {!r})".format(who, scales))
+    if not scales or any(not math.isfinite(s) or s <= 0 for s in scales):
+        raise ValueError("{}: scales must be a non-empty sequence of positive finite numbers (got {!r})".format(
+            who, scales))
+    if len(set(scales)) != len(scales):
+        raise ValueError("{}: a scale is given twice (got {!r})".format(who, scales))
+    n = len(scales) * (2 if flip else 1)
+    if n > F.MAX_VIEWS:
+        raise ValueError("{}: {} views (scales{}), at most {} are fused".format(
+            who, n, " x 2 for mirroring" if flip else "", F.MAX_VIEWS))
+    return tuple((s, m) for s in scales for m in ((False, True) if flip else (False,)))
+
+
+def view_inputs(x, views):
+    """the network inputs of ``views`` for the normalised image x (B x 3 x H x W): the view (1.0, False) is x
+    itself, every other one F.view_image launch"""
+    H, W = x.shape[2:]
+    return [x if (s == 1.0 and not m) else F.view_image(x, (F.view_size(H, s), F.view_size(W, s)), m)
+            for s, m in views]
 
 
 def _first(output):
@@ -100,13 +137,21 @@ class Predictor(object):
     graph   "auto": a shape (batch, image size, out_size, dtype) is replayed from a hipGraph from its second call on,
             when B*H*W <= engine.graphed.AUTO_GRAPH_MAX_PIXELS and NASSEG_GRAPH is not "0" ("1": every shape);
             True: from the first call; False: always launched from the host.
+    scales, flip   the test-time ensemble: one view per scale (its input max(1, floor(n s + 0.5)) on a side, resized
+            bilinearly) and, ``flip``, its mirror image; at most 16 views.  Labels: the argmax of the mean over the
+            views of softmax(cubic-resized logits) (at most 64 classes); depth: the mean of the cubic-resized maps.
+            One hipGraph holds every forward and the fusion; "auto" counts the pixels of all views.  The default
+            (1.0,), False is the single forward.
 
     ``pred(img, out_size=None)``: img a uint8 H x W x 3 or B x H x W x 3 numpy array or tensor (host or device);
     out_size None: the image's size, "model": the network's output size, (H, W): any other.  Returns a device tensor
     (H, W) or (B, H, W).  ``pred.logits(x)``: the network's first output for a normalised B x 3 x H x W float x.
+    ``pred.probabilities(img, out_size=None)`` (segmentation): the fp32 mean over the views of the class
+    probabilities, (C, H, W) or (B, C, H, W).
     """
 
-    def __init__(self, model, task="segm", dtype=torch.float32, graph="auto", max_captures=MAX_CAPTURES):
+    def __init__(self, model, task="segm", dtype=torch.float32, graph="auto", max_captures=MAX_CAPTURES,
+                 scales=(1.0,), flip=False):
         if task not in TASKS:
             raise ValueError("Predictor: task must be one of {} (got {!r})".format(TASKS, task))
         if dtype not in DTYPES:
@@ -115,6 +160,8 @@ class Predictor(object):
             raise ValueError("Predictor: graph must be 'auto', True or False (got {!r})".format(graph))
         if not isinstance(model, nn.Module):
             raise ValueError("Predictor: model must be a torch.nn.Module (got {})".format(type(model).__name__))
+        self.views = ensemble_views(scales, flip)
+        self.scales, self.flip = tuple(s for s, m in self.views if not m), bool(flip)
         self._model = weakref.ref(model)
         self.task, self.dtype, self.graph = task, dtype, graph
         self.max_captures = max(1, int(max_captures))
@@ -128,7 +175,20 @@ class Predictor(object):
         img, squeeze = self._image(img)
         B, H, W = (int(s) for s in img.shape[:3])
         size = (H, W) if out_size is None else out_size
-        out = self._run(("predict", B, H, W, size), img, B * H * W, lambda m: self._predict_fn(m, size))
+        if self.views == ((1.0, False),):
+            out = self._run(("predict", B, H, W, size), img, B * H * W, lambda m: self._predict_fn(m, size))
+        else:
+            out = self._run_views("ensemble", img, size, probs=False)
+        return out[0] if squeeze else out
+
+    def probabilities(self, img, out_size=None):
+        """the mean over the views of softmax(cubic-resized logits): fp32 (C, H, W) or (B, C, H, W)"""
+        if self.task != "segm":
+            raise ValueError("Predictor.probabilities: a {} network has no classes".format(self.task))
+        out_size = _check_out_size(out_size)
+        img, squeeze = self._image(img)
+        out = self._run_views("probabilities", img, tuple(img.shape[1:3]) if out_size is None else out_size,
+                              probs=True)
         return out[0] if squeeze else out
 
     def logits(self, x):
@@ -164,6 +224,44 @@ class Predictor(object):
             if segm:
                 return F.resize_cubic_argmax(logits, (H, W), tables=keep["tables"])
             return F.resize_cubic(logits, (H, W), tables=keep["tables"])[:, 0]
+
+        return run
+
+    def _run_views(self, what, img, size, probs):
+        if size == "model":
+            raise ValueError("Predictor: out_size='model' needs the single view (1.0, False): the views of an "
+                             "ensemble differ in size")
+        B, H, W = (int(s) for s in img.shape[:3])
+        size = (int(size[0]), int(size[1]))
+        n_pixels = B * sum(F.view_size(H, s) * F.view_size(W, s) for s, _ in self.views)
+        return self._run((what, B, H, W, size, self.scales, self.flip), img, n_pixels,
+                         lambda m: self._views_fn(m, size, probs))
+
+    def _views_fn(self, model, size, probs):
+        segm = self.task == "segm"
+        mirrored = [m for _, m in self.views]
+
+        def run(img, keep):
+            if "plan" not in keep:
+                keep["plan"] = F.prepare_plan(img.device, *img.shape[:3], dtype=self.dtype)
+            x = F.prepare_image(img, self.dtype, plan=keep["plan"])
+            outs = []
+            for xv in view_inputs(x, self.views):
+                z = _first(model(xv))
+                if not torch.is_tensor(z) or z.dim() != 4:
+                    raise ValueError("Predictor: the network's output is not B x C x h x w logits")
+                outs.append(z)
+            C = outs[0].shape[1]
+            if C > F.MAX_FUSE_CLASSES:
+                raise ValueError("Predictor: an ensemble fuses at most {} channels (got {})".format(
+                    F.MAX_FUSE_CLASSES, C))
+            if "fuse" not in keep:
+                keep["fuse"] = F.fuse_tables(x.device, [z.shape[2:] for z in outs], mirrored, size[0], size[1])
+            if not segm:
+                return F.fuse_views_mean(outs, size, mirrored, tables=keep["fuse"])[:, 0]
+            if probs:
+                return F.fuse_views(outs, size, mirrored, return_probs=True, tables=keep["fuse"])[1]
+            return F.fuse_views(outs, size, mirrored, tables=keep["fuse"])
 
         return run
 

@@ -2825,6 +2825,193 @@ def resize_cubic_argmax(x, size, tables=None):
     return labels
 
 
+# -- test-time ensemble over scales and mirroring (csrc/ensemble.hip) ---------------------------------------------
+MAX_VIEWS = 16         # views one nasseg_fuse_views launch fuses
+MAX_FUSE_CLASSES = 64  # channels of a fused view (the kernel's per-pixel sums live in registers)
+FUSE_MODES = {"cubic": 4, "bilinear": 2}  # taps per axis
+_FUSE_TABLES = collections.OrderedDict()
+
+
+def view_size(n, s):
+    """the side of a view's network input for an image side n at scale s: max(1, floor(n s + 0.5))"""
+    import math
+
+    return max(1, int(math.floor(n * s + 0.5)))
+
+
+def _size_pair(name, size):
+    try:
+        H, W = (int(s) for s in size)
+        ok = H > 0 and W > 0 and (H, W) == tuple(size)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise NassegError("{}: size must be two positive integers (got {!r})".format(name, size))
+    return H, W
+
+
+def view_image(x, size, mirror=False):
+    """The network input of one view: x B x C x Hi x Wi (channels_last, fp32 or bf16) resized bilinearly to ``size``
+    with align_corners=False (torch's F.interpolate, nasseg_bilinear_fwd's arithmetic) and, ``mirror``, with its
+    columns reversed; one nasseg_view_image launch."""
+    x = _cl(x.detach())
+    B, C, Hi, Wi = x.shape
+    Ho, Wo = _size_pair("view_image", size)
+    if min(B, C, Hi, Wi) == 0:
+        raise NassegError("view_image: empty input {}".format(tuple(x.shape)))
+    y = _new(x, B, C, Ho, Wo)
+    lib.call(_k("nasseg_view_image", x), ptr(x), ptr(y), B, Hi, Wi, C, Ho, Wo, int(bool(mirror)), current_stream())
+    return y
+
+
+def linear_tables_host(h, w, H, W):
+    """(taps int32 [2 (H + W)], coef float32 [2 (H + W)]) of an h x w -> H x W bilinear resize with
+    align_corners=False, rows then columns: torch's area_pixel_compute_source_index in fp32 (csrc/resize_index.h) -
+    scale = in / out, src = max(scale (dst + 0.5) - 0.5, 0), taps floor(src) and the next (clipped), weights
+    1 - frac and frac; equal sizes: the identity."""
+    import numpy as np
+
+    out = []
+    for n_src, n_dst in ((h, H), (w, W)):
+        d = np.arange(n_dst, dtype=np.float32)
+        if n_src == n_dst:
+            src = d
+        else:
+            scale = np.float32(n_src) / np.float32(n_dst)
+            src = np.maximum(scale * (d + np.float32(0.5)) - np.float32(0.5), np.float32(0))
+        i0 = np.minimum(src.astype(np.int64), n_src - 1)
+        i1 = np.minimum(i0 + 1, n_src - 1)
+        l1 = np.clip(src - i0.astype(np.float32), np.float32(0), np.float32(1)).astype(np.float32)
+        out.append((np.stack([i0, i1], 1), np.stack([np.float32(1) - l1, l1], 1)))
+    (iy, wy), (ix, wx) = out
+    return (np.concatenate([iy.ravel(), ix.ravel()]).astype(np.int32),
+            np.concatenate([wy.ravel(), wx.ravel()]).astype(np.float32))
+
+
+def fuse_tables_host(shapes, mirrored, H, W, mode="cubic"):
+    """The tables of ``fuse_views``: per view (h, w) of ``shapes`` a block of T (H + W) entries, T = 4
+    (``cubic_tables_host``) or 2 (``linear_tables_host``).  A mirrored view is un-mirrored here: its column taps t
+    become w - 1 - t (the weights and the order of the taps stay: the sums are those of the resize of the flipped
+    map).  Returns (taps int32, coef float32, dims int32 [V][3] = h, w, offset of the block)."""
+    import numpy as np
+
+    if mode not in FUSE_MODES:
+        raise NassegError("fuse_views: mode must be one of {} (got {!r})".format(sorted(FUSE_MODES), mode))
+    T = FUSE_MODES[mode]
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    mirrored = [bool(m) for m in mirrored]
+    if not shapes or len(shapes) != len(mirrored):
+        raise NassegError("fuse_views: {} shapes and {} mirror flags".format(len(shapes), len(mirrored)))
+    taps, coef, dims = [], [], []
+    for (h, w), m in zip(shapes, mirrored):
+        t, c = (cubic_tables_host if T == 4 else linear_tables_host)(h, w, H, W)
+        if m:
+            t = t.copy()
+            t[T * H:] = w - 1 - t[T * H:]
+        dims.append((h, w, len(taps) * T * (H + W)))
+        taps.append(t)
+        coef.append(c)
+    return np.concatenate(taps), np.concatenate(coef), np.asarray(dims, np.int32)
+
+
+def fuse_tables(device, shapes, mirrored, H, W, mode="cubic"):
+    """``fuse_tables_host`` with taps and coef uploaded to ``device`` (dims stays on the host), cached per argument
+    list.  A caller that records the fusion into a hipGraph holds on to what it passes (``tables=``): the cache may
+    drop it later."""
+    shapes = tuple((int(h), int(w)) for h, w in shapes)
+    mirrored = tuple(bool(m) for m in mirrored)
+
+    def make():
+        taps, coef, dims = fuse_tables_host(shapes, mirrored, H, W, mode)
+        return torch.from_numpy(taps).to(device), torch.from_numpy(coef).to(device), dims
+
+    return _lru(_FUSE_TABLES, (torch.device(device), shapes, mirrored, int(H), int(W), mode), make)
+
+
+def _fuse(name, views, size, mirrored, mode, tables, gt, n_classes, cm, want_labels, want_probs, want_mean):
+    views = [_cl(v.detach()) for v in views]
+    if not views or len(views) > MAX_VIEWS:
+        raise NassegError("{}: between 1 and {} views (got {})".format(name, MAX_VIEWS, len(views)))
+    B, C = views[0].shape[:2]
+    first = views[0]
+    for v in views:
+        if v.dtype != first.dtype or v.device != first.device or tuple(v.shape[:2]) != (B, C) or v.numel() == 0:
+            raise NassegError("{}: the views differ in dtype, device, batch or channels, or one is empty".format(name))
+    if C > MAX_FUSE_CLASSES:
+        raise NassegError("{}: {} channels (at most {})".format(name, C, MAX_FUSE_CLASSES))
+    H, W = _size_pair(name, size)
+    mirrored = [bool(m) for m in mirrored]
+    if len(mirrored) != len(views):
+        raise NassegError("{}: {} views and {} mirror flags".format(name, len(views), len(mirrored)))
+    if mode not in FUSE_MODES:
+        raise NassegError("{}: mode must be one of {} (got {!r})".format(name, sorted(FUSE_MODES), mode))
+    T = FUSE_MODES[mode]
+    shapes = [tuple(v.shape[2:]) for v in views]
+    taps, coef, dims = tables if tables is not None else fuse_tables(first.device, shapes, mirrored, H, W, mode)
+    n = len(views) * T * (H + W)
+    if (taps.dtype != torch.int32 or coef.dtype != torch.float32 or taps.numel() != n or coef.numel() != n
+            or taps.device != first.device or coef.device != first.device or tuple(dims.shape) != (len(views), 3)
+            or [tuple(d[:2]) for d in dims.tolist()] != [tuple(s) for s in shapes]
+            or any(d[2] < 0 or d[2] + T * (H + W) > n for d in dims.tolist())):
+        raise NassegError("{}: tables do not match {} views resized to {}x{}".format(name, len(views), H, W))
+    if gt is not None:
+        require_device(gt)
+        if gt.dtype != torch.uint8 or tuple(gt.shape) != (B, H, W):
+            raise NassegError("{}: gt must be uint8 {} (got {} {})".format(name, (B, H, W), gt.dtype, tuple(gt.shape)))
+        gt = gt.contiguous()
+        if n_classes is None:
+            raise NassegError("{}: gt needs n_classes".format(name))
+        n_classes = int(n_classes)
+        if not 0 < n_classes <= 256:
+            raise NassegError("{}: n_classes={} (at most 256)".format(name, n_classes))
+        if cm is None:
+            cm = torch.zeros((n_classes, n_classes), device=first.device, dtype=torch.int64)
+        elif (cm.dtype != torch.int64 or tuple(cm.shape) != (n_classes, n_classes) or not cm.is_contiguous()
+              or cm.device != first.device):
+            raise NassegError("{}: cm must be a contiguous int64 {} tensor on the device".format(
+                name, (n_classes, n_classes)))
+    else:
+        cm = None
+    dev = first.device
+    labels = torch.empty((B, H, W), device=dev, dtype=torch.uint8) if want_labels else None
+    probs = (torch.empty((B, C, H, W), device=dev, dtype=torch.float32, memory_format=torch.channels_last)
+             if want_probs else None)
+    mean = (torch.empty((B, C, H, W), device=dev, dtype=torch.float32, memory_format=torch.channels_last)
+            if want_mean else None)
+    table = (ctypes.c_void_p * len(views))(*[ptr(v) for v in views])
+    hdims = (ctypes.c_int * (3 * len(views)))(*[int(d) for d in dims.ravel()])
+    if lib.recorder is not None:  # (the pointer table: what the launch reads behind it)
+        lib.recorder.annotate(reads=views + [taps, coef, gt], writes=[labels, probs, cm, mean])
+    lib.call(_k("nasseg_fuse_views", first), len(views), table, hdims, ptr(taps), ptr(coef), T, B, C, H, W, ptr(gt),
+             n_classes if cm is not None else 0, ptr(labels), ptr(probs), ptr(cm), ptr(mean), current_stream())
+    return labels, probs, cm, mean
+
+
+def fuse_views(views, size, mirrored, mode="cubic", gt=None, n_classes=None, cm=None, return_probs=False,
+               tables=None, return_mean=False):
+    """The ensemble of V <= 16 views in ONE nasseg_fuse_views launch: views[v] B x C x h_v x w_v logits (channels_last,
+    all fp32 or all bf16, C <= 64), ``mirrored[v]``: the view's image was mirrored.  Every view is resampled to
+    ``size`` (mode "cubic": ``resize_cubic``'s arithmetic bit for bit; "bilinear": align_corners=False), soft-maxed
+    over C in fp32, the probabilities are added in view order and the label is their argmax (lowest index wins
+    ties) - nothing of a view is stored at full resolution.
+
+    Returns uint8 labels B x H x W; with ``gt`` (uint8 B x H x W) and ``n_classes``: (cm, labels), the int64
+    confusion matrix ``cm`` (created when None) accumulated over the pixels with gt < n_classes as
+    ``argmax_confusion`` does.  ``return_probs`` appends the mean probabilities, ``return_mean`` the mean of the
+    resampled views (both fp32 B x C x H x W channels_last).  ``tables``: what ``fuse_tables`` returns for it."""
+    labels, probs, cm, mean = _fuse("fuse_views", views, size, mirrored, mode, tables, gt, n_classes, cm, True,
+                                    return_probs, return_mean)
+    out = ([cm] if gt is not None else []) + [labels] + ([probs] if return_probs else []) + (
+        [mean] if return_mean else [])
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def fuse_views_mean(views, size, mirrored, mode="cubic", tables=None):
+    """The mean over the views of their maps resampled to ``size`` (no softmax: depth) -> fp32 B x C x H x W
+    channels_last; one nasseg_fuse_views launch.  One un-mirrored view, mode "cubic": ``resize_cubic``."""
+    return _fuse("fuse_views_mean", views, size, mirrored, mode, tables, None, None, None, False, False, True)[3]
+
+
 def prepare_plan(device, B, H, W, dtype=torch.float32):
     """(desc, taps, lut) of ``prepare_image`` for B images of H x W on ``device``: nasseg_augment's descriptor and
     tables with an identity plan - one tap per row and column, coefficients (0, 2048, 0, 0), so the fixed-point

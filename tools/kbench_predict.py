@@ -7,9 +7,14 @@
            numpy restatement, argmax).
   e2e      ms per pred(img) of a uint8 2048x1024 image (WACV arch0, labels at the image's size), host-launched and
            replayed.
+  ensemble the test-time ensemble of WACV arch0 on a 2048x1024 image, scales 0.5 .. 1.75 in steps of 0.25 plus
+           mirroring (12 views): the fused launch alone (F.fuse_views on the 12 logit maps), the same fusion composed
+           from the single-view entry points (per view F.resize_cubic to full size, torch softmax and add; then
+           argmax - the mirrored maps flipped outside the timed region), and pred(img) end to end, host-launched
+           and replayed.
 
 Device times: HIP events around KBENCH_ITERS calls (default 20) after 3 warm-up calls; host path: wall clock.
-usage (GPU box): python tools/kbench_predict.py [forward|post|e2e|all]   One JSON line per measurement on stdout."""
+usage (GPU box): python tools/kbench_predict.py [forward|post|e2e|ensemble|all]   One JSON line per measurement on stdout."""
 import json
 import os
 import sys
@@ -99,9 +104,50 @@ def e2e():
         emit(bench="e2e", net="wacv_arch0", image=[1024, 2048], graph=graph, ms=round(ms, 3))
 
 
+def ensemble():
+    from nas_segm_amd.engine.predict import view_inputs
+
+    scales = (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)
+    H, W = 1024, 2048
+    net = net_of("wacv_arch0")
+    img = np.random.RandomState(0).randint(0, 256, (H, W, 3)).astype(np.uint8)
+    plain = Predictor(net, graph=False)
+    pred = Predictor(net, graph=False, scales=scales, flip=True)
+    mirrored = [m for _, m in pred.views]
+    x = F.prepare_image(torch.from_numpy(img[None]).to(DEV))
+    outs = [plain.logits(xv) for xv in view_inputs(x, pred.views)]
+    del x
+    tables = F.fuse_tables(outs[0].device, [z.shape[2:] for z in outs], mirrored, H, W)
+    fused = F.fuse_views(outs, (H, W), mirrored, tables=tables)
+    emit(bench="ensemble", path="fuse_views", views=len(outs), classes=int(outs[0].shape[1]), out=[H, W],
+         ms=round(device_ms(lambda: F.fuse_views(outs, (H, W), mirrored, tables=tables)), 3))
+    plainly = [z.flip(3).contiguous(memory_format=torch.channels_last) if m else z for z, m in zip(outs, mirrored)]
+
+    def composed():
+        total = None
+        for z in plainly:
+            p = torch.softmax(F.resize_cubic(z, (H, W)), dim=1)
+            total = p if total is None else total.add_(p)
+        return total.argmax(1).to(torch.uint8)
+
+    differing = float((composed() != fused).float().mean())
+    emit(bench="ensemble", path="resize_cubic_softmax_add_argmax", views=len(outs), out=[H, W],
+         ms=round(device_ms(composed, n=max(2, ITERS // 4), warm=1), 3), labels_differing=differing)
+    del plainly, outs
+    torch.cuda.empty_cache()
+    for graph in (False, True):
+        pred = Predictor(net, graph=graph, scales=scales, flip=True)
+        ms = device_ms(lambda: pred(img), n=max(2, ITERS // 2), warm=2)
+        emit(bench="ensemble", path="e2e", net="wacv_arch0", image=[H, W], views=len(pred.views), graph=graph,
+             ms=round(ms, 3))
+    single = Predictor(net, graph=True)
+    emit(bench="ensemble", path="e2e_single_view", net="wacv_arch0", image=[H, W], graph=True,
+         ms=round(device_ms(lambda: single(img)), 3))
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     emit(device=torch.cuda.get_device_name(0), torch=torch.__version__, iters=ITERS)
-    for name, fn in (("forward", forward), ("post", post), ("e2e", e2e)):
+    for name, fn in (("forward", forward), ("post", post), ("e2e", e2e), ("ensemble", ensemble)):
         if what in (name, "all"):
             fn()
