@@ -430,6 +430,34 @@ int nasseg_ce_mse_bwd(const float* logits, const void* target, int elem_size, co
                       const float* stats, const float* g_ce, const float* g_mse, int64_t P, int C, int ignore,
                       float* dlogits, void* stream);
 
+/* Class-weighted cross-entropy with hard-example selection: what a caller gets who hands the reference's call
+ * sites - segm_crit of src/main_search.py:435, used at src/engine/trainer.py:144-146,239-250 - a criterion with
+ * class weights (nn.NLLLoss2d(weight=w)) or with online hard-example mining (absent from the reference).
+ * Pixel p is valid iff its label t != ignore and 0 <= t < C; l_p = logsumexp(x_p) - x_p[t], computed exactly as
+ * nasseg_ce_fwd computes it.  select != 0 (needs min_kept >= 1, 0 <= keep_fraction <= 1): n = valid pixels,
+ * k = min(n, max(min_kept, ceil(keep_fraction * n))) (in double), tau = min(t_loss, k-th largest l_p); a valid pixel
+ * is kept iff l_p >= tau on the fp32 values (ties at tau are all kept; t_loss = +inf: top-k only).  select == 0:
+ * every valid pixel is kept, tau = -inf.  Selection ignores the weights.
+ *   loss = sum_kept w[t_p] l_p / sum_kept w[t_p]      (weight: fp32 [C], null = ones; nothing kept: NaN)
+ *   stats = {sum_kept w, tau};  counts = {k, n, pixels kept};  pixel_loss[p] = l_p, -1 where p is not valid
+ * Backward (tau and the kept set are constants): dlogits = gscale * w[t_p] * (softmax(x_p) - onehot(t_p)) / stats[0]
+ * on kept pixels, exact zeros on all others, written once (gscale: device scalar, null = 1).  With unit weights
+ * and no selection loss and dlogits are bit-identical to nasseg_ce_fwd's / nasseg_ce_bwd's.
+ * nasseg_ohem_threshold is the selection alone, over any fp32 array: entries < 0 do not take part; counts[2] =
+ * entries >= tau among those that do.  An exact radix select (11 + 11 + 10 bits of the fp32 pattern) on the device:
+ * no host synchronisation, no allocation, integer atomics only - deterministic, capturable.
+ * ws: nasseg_ohem_workspace() 4-byte words / nasseg_ce_sel_workspace() floats.  P < 2^32. */
+int64_t nasseg_ohem_workspace(void);
+int nasseg_ohem_threshold(const float* pixel_loss, int64_t P, float t_loss, int64_t min_kept, double keep_fraction,
+                          float* tau, int64_t* counts, void* ws, void* stream);
+int64_t nasseg_ce_sel_workspace(void);
+int nasseg_ce_sel_fwd(const float* logits, const void* target, int elem_size, const float* weight, int64_t P, int C,
+                      int ignore, int select, float t_loss, int64_t min_kept, double keep_fraction, float* loss,
+                      float* stats, int64_t* counts, float* pixel_loss, float* ws, void* stream);
+int nasseg_ce_sel_bwd(const float* logits, const void* target, int elem_size, const float* weight,
+                      const float* pixel_loss, const float* stats, const float* gscale, int64_t P, int C, int ignore,
+                      float* dlogits, void* stream);
+
 /* berHu loss of the depth head (BASELINE config 5; absent from the reference - Laina et al.
  * 2016 eq. 2, "parity unpinned") */
 int nasseg_berhu_fwd(const float* pred, const float* target, int64_t n, float* out, float* ws,
@@ -697,6 +725,13 @@ int nasseg_bf16_ce_mse_fwd(const nasseg_bf16_t* logits, const void* target, int 
 int nasseg_bf16_ce_mse_bwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* teacher,
                            const float* stats, const float* g_ce, const float* g_mse, int64_t P, int C, int ignore,
                            nasseg_bf16_t* dlogits, void* stream);
+int nasseg_bf16_ce_sel_fwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* weight,
+                           int64_t P, int C, int ignore, int select, float t_loss, int64_t min_kept,
+                           double keep_fraction, float* loss, float* stats, int64_t* counts, float* pixel_loss,
+                           float* ws, void* stream);
+int nasseg_bf16_ce_sel_bwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* weight,
+                           const float* pixel_loss, const float* stats, const float* gscale, int64_t P, int C,
+                           int ignore, nasseg_bf16_t* dlogits, void* stream);
 int nasseg_bf16_berhu_fwd(const nasseg_bf16_t* pred, const nasseg_bf16_t* target, int64_t n, float* out, float* ws,
                      void* stream);
 int nasseg_bf16_berhu_bwd(const nasseg_bf16_t* pred, const nasseg_bf16_t* target, const float* stats,

@@ -14,14 +14,35 @@
 
 namespace {
 
+// Is a per-pixel loss that takes part (l >= 0; -1 marks the others) kept at threshold tau?  l >= tau on the fp32
+// values, compared through their bit patterns (for non-negative floats the order of the patterns is the order of
+// the values) so that the answer is the same integer comparison the radix selection below made, denormals included.
+__device__ __forceinline__ bool sel_kept(float l, float tau) {
+  if (l < 0.f) return false;
+  return !(tau > 0.f) || __float_as_uint(l) >= __float_as_uint(tau);
+}
+
+// The selection's histograms (3 x 2048 words, see sel_hist_kernel) back to zero, by whatever grid runs this: the
+// forward kernels of nasseg_ce_sel_fwd do it on their way, the selection's launches follow them.
+constexpr int kSelBins = 2048;
+constexpr int kSelHistWords = 3 * kSelBins;
+__device__ __forceinline__ void sel_clear(uint32_t* __restrict__ hist) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < kSelHistWords; i += gridDim.x * blockDim.x) hist[i] = 0u;
+}
+
 // KD (nasseg_ce_mse_fwd): each thread also adds (x - t)^2 over its pixels' rows - ignored pixels included, as
 // nn.MSELoss knows no ignore index - and the workgroup's sum goes to sqpart[blockIdx.x].
-template <typename TL, bool KD = false>
+// SEL (nasseg_ce_sel_fwd): the same per-pixel arithmetic, but l_p goes to pixel_loss[p] (-1 for a pixel that is
+// not valid) and nothing is reduced here.
+template <typename TL, bool KD = false, bool SEL = false>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const act_t* __restrict__ logits,
                                                      const TL* __restrict__ target, int64_t P,
                                                      int C, int ignore, float* __restrict__ partial,
                                                      const float* __restrict__ teacher = nullptr,
-                                                     float* __restrict__ sqpart = nullptr) {
+                                                     float* __restrict__ sqpart = nullptr,
+                                                     float* __restrict__ pixel_loss = nullptr,
+                                                     uint32_t* __restrict__ sel_hist = nullptr) {
+  if (SEL && sel_hist) sel_clear(sel_hist);
   __shared__ float red_l[256];
   __shared__ float red_n[256];
   __shared__ float red_s[KD ? 256 : 1];
@@ -34,15 +55,23 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const act_t* __restrict__ l
         const float d = lda1(lp + c) - teacher[p * C + c];
         sq += d * d;
       }
-    if (t == ignore || t < 0 || t >= C) continue;  // out-of-range labels are skipped, never read
+    if (t == ignore || t < 0 || t >= C) {  // out-of-range labels are skipped, never read
+      if (SEL) pixel_loss[p] = -1.f;
+      continue;
+    }
     float m = lda1(lp);
     for (int c = 1; c < C; ++c) m = fmaxf(m, lda1(lp + c));
     float s = 0.f;
     for (int c = 0; c < C; ++c) s += expf(lda1(lp + c) - m);
     const float lse = m + logf(s);
+    if (SEL) {
+      pixel_loss[p] = lse - lda1(lp + t);
+      continue;
+    }
     loss += lse - lda1(lp + t);
     cnt += 1.f;
   }
+  if (SEL) return;
   red_l[threadIdx.x] = loss;
   red_n[threadIdx.x] = cnt;
   if (KD) red_s[threadIdx.x] = sq;
@@ -113,7 +142,11 @@ __global__ __launch_bounds__(256) void ce_finalize_kernel(const float* __restric
 // backward, by the store loop, which adds gmse * 2 (x - t) / (P*C) to the cross-entropy gradient.  Pixel mapping,
 // per-pixel arithmetic and the reduction order of the cross-entropy part are those of the plain kernel, so the NLL
 // and (with gmse = 0) its gradient are bit-identical to nasseg_ce_fwd / nasseg_ce_bwd.
-template <typename TL, bool BWD, bool KD = false>
+// SEL (nasseg_ce_sel_fwd / _bwd): forward, l_p goes to pixel_loss[p] (-1 where the pixel is not valid) instead of
+// into the workgroup's sums; backward, stats = {sum of the kept pixels' weights, tau}: a pixel is skipped (zeros)
+// unless it is valid and sel_kept(pixel_loss[p], tau), and its factor is gscale * weight[t] / stats[0] - with unit
+// weights the very division of the plain kernel.
+template <typename TL, bool BWD, bool KD = false, bool SEL = false>
 __global__ __launch_bounds__(256) void ce_tile_kernel(const act_t* __restrict__ logits,
                                                       const TL* __restrict__ target, int64_t P, int C,
                                                       int ignore, float* __restrict__ partial,
@@ -122,7 +155,11 @@ __global__ __launch_bounds__(256) void ce_tile_kernel(const act_t* __restrict__ 
                                                       act_t* __restrict__ dlogits,
                                                       const float* __restrict__ teacher = nullptr,
                                                       const float* __restrict__ gmse = nullptr,
-                                                      float* __restrict__ sqpart = nullptr) {
+                                                      float* __restrict__ sqpart = nullptr,
+                                                      const float* __restrict__ weight = nullptr,
+                                                      float* __restrict__ pixel_loss = nullptr,
+                                                      uint32_t* __restrict__ sel_hist = nullptr) {
+  if (!BWD && SEL && sel_hist) sel_clear(sel_hist);
   extern __shared__ float tile[];  // [256][C | 1]
   __shared__ float red_l[256];
   __shared__ float red_n[256];
@@ -132,7 +169,8 @@ __global__ __launch_bounds__(256) void ce_tile_kernel(const act_t* __restrict__ 
   const int64_t ntiles = (P + 255) / 256;
   float loss = 0.f, cnt = 0.f, sq = 0.f;
   float g = 0.f, gm = 0.f;
-  if (BWD) g = (gscale ? gscale[0] : 1.f) / stats[1];
+  if (BWD) g = SEL ? (gscale ? gscale[0] : 1.f) : (gscale ? gscale[0] : 1.f) / stats[1];
+  const float sumw = BWD && SEL ? stats[0] : 1.f, tau = BWD && SEL ? stats[1] : 0.f;
   if (BWD && KD) gm = (float)(2.0 * (double)(gmse ? gmse[0] : 1.f) / ((double)P * (double)C));
   for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const int64_t p0 = t * 256;
@@ -141,6 +179,8 @@ __global__ __launch_bounds__(256) void ce_tile_kernel(const act_t* __restrict__ 
     const act_t* src = logits + p0 * C;
     const float* tsrc = KD ? teacher + p0 * C : nullptr;
     const int nel4 = nel >> 2;  // (p0*C is a multiple of 4: vector accesses are aligned)
+    float pl = -1.f;  // (SEL backward: asked for before the tile is staged, needed after it)
+    if (BWD && SEL && tid < np) pl = pixel_loss[p0 + tid];
     for (int i = tid; i < nel4; i += 256) {
       const float4 v = lda4(src + 4 * i);
       if (KD && !BWD) {
@@ -176,7 +216,13 @@ __global__ __launch_bounds__(256) void ce_tile_kernel(const act_t* __restrict__ 
     if (tid < np) {
       float* row = tile + tid * CS;
       const int64_t tg = (int64_t)target[p0 + tid];
-      const bool skip = tg == ignore || tg < 0 || tg >= C;
+      bool skip = tg == ignore || tg < 0 || tg >= C;
+      float gp = g;
+      if (BWD && SEL && !skip) {
+        skip = !sel_kept(pl, tau);
+        gp = (g * (weight ? weight[tg] : 1.f)) / sumw;
+      }
+      if (!BWD && SEL && skip) pixel_loss[p0 + tid] = -1.f;
       if (BWD && skip) {
         for (int c = 0; c < C; ++c) row[c] = 0.f;
       } else if (!skip) {
@@ -190,7 +236,9 @@ __global__ __launch_bounds__(256) void ce_tile_kernel(const act_t* __restrict__ 
         }
         if (BWD) {
           const float inv = 1.f / sum;
-          for (int c = 0; c < C; ++c) row[c] = g * (row[c] * inv - ((int64_t)c == tg ? 1.f : 0.f));
+          for (int c = 0; c < C; ++c) row[c] = gp * (row[c] * inv - ((int64_t)c == tg ? 1.f : 0.f));
+        } else if (SEL) {
+          pixel_loss[p0 + tid] = (m + logf(sum)) - row[tg];
         } else {
           loss += (m + logf(sum)) - row[tg];
           cnt += 1.f;
@@ -231,7 +279,7 @@ __global__ __launch_bounds__(256) void ce_tile_kernel(const act_t* __restrict__ 
       __syncthreads();
     }
   }
-  if (!BWD) {
+  if (!BWD && !SEL) {
     red_l[tid] = loss;
     red_n[tid] = cnt;
     if (KD) red_s[tid] = sq;
@@ -255,22 +303,32 @@ constexpr int kCeTileMaxC = 63;
 
 // dlogits[p][c] = gscale[0] * (softmax(p)[c] - [c == target]) / nvalid   (0 for ignored pixels)
 // KD (nasseg_ce_mse_bwd): + gmse[0] * 2 (x - teacher) / (P*C) on every element, ignored pixels included.
-template <typename TL, bool KD = false>
+// SEL (nasseg_ce_sel_bwd): as in ce_tile_kernel.
+template <typename TL, bool KD = false, bool SEL = false>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const act_t* __restrict__ logits,
                                                      const TL* __restrict__ target,
                                                      const float* __restrict__ stats,
                                                      const float* __restrict__ gscale, int64_t P,
                                                      int C, int ignore, act_t* __restrict__ dlogits,
                                                      const float* __restrict__ teacher = nullptr,
-                                                     const float* __restrict__ gmse = nullptr) {
-  const float g = (gscale ? gscale[0] : 1.f) / stats[1];
+                                                     const float* __restrict__ gmse = nullptr,
+                                                     const float* __restrict__ weight = nullptr,
+                                                     const float* __restrict__ pixel_loss = nullptr) {
+  const float g = SEL ? (gscale ? gscale[0] : 1.f) : (gscale ? gscale[0] : 1.f) / stats[1];
+  const float sumw = SEL ? stats[0] : 1.f, tau = SEL ? stats[1] : 0.f;
   const float gm = KD ? (float)(2.0 * (double)(gmse ? gmse[0] : 1.f) / ((double)P * (double)C)) : 0.f;
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
     const int64_t t = (int64_t)target[p];
     const act_t* lp = logits + p * C;
     act_t* dp = dlogits + p * C;
     const float* tp = KD ? teacher + p * C : nullptr;
-    if (t == ignore || t < 0 || t >= C) {
+    bool skip = t == ignore || t < 0 || t >= C;
+    float gp = g;
+    if (SEL && !skip) {
+      skip = !sel_kept(pixel_loss[p], tau);
+      gp = (g * (weight ? weight[t] : 1.f)) / sumw;
+    }
+    if (skip) {
       for (int c = 0; c < C; ++c) sta1(dp + c, KD ? gm * (lda1(lp + c) - tp[c]) : 0.f);
       continue;
     }
@@ -281,9 +339,231 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const act_t* __restrict__ l
     const float inv = 1.f / s;
     for (int c = 0; c < C; ++c) {
       float sm = expf(lda1(lp + c) - m) * inv;
-      float d = g * (sm - ((int64_t)c == t ? 1.f : 0.f));
+      float d = gp * (sm - ((int64_t)c == t ? 1.f : 0.f));
       if (KD) d = fmaf(gm, lda1(lp + c) - tp[c], d);
       sta1(dp + c, d);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Hard-example selection (nasseg_ohem_threshold, nasseg_ce_sel_fwd): the exact k-th largest of the per-pixel
+// losses that take part (entries >= 0), by a radix select on their bit patterns - for non-negative floats the
+// unsigned order of the patterns is the order of the values.  Three digits of 11 + 11 + 10 bits, most significant
+// first; per digit one histogram pass over the array (the values that match the digits found so far; LDS
+// histogram per workgroup, flushed with INTEGER atomics - sums of integers do not depend on arrival order) and
+// one single-workgroup scan that walks the bins from the top until k is reached.  k itself is computed on the
+// device from the number of entries that take part (the total of the first histogram).  No host synchronisation,
+// no allocation, no float atomics.
+// Workspace (4-byte words): hist[3][2048] | SelState.
+// ---------------------------------------------------------------------------
+struct SelState {
+  int64_t krem;     // rank still to find among the entries that match `prefix`
+  uint32_t prefix;  // the digits found so far, right-aligned
+  uint32_t pad;
+};
+constexpr int kSelWsWords = kSelHistWords + (int)(sizeof(SelState) / 4);
+
+__global__ __launch_bounds__(256) void sel_zero_kernel(uint32_t* __restrict__ hist) { sel_clear(hist); }
+
+template <int PASS>
+__global__ __launch_bounds__(256) void sel_hist_kernel(const float* __restrict__ v, int64_t P,
+                                                       const SelState* __restrict__ st,
+                                                       uint32_t* __restrict__ hist) {
+  __shared__ uint32_t bins[kSelBins];
+  constexpr int NB = PASS == 2 ? 1024 : 2048;
+  for (int i = threadIdx.x; i < NB; i += 256) bins[i] = 0u;
+  __syncthreads();
+  const uint32_t prefix = PASS ? st->prefix : 0u;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
+    const float x = v[p];
+    if (x < 0.f) continue;
+    const uint32_t key = __float_as_uint(x) & 0x7fffffffu;  // (-0 takes part as +0)
+    if (PASS == 0) {
+      atomicAdd(&bins[key >> 21], 1u);
+    } else if (PASS == 1) {
+      if ((key >> 21) == prefix) atomicAdd(&bins[(key >> 10) & 0x7ffu], 1u);
+    } else {
+      if ((key >> 10) == prefix) atomicAdd(&bins[key & 0x3ffu], 1u);
+    }
+  }
+  __syncthreads();
+  uint32_t* out = hist + PASS * kSelBins;
+  for (int i = threadIdx.x; i < NB; i += 256)
+    if (bins[i]) atomicAdd(&out[i], bins[i]);
+}
+
+// One workgroup of 256 threads, 8 (4 in the last pass) consecutive bins each.  PASS 0 also computes
+// k = min(n, max(min_kept, ceil(keep_fraction * n))) from n = the histogram's total; PASS 2 ends the selection:
+// tau = min(t_loss, L_(k)), counts = {k, n, 0} (n == 0: L_(k) = +inf).
+template <int PASS>
+__global__ __launch_bounds__(256) void sel_scan_kernel(const uint32_t* __restrict__ hist, SelState* __restrict__ st,
+                                                       float t_loss, int64_t min_kept, double keep_fraction,
+                                                       float* __restrict__ tau, int64_t* __restrict__ counts) {
+  constexpr int PER = PASS == 2 ? 4 : 8;
+  __shared__ int64_t sums[256];
+  __shared__ int64_t s_krem;
+  const uint32_t* h = hist + PASS * kSelBins;
+  const int tid = threadIdx.x;
+  uint32_t c[PER];
+  int64_t mine = 0;
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    c[i] = h[tid * PER + i];
+    mine += (int64_t)c[i];
+  }
+  sums[tid] = mine;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {  // suffix sums: sums[t] = the entries in the bins of threads t .. 255
+    const int64_t add = tid + off < 256 ? sums[tid + off] : 0;
+    __syncthreads();
+    sums[tid] += add;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    if (PASS == 0) {
+      const int64_t n = sums[0];
+      int64_t k = (int64_t)ceil(keep_fraction * (double)n);
+      if (k < min_kept) k = min_kept;
+      if (k > n) k = n;
+      s_krem = k;
+      counts[0] = k;
+      counts[1] = n;
+      counts[2] = 0;
+    } else {
+      s_krem = st->krem;
+    }
+  }
+  __syncthreads();
+  const int64_t krem = s_krem;
+  if (PASS == 0 && krem == 0) {  // nothing takes part
+    if (tid == 0) {
+      st->krem = 0;
+      st->prefix = 0u;
+    }
+    return;
+  }
+  int64_t above = sums[tid] - mine;  // entries in the bins of the threads after this one
+  if (above < krem && krem <= above + mine) {  // exactly one thread: the k-th largest lies in its bins
+#pragma unroll
+    for (int i = PER - 1; i >= 0; --i) {
+      if (krem <= above + (int64_t)c[i]) {
+        const uint32_t digit = (uint32_t)(tid * PER + i);
+        const uint32_t prefix = PASS == 0 ? digit : ((st->prefix << (PASS == 1 ? 11 : 10)) | digit);
+        st->prefix = prefix;
+        st->krem = krem - above;
+        break;
+      }
+      above += (int64_t)c[i];
+    }
+  }
+  if (PASS == 2) {
+    __syncthreads();
+    if (tid == 0) {
+      const bool none = counts[1] == 0;
+      const float lk = none ? __builtin_inff() : __uint_as_float(st->prefix);
+      // min(t_loss, L_(k)): L_(k) >= 0, so a t_loss that is not positive is the smaller one
+      const bool t_smaller = !(t_loss > 0.f) || __float_as_uint(t_loss) < __float_as_uint(lk);
+      tau[0] = t_smaller ? t_loss : lk;
+    }
+  }
+}
+
+// counts[2] += entries kept at tau (integer atomics; sel_scan_kernel<2> left 0 there)
+__global__ __launch_bounds__(256) void sel_count_kernel(const float* __restrict__ v, int64_t P,
+                                                        const float* __restrict__ tau,
+                                                        int64_t* __restrict__ counts) {
+  __shared__ unsigned int red[256];
+  const float t = tau[0];
+  unsigned int n = 0;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256)
+    n += sel_kept(v[p], t) ? 1u : 0u;
+  red[threadIdx.x] = n;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && red[0])
+    atomicAdd(reinterpret_cast<unsigned long long*>(counts + 2), (unsigned long long)red[0]);
+}
+
+// Sum pass of nasseg_ce_sel_fwd over pixel_loss + labels: partial[b] = {sum w l, sum w, count} over the kept pixels
+// of workgroup b, with the pixel -> (workgroup, thread) mapping, the accumulation order and the tree of
+// ce_fwd_kernel: with unit weights and everything kept, the very sums of nasseg_ce_fwd.  tau == nullptr: no
+// selection, every valid pixel is kept.
+template <typename TL>
+__global__ __launch_bounds__(256) void ce_sel_sum_kernel(const float* __restrict__ pixel_loss,
+                                                         const TL* __restrict__ target,
+                                                         const float* __restrict__ weight, int64_t P,
+                                                         const float* __restrict__ tau,
+                                                         float* __restrict__ partial) {
+  __shared__ float red_l[256];
+  __shared__ float red_w[256];
+  __shared__ float red_n[256];
+  const float t = tau ? tau[0] : 0.f;
+  float loss = 0.f, sw = 0.f, cnt = 0.f;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
+    const float l = pixel_loss[p];
+    if (!sel_kept(l, t)) continue;
+    const float w = weight ? weight[(int64_t)target[p]] : 1.f;  // (l >= 0: the label is in [0, C))
+    loss += w * l;
+    sw += w;
+    cnt += 1.f;
+  }
+  red_l[threadIdx.x] = loss;
+  red_w[threadIdx.x] = sw;
+  red_n[threadIdx.x] = cnt;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      red_l[threadIdx.x] += red_l[threadIdx.x + s];
+      red_w[threadIdx.x] += red_w[threadIdx.x + s];
+      red_n[threadIdx.x] += red_n[threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x * 3] = red_l[0];
+    partial[blockIdx.x * 3 + 1] = red_w[0];
+    partial[blockIdx.x * 3 + 2] = red_n[0];
+  }
+}
+
+// loss = sum w l / sum w, stats = {sum w, tau}, counts[2] = kept pixels (selected: counts[0..1] and stats[1] are
+// the selection's; else k = n = kept and tau = -inf); the order of ce_finalize_kernel.
+__global__ __launch_bounds__(256) void ce_sel_finalize_kernel(const float* __restrict__ partial, int nblk,
+                                                              int selected, float* __restrict__ loss,
+                                                              float* __restrict__ stats,
+                                                              int64_t* __restrict__ counts) {
+  __shared__ double red_l[256];
+  __shared__ double red_w[256];
+  __shared__ double red_n[256];
+  double l = 0.0, w = 0.0, n = 0.0;
+  for (int b = threadIdx.x; b < nblk; b += 256) {
+    l += (double)partial[b * 3];
+    w += (double)partial[b * 3 + 1];
+    n += (double)partial[b * 3 + 2];
+  }
+  red_l[threadIdx.x] = l;
+  red_w[threadIdx.x] = w;
+  red_n[threadIdx.x] = n;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      red_l[threadIdx.x] += red_l[threadIdx.x + s];
+      red_w[threadIdx.x] += red_w[threadIdx.x + s];
+      red_n[threadIdx.x] += red_n[threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    loss[0] = (float)(red_l[0] / red_w[0]);
+    stats[0] = (float)red_w[0];
+    counts[2] = (int64_t)red_n[0];
+    if (!selected) {
+      stats[1] = -__builtin_inff();
+      counts[0] = counts[1] = (int64_t)red_n[0];
     }
   }
 }
@@ -371,6 +651,32 @@ inline int ce_grid(int64_t P) {
   return (int)b;
 }
 
+// the selection's launches: [zero the histograms, unless an earlier launch did,] 3 x (histogram, scan); tau[0] and
+// counts[0..2] = {k, n, 0} after
+int sel_launch(const float* v, int64_t P, float t_loss, int64_t min_kept, double keep_fraction, float* tau,
+               int64_t* counts, void* ws, bool zeroed, hipStream_t s) {
+  uint32_t* hist = (uint32_t*)ws;
+  SelState* st = (SelState*)(hist + kSelHistWords);
+  const int grid = ce_grid(P);
+  if (!zeroed) {
+    hipLaunchKernelGGL(sel_zero_kernel, dim3(6), dim3(256), 0, s, hist);
+    NASSEG_LAUNCH_CHECK("sel_zero");
+  }
+  hipLaunchKernelGGL(sel_hist_kernel<0>, dim3(grid), dim3(256), 0, s, v, P, st, hist);
+  hipLaunchKernelGGL(sel_scan_kernel<0>, dim3(1), dim3(256), 0, s, hist, st, t_loss, min_kept, keep_fraction, tau,
+                     counts);
+  NASSEG_LAUNCH_CHECK("sel_pass0");
+  hipLaunchKernelGGL(sel_hist_kernel<1>, dim3(grid), dim3(256), 0, s, v, P, st, hist);
+  hipLaunchKernelGGL(sel_scan_kernel<1>, dim3(1), dim3(256), 0, s, hist, st, t_loss, min_kept, keep_fraction, tau,
+                     counts);
+  NASSEG_LAUNCH_CHECK("sel_pass1");
+  hipLaunchKernelGGL(sel_hist_kernel<2>, dim3(grid), dim3(256), 0, s, v, P, st, hist);
+  hipLaunchKernelGGL(sel_scan_kernel<2>, dim3(1), dim3(256), 0, s, hist, st, t_loss, min_kept, keep_fraction, tau,
+                     counts);
+  NASSEG_LAUNCH_CHECK("sel_pass2");
+  return NASSEG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -378,7 +684,109 @@ extern "C" {
 #if NASSEG_FP32_ONLY
 int64_t nasseg_ce_workspace(void) { return 2 * 1024; }
 int64_t nasseg_ce_mse_workspace(void) { return 3 * 1024; }
+int64_t nasseg_ohem_workspace(void) { return kSelWsWords; }
+int64_t nasseg_ce_sel_workspace(void) { return 3 * 1024 + kSelWsWords; }
+
+// tau = min(t_loss, k-th largest of the entries of pixel_loss that are >= 0), k = min(n, max(min_kept,
+// ceil(keep_fraction * n))) with n = the number of such entries; counts = {k, n, entries >= tau among them}.
+// ws: nasseg_ohem_workspace() 4-byte words.
+int nasseg_ohem_threshold(const float* pixel_loss, int64_t P, float t_loss, int64_t min_kept, double keep_fraction,
+                          float* tau, int64_t* counts, void* ws, void* stream) {
+  NASSEG_REQUIRE(P > 0 && P < ((int64_t)1 << 32), "ohem_threshold: bad size");
+  NASSEG_REQUIRE(min_kept >= 1 && keep_fraction >= 0.0 && keep_fraction <= 1.0,
+                 "ohem_threshold: min_kept >= 1 and 0 <= keep_fraction <= 1 expected");
+  NASSEG_REQUIRE(pixel_loss && tau && counts && ws, "ohem_threshold: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = sel_launch(pixel_loss, P, t_loss, min_kept, keep_fraction, tau, counts, ws, false, s);
+  if (rc != NASSEG_OK) return rc;
+  hipLaunchKernelGGL(sel_count_kernel, dim3(ce_grid(P)), dim3(256), 0, s, pixel_loss, P, tau, counts);
+  NASSEG_LAUNCH_CHECK("sel_count");
+  return NASSEG_OK;
+}
 #endif
+
+// Class-weighted cross-entropy with hard-example selection (include/nasseg.h).  One pass over the logits writes
+// pixel_loss; the selection and the sum pass read pixel_loss (and the labels) only.
+// ws: nasseg_ce_sel_workspace() floats = [1024][3] partials | the selection's words.
+int NASSEG_FN(ce_sel_fwd)(const act_t* logits, const void* target, int elem_size, const float* weight, int64_t P,
+                          int C, int ignore, int select, float t_loss, int64_t min_kept, double keep_fraction,
+                          float* loss, float* stats, int64_t* counts, float* pixel_loss, float* ws, void* stream) {
+  NASSEG_REQUIRE(P > 0 && P < ((int64_t)1 << 32) && C > 0, "ce_sel_fwd: bad shape");
+  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_sel_fwd: elem_size %d not supported", elem_size);
+  NASSEG_REQUIRE(logits && target && loss && stats && counts && pixel_loss && ws, "ce_sel_fwd: null pointer");
+  NASSEG_REQUIRE(!select || (min_kept >= 1 && keep_fraction >= 0.0 && keep_fraction <= 1.0),
+                 "ce_sel_fwd: selection needs min_kept >= 1 and 0 <= keep_fraction <= 1");
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = ce_grid(P);
+  const size_t lds = (size_t)256 * (C | 1) * sizeof(float);
+  const bool tiled = C <= kCeTileMaxC && ((uintptr_t)logits & 15) == 0;
+  uint32_t* hist = select ? (uint32_t*)(ws + 3 * 1024) : nullptr;  // (cleared by the forward kernel on its way)
+  if (tiled && elem_size == 8)
+    hipLaunchKernelGGL((ce_tile_kernel<int64_t, false, false, true>), dim3(grid), dim3(256), lds, s, logits,
+                       (const int64_t*)target, P, C, ignore, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       nullptr, nullptr, pixel_loss, hist);
+  else if (tiled)
+    hipLaunchKernelGGL((ce_tile_kernel<uint8_t, false, false, true>), dim3(grid), dim3(256), lds, s, logits,
+                       (const uint8_t*)target, P, C, ignore, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       nullptr, nullptr, pixel_loss, hist);
+  else if (elem_size == 8)
+    hipLaunchKernelGGL((ce_fwd_kernel<int64_t, false, true>), dim3(grid), dim3(256), 0, s, logits,
+                       (const int64_t*)target, P, C, ignore, nullptr, nullptr, nullptr, pixel_loss, hist);
+  else
+    hipLaunchKernelGGL((ce_fwd_kernel<uint8_t, false, true>), dim3(grid), dim3(256), 0, s, logits,
+                       (const uint8_t*)target, P, C, ignore, nullptr, nullptr, nullptr, pixel_loss, hist);
+  NASSEG_LAUNCH_CHECK("ce_sel_fwd");
+  if (select) {
+    const int rc = sel_launch(pixel_loss, P, t_loss, min_kept, keep_fraction, stats + 1, counts, ws + 3 * 1024, true, s);
+    if (rc != NASSEG_OK) return rc;
+  }
+  const float* tau = select ? stats + 1 : nullptr;
+  if (elem_size == 8)
+    hipLaunchKernelGGL(ce_sel_sum_kernel<int64_t>, dim3(grid), dim3(256), 0, s, pixel_loss, (const int64_t*)target,
+                       weight, P, tau, ws);
+  else
+    hipLaunchKernelGGL(ce_sel_sum_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, pixel_loss, (const uint8_t*)target,
+                       weight, P, tau, ws);
+  NASSEG_LAUNCH_CHECK("ce_sel_sum");
+  hipLaunchKernelGGL(ce_sel_finalize_kernel, dim3(1), dim3(256), 0, s, ws, grid, select, loss, stats, counts);
+  NASSEG_LAUNCH_CHECK("ce_sel_finalize");
+  return NASSEG_OK;
+}
+
+// dlogits = gscale * weight[t] * (softmax - onehot) / stats[0] for the pixels kept at stats[1] (pixel_loss, stats:
+// from nasseg_ce_sel_fwd), exact zeros elsewhere; written once.
+int NASSEG_FN(ce_sel_bwd)(const act_t* logits, const void* target, int elem_size, const float* weight,
+                          const float* pixel_loss, const float* stats, const float* gscale, int64_t P, int C,
+                          int ignore, act_t* dlogits, void* stream) {
+  NASSEG_REQUIRE(P > 0 && C > 0, "ce_sel_bwd: bad shape");
+  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_sel_bwd: elem_size %d not supported", elem_size);
+  NASSEG_REQUIRE(logits && target && pixel_loss && stats && dlogits, "ce_sel_bwd: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = ce_grid(P) * 2;
+  const size_t lds = (size_t)256 * (C | 1) * sizeof(float);
+  int64_t tiles = (P + 255) / 256;
+  if (tiles > 4096) tiles = 4096;
+  const bool tiled = C <= kCeTileMaxC && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0;
+  float* pl = const_cast<float*>(pixel_loss);  // (the kernel's one parameter for both directions; backward reads)
+  if (tiled && elem_size == 8)
+    hipLaunchKernelGGL((ce_tile_kernel<int64_t, true, false, true>), dim3((unsigned)tiles), dim3(256), lds, s,
+                       logits, (const int64_t*)target, P, C, ignore, nullptr, stats, gscale, dlogits, nullptr,
+                       nullptr, nullptr, weight, pl);
+  else if (tiled)
+    hipLaunchKernelGGL((ce_tile_kernel<uint8_t, true, false, true>), dim3((unsigned)tiles), dim3(256), lds, s,
+                       logits, (const uint8_t*)target, P, C, ignore, nullptr, stats, gscale, dlogits, nullptr,
+                       nullptr, nullptr, weight, pl);
+  else if (elem_size == 8)
+    hipLaunchKernelGGL((ce_bwd_kernel<int64_t, false, true>), dim3(grid), dim3(256), 0, s, logits,
+                       (const int64_t*)target, stats, gscale, P, C, ignore, dlogits, nullptr, nullptr, weight,
+                       pixel_loss);
+  else
+    hipLaunchKernelGGL((ce_bwd_kernel<uint8_t, false, true>), dim3(grid), dim3(256), 0, s, logits,
+                       (const uint8_t*)target, stats, gscale, P, C, ignore, dlogits, nullptr, nullptr, weight,
+                       pixel_loss);
+  NASSEG_LAUNCH_CHECK("ce_sel_bwd");
+  return NASSEG_OK;
+}
 
 // logits [P][C] dense NHWC, target [P] (elem_size 1 = uint8, 8 = int64).
 // out[0] = mean NLL over valid pixels, out[1] = valid count. ws: nasseg_ce_workspace() floats.

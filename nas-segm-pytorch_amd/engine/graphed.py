@@ -343,18 +343,22 @@ class GraphedSegmenterStep(_GraphedStep):
 
     def __init__(self, segmenter, image, target, optim_enc, optim_dec, ignore_index=255,
                  enc_grad_clip=0.0, dec_grad_clip=0.0, aux_weight=-1, capture_optimisers=False,
-                 warmup=2, loss_fn=None, depth_crit=None):
+                 warmup=2, loss_fn=None, depth_crit=None, segm_crit=None):
         """loss_fn(output, target) -> scalar replaces the softmax/NLL (+ aux heads) of the
         segmentation step, e.g. ``F.berhu_loss`` for a depth head; it must be capturable (device
         tensors in, device scalar out, no host synchronisation).
         depth_crit (an ``nn.BerHuLoss``): the depth step of ``train_segmenter`` - ``target`` is the fp32 (B, H, W)
-        depth map at the image's size, the loss is ``task1_depth_loss`` (auxiliary heads included)."""
+        depth map at the image's size, the loss is ``task1_depth_loss`` (auxiliary heads included).
+        segm_crit (an ``nn.SegmCrossEntropy``): the loss of every head instead of the plain softmax/NLL; its
+        threshold, ``min_kept`` and ``keep_fraction`` are recorded by value - a change needs a new stepper
+        (engine/trainer.py's cache keys on them)."""
         model = inner(segmenter)
         self.optim_enc, self.optim_dec = optim_enc, optim_dec
         self.ignore_index = ignore_index
         self.aux_weight = aux_weight
         self.loss_fn = loss_fn
         self.depth_crit = depth_crit
+        self.segm_crit = segm_crit
         self._trained = [model.encoder, model.decoder]
         self.groups = [
             (list(model.encoder.parameters()), enc_grad_clip, optim_enc),
@@ -368,7 +372,8 @@ class GraphedSegmenterStep(_GraphedStep):
         if self.depth_crit is not None:
             return task1_depth_loss(self.segmenter, self.image, self.target, self.depth_crit, self.aux_weight)
         if self.loss_fn is None:
-            return task1_loss(self.segmenter, self.image, self.target, self.ignore_index, self.aux_weight)
+            return task1_loss(self.segmenter, self.image, self.target, self.ignore_index, self.aux_weight,
+                              self.segm_crit)
         output = self.segmenter(self.image)
         return self.loss_fn(output[0] if isinstance(output, tuple) else output, self.target)
 
@@ -395,13 +400,16 @@ class GraphedTask0Step(_GraphedStep):
     """
 
     def __init__(self, Xy_train, segmenter, optim_dec, batch_size, ignore_index=255, dec_grad_clip=0.0,
-                 aux_weight=0, capture_optimisers=False, warmup=2, kd_coeff=None):
+                 aux_weight=0, capture_optimisers=False, warmup=2, kd_coeff=None, segm_crit=None):
+        if kd_coeff is not None and segm_crit is not None:
+            raise ValueError("GraphedTask0Step: the fused distillation term exists for the plain softmax/NLL only")
         model = inner(segmenter)
         self.cache = Xy_train
         self.optim_dec = optim_dec
         self.ignore_index = ignore_index
         self.aux_weight = aux_weight
         self.kd_coeff = kd_coeff
+        self.segm_crit = segm_crit  # (an nn.SegmCrossEntropy; not together with kd_coeff: no fused term for it)
         self._trained = [model.decoder]
         self.groups = [(list(model.decoder.parameters()), dec_grad_clip, optim_dec)]
         self.decoder = model.decoder
@@ -409,7 +417,8 @@ class GraphedTask0Step(_GraphedStep):
         self._init_common(segmenter, capture_optimisers, (optim_dec,), warmup)
 
     def _forward_loss(self):
-        return task0_loss(self.cache, self.index, self.decoder, self.ignore_index, self.aux_weight, self.kd_coeff)
+        return task0_loss(self.cache, self.index, self.decoder, self.ignore_index, self.aux_weight, self.kd_coeff,
+                          segm_crit=self.segm_crit)
 
     def step(self, indices):
         idx = torch.as_tensor(indices, dtype=torch.int64)

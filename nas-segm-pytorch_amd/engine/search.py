@@ -17,7 +17,7 @@ from .graphed import GraphedSegmenterStep
 from ..nn.losses import BerHuLoss
 from .inference import validate, validate_depth
 from .segmenter import RankParallel, Segmenter
-from .trainer import train_segmenter
+from .trainer import _ignore_index, _segm_crit, train_segmenter
 
 
 class _Crit(object):
@@ -47,12 +47,14 @@ def build_candidate(config, ctrl_version="wacv", num_classes=19, agg_size=48, au
 def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", num_classes=19,
                        agg_size=48, aux_cell=True, repeats=1, epochs=1, aux_weight=0.15,
                        omit_classes=(0,), device="cuda", stats=None, graphed=False, task="segm",
-                       min_depth=1e-3, max_depth=10.0):
+                       min_depth=1e-3, max_depth=10.0, segm_crit=None):
     """Train the candidate on ``train_batches`` (lists of {"image", "mask"}) for ``epochs``
     passes and return its validation reward; failures score 0 like in the reference.
     task="depth": the masks are fp32 depth maps at the image's size (holes: 0 / NaN / inf), the decoder has one
     output channel, the loss is BerHuLoss(valid_min=0) and the reward comes from ``validate_depth``
-    (``min_depth`` / ``max_depth``: its valid range)."""
+    (``min_depth`` / ``max_depth``: its valid range).
+    ``segm_crit`` (task="segm"): the training criterion, e.g. an nn.SegmCrossEntropy with class weights or
+    hard-example mining; None: LogSoftmax + NLL with ignore index 255."""
     if _task(task) == "depth":
         return _evaluate_depth_candidate(config, train_batches, val_batches, ctrl_version, agg_size, aux_cell,
                                          repeats, epochs, aux_weight, device, stats, graphed, min_depth, max_depth)
@@ -65,6 +67,7 @@ def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", 
     optim_enc = torch.optim.SGD(model.encoder.parameters(), lr=1e-3, momentum=0.9, weight_decay=1e-5)
     optim_dec = torch.optim.Adam(model.decoder.parameters(), lr=3e-3, weight_decay=1e-5)
     aux = aux_weight if ctrl_version == "cvpr" else -1
+    segm_crit = _Crit() if segm_crit is None else segm_crit
     if graphed:
         # one capture per candidate, one replay per step (engine/graphed.py): same results, no host
         # launch cost - what bounds a candidate at 321x321 ... 713x713
@@ -73,7 +76,8 @@ def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", 
             image = first["image"].to(device=device, dtype=torch.float32).contiguous(
                 memory_format=torch.channels_last)
             stepper = GraphedSegmenterStep(segmenter, image, first["mask"].to(device).long(), optim_enc,
-                                           optim_dec, 255, 3.0, 3.0, aux)
+                                           optim_dec, _ignore_index(segm_crit), 3.0, 3.0, aux,
+                                           segm_crit=_segm_crit(segm_crit, image.device))
             for epoch in range(epochs):
                 for sample in train_batches:
                     stepper.step(sample["image"].to(device=device, dtype=torch.float32).contiguous(
@@ -82,7 +86,7 @@ def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", 
             return 0.0
     else:
         for epoch in range(epochs):
-            ret = train_segmenter(segmenter, train_batches, optim_enc, optim_dec, epoch, _Crit(), False,
+            ret = train_segmenter(segmenter, train_batches, optim_enc, optim_dec, epoch, segm_crit, False,
                                   3.0, 3.0, False, print_every=10 ** 9, aux_weight=aux)
             if ret == 0:  # try_except: RuntimeError inside the step
                 return 0.0

@@ -13,6 +13,7 @@ import contextlib
 import logging
 import os
 import time
+import weakref
 
 import numpy as np
 import torch
@@ -20,7 +21,7 @@ from torch import nn
 
 from .. import functional as F
 from ..helpers.utils import AverageMeter, try_except
-from ..nn.losses import BerHuLoss
+from ..nn.losses import BerHuLoss, SegmCrossEntropy
 from ..nn.modules import TREE_VERSION
 from . import graphed
 from .trainer_common import cache_feature_keys, check_cache_rows, task0_loss, task1_depth_loss, task1_loss
@@ -78,6 +79,32 @@ def _depth_crit(segm_crit):
     """the criterion itself when it selects the depth step (an nn.BerHuLoss: fp32 full-size targets, masked berHu),
     else None: softmax/NLL on class labels, as ever"""
     return segm_crit if isinstance(segm_crit, BerHuLoss) else None
+
+
+_MAPPED_CRITS = weakref.WeakKeyDictionary()  # nn.NLLLoss with class weights -> its SegmCrossEntropy
+
+
+def _segm_crit(segm_crit, device=None):
+    """the criterion that replaces the plain softmax/NLL of every head, else None (F.log_softmax_nll with the
+    criterion's ``ignore_index``, as ever).  An nn.SegmCrossEntropy with class weights or hard-example selection is
+    that criterion itself; an nn.NLLLoss (nn.NLLLoss2d where torch has it) with ``weight`` and mean reduction - the
+    one-line change to src/main_search.py:435 - is mapped to the equivalent SegmCrossEntropy, once per criterion
+    and weight tensor.  ``device``: the weights are made fp32 there now (not inside a step being recorded)."""
+    crit = None
+    if isinstance(segm_crit, SegmCrossEntropy):
+        if segm_crit.weight is not None or segm_crit.selects:
+            crit = segm_crit
+    elif (isinstance(segm_crit, nn.NLLLoss) and segm_crit.weight is not None
+          and getattr(segm_crit, "reduction", "mean") == "mean"):
+        key = (id(segm_crit.weight), int(segm_crit.ignore_index))
+        hit = _MAPPED_CRITS.get(segm_crit)
+        if hit is None or hit[0] != key:
+            hit = (key, SegmCrossEntropy(weight=segm_crit.weight.detach(), ignore_index=segm_crit.ignore_index))
+            _MAPPED_CRITS[segm_crit] = hit
+        crit = hit[1]
+    if crit is not None and device is not None:
+        crit.prepare(device)
+    return crit
 
 
 def _depth_target(mask, device):
@@ -259,20 +286,26 @@ def _cached_stepper(owner, slot, base_key, shape_key, build):
     return stepper
 
 
-def _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_clip, aux_weight, kd_coeff=None):
-    """kd_coeff: None - no distillation term; else the coefficient of the fused nn.MSELoss term (``native_kd``)"""
+def _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_clip, aux_weight, kd_coeff=None,
+                   segm_crit=None):
+    """kd_coeff: None - no distillation term; else the coefficient of the fused nn.MSELoss term (``native_kd``);
+    segm_crit: ``_segm_crit``'s"""
     model = _inner(segmenter)
     base = (TREE_VERSION[0], id(optim_dec), ignore, dec_grad_clip, aux_weight, _bn_modes(model.decoder),
             _trainable_signature(list(model.decoder.parameters()), (optim_dec,)))
     if kd_coeff is not None:
         base = base + (("kd_mse", float(kd_coeff)),)
+    extra = {}
+    if segm_crit is not None:  # (threshold, min_kept and keep_fraction are kernel arguments: recorded by value)
+        base = base + (segm_crit.config(),)
+        extra["segm_crit"] = segm_crit
     shape = (batch_size, tuple((k, v.data_ptr(), tuple(v.shape)) for k, v in Xy_train.items() if k != "out_size"))
     return _cached_stepper(model, "_nasseg_task0_stepper", base, shape, lambda: graphed.GraphedTask0Step(
-        Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_clip, aux_weight, kd_coeff=kd_coeff))
+        Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_clip, aux_weight, kd_coeff=kd_coeff, **extra))
 
 
 def _segmenter_stepper(segmenter, image, target, optim_enc, optim_dec, ignore, enc_grad_clip, dec_grad_clip,
-                       aux_weight, depth_crit=None):
+                       aux_weight, depth_crit=None, segm_crit=None):
     model = _inner(segmenter)
     base = (TREE_VERSION[0], id(optim_enc), id(optim_dec), ignore, enc_grad_clip, dec_grad_clip, aux_weight,
             _bn_modes(model), _trainable_signature(list(model.parameters()), (optim_enc, optim_dec)))
@@ -280,6 +313,9 @@ def _segmenter_stepper(segmenter, image, target, optim_enc, optim_dec, ignore, e
     if depth_crit is not None:  # (the loss kind, and what the recorded launches carry by value)
         base = base + (("berhu", id(depth_crit), depth_crit.valid_min, depth_crit.valid_max),)
         extra["depth_crit"] = depth_crit
+    if segm_crit is not None:
+        base = base + (segm_crit.config(),)
+        extra["segm_crit"] = segm_crit
     shape = (tuple(image.shape), image.dtype, tuple(target.shape), target.dtype)
     return _cached_stepper(model, "_nasseg_task1_stepper", base, shape, lambda: graphed.GraphedSegmenterStep(
         segmenter, image, target, optim_enc, optim_dec, ignore, enc_grad_clip, dec_grad_clip, aux_weight, **extra))
@@ -347,7 +383,7 @@ def populate_task0(segmenter, train_loader, kd_net, n_train, do_kd=False):
 
 
 def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255, dec_grad_clip=0.0, aux_weight=0,
-                    freeze_bn=False, do_kd=False, kd_coeff=0.0, kd_crit=None):
+                    freeze_bn=False, do_kd=False, kd_coeff=0.0, kd_crit=None, segm_crit=None):
     """step(batch_idx) -> device loss: one decoder-only training step on the cache rows
     ``batch_idx`` (a host array of ``batch_size`` indices).  Small batches are launch-bound, so the
     step is replayed from a hipGraph where that wins (engine/graphed.py: auto_graph; the stepper
@@ -356,7 +392,9 @@ def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255
     ``nn.MSELoss()`` (``native_kd``), or data parallel - it is launched from the host: gather the
     batch (one kernel per cache entry), decoder forward, bilinear resize to ``out_size``,
     softmax/NLL [+ kd_coeff * MSE to the cached teacher logits, one fused kernel] (+ aux heads),
-    backward, [all-reduce], clip, optimiser."""
+    backward, [all-reduce], clip, optimiser.
+    ``segm_crit`` (``_segm_crit``'s: class weights / hard-example selection) is the loss of every head; with
+    distillation as well the step is launched from the host and ``kd_crit`` is called as written."""
     decoder = _inner(segmenter).decoder
     feat = Xy_train[cache_feature_keys(Xy_train)[0]]
     out_size = tuple(Xy_train["out_size"])
@@ -364,10 +402,11 @@ def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255
     dec_params = list(decoder.parameters())
     pack_memo = F.PackMemo()
     n_pixels = batch_size * int(feat.shape[2]) * int(feat.shape[3]) * 16
-    fused_kd = do_kd and native_kd(kd_crit, Xy_train.get("kd_y"), out_size)
+    fused_kd = do_kd and segm_crit is None and native_kd(kd_crit, Xy_train.get("kd_y"), out_size)
+    extra = {} if segm_crit is None else {"segm_crit": segm_crit}
     if (not do_kd or fused_kd) and _replays(segmenter, device, n_pixels):
         stepper = _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore_index, dec_grad_clip,
-                                 aux_weight, kd_coeff if fused_kd else None)
+                                 aux_weight, kd_coeff if fused_kd else None, **extra)
         if stepper is not None:
             return stepper.step
 
@@ -378,7 +417,7 @@ def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255
             idx = idx.to(device, non_blocking=True)
             with F.packed_once(pack_memo):  # (one weight re-pack launch per step)
                 loss = task0_loss(Xy_train, idx, decoder, ignore_index, aux_weight, kd_coeff if do_kd else None,
-                                  kd_crit, fused_kd)
+                                  kd_crit, fused_kd, **extra)
                 _zero_grads(segmenter, (optim_dec,))
                 with F.deferred_wgrad(params=dec_params, second_stream=False):  # (crops of the feature cache: launch-bound)
                     loss.backward()
@@ -413,7 +452,8 @@ def train_task0(Xy_train, segmenter, optim_dec, epoch, segm_crit, kd_crit, batch
         _freeze_bn(decoder)
     np.random.shuffle(indices)
     step = make_task0_step(Xy_train, segmenter, optim_dec, batch_size, _ignore_index(segm_crit), dec_grad_clip,
-                           aux_weight, freeze_bn, do_kd, kd_coeff, kd_crit)
+                           aux_weight, freeze_bn, do_kd, kd_coeff, kd_crit,
+                           _segm_crit(segm_crit, Xy_train["y"].device))
     for i in range(n_passes):
         start = time.time()
         syncs = _syncs(segmenter)
@@ -432,7 +472,7 @@ def train_task0(Xy_train, segmenter, optim_dec, epoch, segm_crit, kd_crit, batch
 
 
 def segmenter_step(segmenter, image, target, optim_enc, optim_dec, ignore_index=255,
-                   enc_grad_clip=0.0, dec_grad_clip=0.0, aux_weight=-1, depth_crit=None):
+                   enc_grad_clip=0.0, dec_grad_clip=0.0, aux_weight=-1, depth_crit=None, segm_crit=None):
     """One end-to-end training step on device tensors; returns the (device) loss.
 
     forward -> nearest-resize labels to the logits' size -> fused log-softmax/NLL
@@ -440,7 +480,10 @@ def segmenter_step(segmenter, image, target, optim_enc, optim_dec, ignore_index=
     -> per-sub-module norm clipping -> optimiser steps.
     ``depth_crit`` (an nn.BerHuLoss): the depth step instead - ``target`` is the fp32 (B, H, W) depth map and the
     loss is the masked berHu of every head against it (trainer_common.task1_depth_loss).
+    ``segm_crit``: any segmentation criterion - one with class weights or hard-example selection (``_segm_crit``)
+    is the loss of every head, anything else leaves the plain softmax/NLL with ``ignore_index``.
     """
+    segm_crit = _segm_crit(segm_crit, image.device)
     model = _inner(segmenter)
     cached = getattr(model, "_nasseg_step_params", None)
     if cached is None or cached[0] != TREE_VERSION[0]:
@@ -457,7 +500,7 @@ def segmenter_step(segmenter, image, target, optim_enc, optim_dec, ignore_index=
             if depth_crit is not None:
                 loss = task1_depth_loss(segmenter, image, target, depth_crit, aux_weight)
             else:
-                loss = task1_loss(segmenter, image, target, ignore_index, aux_weight)
+                loss = task1_loss(segmenter, image, target, ignore_index, aux_weight, segm_crit)
             _zero_grads(segmenter, (optim_enc, optim_dec))
             # gradients were just cleared: the second stages of all weight-gradient reductions run
             # batched when backward is through
@@ -493,6 +536,9 @@ def train_segmenter(segmenter, train_loader, optim_enc, optim_dec, epoch, segm_c
     depth_crit = _depth_crit(segm_crit)
     extra = {} if depth_crit is None else {"depth_crit": depth_crit}  # (any other criterion: exactly as ever)
     device = _model_device(_inner(segmenter))
+    weighted = None if depth_crit is not None else _segm_crit(segm_crit, device)
+    if weighted is not None:  # (class weights / hard-example selection: the loss of every head)
+        extra = {"segm_crit": weighted}
     # data parallel: the ranks agree on the number of steps (loaders of unequal length would leave
     # the longer ones waiting in an all-reduce), and a rank that fails ANYWHERE in its step - the
     # loader, the copy to the device, the optimiser - tells its peers before it leaves (_tell_peers)

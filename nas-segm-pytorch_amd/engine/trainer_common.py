@@ -37,23 +37,31 @@ def _heads(output):
     return output if isinstance(output, tuple) else (output, [])
 
 
-def segmentation_loss(output, aux_outs, target, ignore_index, aux_weight, loss=None):
+def _head_loss(logits, target, ignore_index, segm_crit):
+    """the loss of one head: F.log_softmax_nll, or ``segm_crit`` (an nn.SegmCrossEntropy with class weights or
+    hard-example selection - every head selects among its own pixels)"""
+    if segm_crit is None:
+        return F.log_softmax_nll(logits, target, ignore_index)
+    return segm_crit(logits, target)
+
+
+def segmentation_loss(output, aux_outs, target, ignore_index, aux_weight, loss=None, segm_crit=None):
     """LogSoftmax + NLL of the main head (``loss``: that term already computed, with the distillation term added)
     + aux_weight * those of the auxiliary heads, each resized to the labels' size, when aux_weight > 0"""
     if loss is None:
-        loss = F.log_softmax_nll(output, target, ignore_index)
+        loss = _head_loss(output, target, ignore_index, segm_crit)
     if aux_weight > 0:
         for aux_out in aux_outs:
             aux_out = F.bilinear_resize(aux_out, target.size()[1:])
-            loss = loss + F.log_softmax_nll(aux_out, target, ignore_index) * aux_weight
+            loss = loss + _head_loss(aux_out, target, ignore_index, segm_crit) * aux_weight
     return loss
 
 
-def task1_loss(segmenter, image, target, ignore_index, aux_weight):
+def task1_loss(segmenter, image, target, ignore_index, aux_weight, segm_crit=None):
     """forward + loss of the end-to-end step: the labels nearest-resized to the logits' size"""
     output, aux_outs = _heads(segmenter(image))
     target = F.nearest_label_resize(target, output.size()[2:])
-    return segmentation_loss(output, aux_outs, target, ignore_index, aux_weight)
+    return segmentation_loss(output, aux_outs, target, ignore_index, aux_weight, segm_crit=segm_crit)
 
 
 def depth_loss(output, aux_outs, target, crit, aux_weight):
@@ -86,24 +94,26 @@ def check_cache_rows(idx, cache, caller):
         raise IndexError("{}: cache row index out of range [0, {})".format(caller, n_rows))
 
 
-def task0_loss(cache, index, decoder, ignore_index, aux_weight, kd_coeff=None, kd_crit=None, fuse_kd=True):
+def task0_loss(cache, index, decoder, ignore_index, aux_weight, kd_coeff=None, kd_crit=None, fuse_kd=True,
+               segm_crit=None):
     """forward + loss of the decoder-only step on the cache rows ``index`` (an int64 device tensor): gather, decoder,
     bilinear resize to ``out_size``, softmax/NLL, distillation term, aux heads.  kd_coeff None: no distillation term.
     ``fuse_kd``: the teacher rows are gathered after the resize and kd_coeff * MSE runs fused with the softmax/NLL
     (F.log_softmax_nll_mse refuses a teacher of another shape) - given a ``kd_crit``, only when the rows have the
-    logits' shape.  Otherwise kd_coeff * kd_crit(output, teacher rows) runs from the host."""
+    logits' shape.  Otherwise kd_coeff * kd_crit(output, teacher rows) runs from the host - always with a
+    ``segm_crit`` (class weights / hard-example selection: there is no fused distillation term for it)."""
     feats = [F.gather_rows(cache[k], index) for k in cache_feature_keys(cache)]
     target = F.gather_rows(cache["y"], index)
     output, aux_outs = _heads(decoder(feats))
     output = F.bilinear_resize(output, cache["out_size"])
     loss = None
     if kd_coeff is not None:
-        kd_y = F.gather_rows(cache["kd_y"], index) if fuse_kd else None
+        kd_y = F.gather_rows(cache["kd_y"], index) if fuse_kd and segm_crit is None else None
         if kd_y is not None and (kd_crit is None or kd_y.shape == output.shape):
             loss, mse = F.log_softmax_nll_mse(output, target, kd_y, ignore_index)
             loss = loss + kd_coeff * mse
         else:
-            loss = F.log_softmax_nll(output, target, ignore_index)
+            loss = _head_loss(output, target, ignore_index, segm_crit)
             kd_y = kd_y if kd_y is not None else F.gather_rows(cache["kd_y"], index)
             loss = loss + kd_coeff * kd_crit(output, kd_y)
-    return segmentation_loss(output, aux_outs, target, ignore_index, aux_weight, loss)
+    return segmentation_loss(output, aux_outs, target, ignore_index, aux_weight, loss, segm_crit)

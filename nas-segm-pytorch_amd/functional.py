@@ -12,6 +12,7 @@ import ctypes
 import os
 import weakref
 
+import numpy as np
 import torch
 
 from ._lib import LaunchProfiler, NassegError, current_stream, lib, ptr, require_device
@@ -2535,6 +2536,117 @@ def log_softmax_nll_mse(logits, target, teacher, ignore_index=255):
     tensors, both differentiable: the decoder-only step's loss and its distillation term (src/engine/trainer.py:
     144-149) from one pass over the logits.  ``teacher``: fp32, the logits' shape (the task0 cache's kd_y)."""
     return _LogSoftmaxNLLMSE.apply(logits, target, teacher, ignore_index)
+
+
+def _own_scalar(t, index):
+    """element ``index`` of the fp32 vector ``t`` under a 0-dim tensor of its own (no view, no copy: see
+    _BerHuMasked.forward)"""
+    return torch.empty(0, device=t.device, dtype=torch.float32).set_(t.untyped_storage(), t.storage_offset() + index,
+                                                                     (), ())
+
+
+def _select_config(who, thresh, min_kept, keep_fraction):
+    """(select, t_loss, min_kept, keep_fraction) of a hard-example selection; ValueError where the definition
+    ("Losses") has no meaning"""
+    min_kept, keep_fraction = int(min_kept), float(keep_fraction)
+    if thresh is not None and not 0.0 < float(thresh) < 1.0:
+        raise ValueError("{}: thresh must lie in (0, 1) (got {})".format(who, thresh))
+    if not 0.0 <= keep_fraction <= 1.0:
+        raise ValueError("{}: keep_fraction must lie in [0, 1] (got {})".format(who, keep_fraction))
+    if min_kept < 0:
+        raise ValueError("{}: min_kept must not be negative (got {})".format(who, min_kept))
+    select = thresh is not None or min_kept > 0 or keep_fraction > 0
+    if select and min_kept < 1:
+        raise ValueError("{}: hard-example selection needs min_kept >= 1".format(who))
+    t_loss = float("inf") if thresh is None else float(np.float32(-np.log(np.float64(thresh))))
+    return int(select), t_loss, min_kept, keep_fraction
+
+
+class _CrossEntropySelect(torch.autograd.Function):
+    """nasseg_ce_sel_fwd / _bwd.  Outputs: the loss (a scalar of its own: ``loss += aux`` is fine), and - not
+    differentiable - pixel_loss (B, H, W), tau (0-dim) and counts = {k, n_valid, n_kept} (int64)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, cfg):
+        logits = _cl(logits)
+        B, C, H, W = logits.shape
+        target, esz = _label_tensor(target)
+        if tuple(target.shape) != (B, H, W):
+            raise NassegError("cross_entropy_select: target {} does not match logits {}".format(
+                tuple(target.shape), tuple(logits.shape)))
+        if weight is not None:
+            require_device(weight)
+            if weight.dtype != torch.float32 or tuple(weight.shape) != (C,):
+                raise NassegError("cross_entropy_select: the class weights must be fp32 of shape ({},) (got {} {})"
+                                  .format(C, weight.dtype, tuple(weight.shape)))
+            weight = weight.contiguous()
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        stats = _vec(logits, 2)
+        counts = torch.empty((3,), device=logits.device, dtype=torch.int64)
+        pixel_loss = torch.empty((B, H, W), device=logits.device, dtype=torch.float32)
+        ws = _ws(logits, lib.query("nasseg_ce_sel_workspace"))
+        lib.call(_k("nasseg_ce_sel_fwd", logits), ptr(logits), ptr(target), esz, ptr(weight), B * H * W, C,
+                 int(ignore_index), *cfg, ptr(loss), ptr(stats), ptr(counts), ptr(pixel_loss), ptr(ws),
+                 current_stream())
+        ctx.save_for_backward(logits, target, weight, pixel_loss, stats)
+        ctx.cfg = (esz, int(ignore_index))
+        tau = _own_scalar(stats, 1)
+        ctx.mark_non_differentiable(pixel_loss, tau, counts)
+        return loss, pixel_loss, tau, counts
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        logits, target, weight, pixel_loss, stats = ctx.saved_tensors
+        esz, ignore = ctx.cfg
+        B, C, H, W = logits.shape
+        g = g.to(torch.float32).contiguous().view(1)
+        d = torch.empty_like(logits)
+        lib.call(_k("nasseg_ce_sel_bwd", logits), ptr(logits), ptr(target), esz, ptr(weight), ptr(pixel_loss),
+                 ptr(stats), ptr(g), B * H * W, C, ignore, ptr(d), current_stream())
+        return d, None, None, None, None
+
+
+def cross_entropy_select(logits, target, weight=None, ignore_index=255, thresh=None, min_kept=0, keep_fraction=0.0,
+                         return_parts=False):
+    """Class-weighted cross-entropy of (B, C, H, W) logits with online hard-example selection -> 0-dim loss of its
+    own storage ("Losses").
+
+    l_p = logsumexp(x_p) - x_p[t] over the valid pixels (label != ignore_index, in [0, C)).  Selection is active iff
+    ``thresh`` is given or ``min_kept`` > 0 or ``keep_fraction`` > 0 (then ``min_kept`` >= 1 is required):
+    k = min(n_valid, max(min_kept, ceil(keep_fraction * n_valid))), tau = min(-log(thresh), k-th largest l_p), and a
+    valid pixel is kept iff l_p >= tau - always on the unweighted l_p.  loss = sum_kept w[t] l_p / sum_kept w[t];
+    tau and the kept set are constants in backward, pixels that are not kept get exact zeros.
+    ``thresh=0.7, min_kept=100000``: the usual OHEM cross-entropy; ``keep_fraction=0.25`` alone (with min_kept=1):
+    top-k bootstrapping; nothing but ``weight``: torch's ``cross_entropy(weight=..., ignore_index=...)``.
+    ``return_parts``: (loss, pixel_loss (B, H, W) with -1 on invalid pixels, tau, counts = [k, n_valid, n_kept]).
+    No host synchronisation: capturable."""
+    cfg = _select_config("cross_entropy_select", thresh, min_kept, keep_fraction)
+    out = _CrossEntropySelect.apply(logits, target, weight, ignore_index, cfg)
+    return out if return_parts else out[0]
+
+
+def ohem_threshold(pixel_loss, thresh=None, min_kept=1, keep_fraction=0.0, t_loss=None):
+    """The selection of ``cross_entropy_select`` alone, over any fp32 tensor: entries < 0 do not take part.
+    Returns (tau, counts): tau = min(t_loss, k-th largest entry) as a 0-dim fp32 tensor, counts = int64
+    [k, n (entries that take part), entries >= tau among them]; t_loss = float32(-log(thresh)), +inf without
+    ``thresh`` (``t_loss``: that value given directly).  Exact (a radix select on the device), deterministic, no
+    host synchronisation."""
+    require_device(pixel_loss)
+    if pixel_loss.dtype != torch.float32 or pixel_loss.numel() == 0:
+        raise NassegError("ohem_threshold: a non-empty fp32 tensor is expected (got {} {})".format(
+            pixel_loss.dtype, tuple(pixel_loss.shape)))
+    _, t, min_kept, keep_fraction = _select_config("ohem_threshold", thresh, min_kept, keep_fraction)
+    if t_loss is not None:
+        if thresh is not None:
+            raise ValueError("ohem_threshold: give thresh or t_loss, not both")
+        t = float(t_loss)
+    v = pixel_loss.contiguous()
+    tau = torch.empty((), device=v.device, dtype=torch.float32)
+    counts = torch.empty((3,), device=v.device, dtype=torch.int64)
+    ws = _ws(v, lib.query("nasseg_ohem_workspace"))
+    lib.call("nasseg_ohem_threshold", ptr(v), v.numel(), t, min_kept, keep_fraction, ptr(tau), ptr(counts), ptr(ws),
+             current_stream())
+    return tau, counts
 
 
 class _BerHu(torch.autograd.Function):

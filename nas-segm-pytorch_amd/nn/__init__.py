@@ -1,2 +1,2 @@
 """Op registry, decoders and encoder of the NAS inner loop (mirrors src/nn)."""
-from .losses import BerHuLoss  # noqa: F401
+from .losses import BerHuLoss, SegmCrossEntropy  # noqa: F401

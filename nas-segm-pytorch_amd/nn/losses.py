@@ -1,4 +1,6 @@
-"""Criteria of the heads the reference has no training loss for."""
+"""Criteria the reference has no training loss for: the depth head's, and the segmentation heads' with class
+weights and hard-example mining."""
+import torch
 from torch import nn
 
 from .. import functional as F
@@ -20,3 +22,57 @@ class BerHuLoss(nn.Module):
 
     def extra_repr(self):
         return "valid_min={}, valid_max={}".format(self.valid_min, self.valid_max)
+
+
+class SegmCrossEntropy(nn.Module):
+    """LogSoftmax + NLL of (B, C, H, W) logits with class weights and online hard-example mining:
+    ``F.cross_entropy_select`` (definition: INTEGRATION.md, "Losses").  forward(logits, target (B, H, W) uint8 or
+    int64) -> 0-dim loss.  ``weight``: (C,) class weights, a buffer (made fp32 on the logits' device at first use);
+    ``thresh``: pixels whose target probability is below it are hard; ``min_kept`` / ``keep_fraction``: at least so
+    many / such a share of the valid pixels are kept.  Selection is active iff one of the three is given and then
+    needs ``min_kept >= 1``.  ``thresh=0.7, min_kept=100000``: the usual OHEM cross-entropy;
+    ``keep_fraction=0.25, min_kept=1``: top-k bootstrapping.  Handed to ``engine.trainer.train_segmenter`` /
+    ``train_task0`` as ``segm_crit`` it is the loss of every head; with neither weights nor selection those steps
+    run the plain ``F.log_softmax_nll`` as ever.  ``thresh``, ``min_kept`` and ``keep_fraction`` may be changed
+    between steps."""
+
+    def __init__(self, weight=None, ignore_index=255, thresh=None, min_kept=0, keep_fraction=0.0):
+        super(SegmCrossEntropy, self).__init__()
+        if weight is not None:
+            weight = torch.as_tensor(weight)
+            if weight.dim() != 1 or weight.numel() == 0:
+                raise ValueError("SegmCrossEntropy: weight must be 1-D, one entry per class (got shape {})".format(
+                    tuple(weight.shape)))
+        F._select_config("SegmCrossEntropy", thresh, min_kept, keep_fraction)
+        self.register_buffer("weight", weight)
+        self.ignore_index = int(ignore_index)
+        self.thresh = thresh
+        self.min_kept = min_kept
+        self.keep_fraction = keep_fraction
+
+    @property
+    def selects(self):
+        return self.thresh is not None or self.min_kept > 0 or self.keep_fraction > 0
+
+    def config(self):
+        """what a recorded step carries by value or by address (the stepper caches' key, engine/trainer.py)"""
+        return ("ce_sel", id(self.weight) if self.weight is not None else None, self.ignore_index, self.thresh,
+                self.min_kept, self.keep_fraction)
+
+    def prepare(self, device):
+        """the weights as the kernels read them: fp32, on ``device`` (a float64 or host vector is converted once,
+        here - never inside a step that is being recorded)"""
+        w = self.weight
+        if w is not None and (w.dtype != torch.float32 or w.device != torch.device(device)):
+            self.weight = w.to(device=device, dtype=torch.float32)
+        return self
+
+    def forward(self, logits, target):
+        self.prepare(logits.device)
+        return F.cross_entropy_select(logits, target, self.weight, self.ignore_index, self.thresh, self.min_kept,
+                                      self.keep_fraction)
+
+    def extra_repr(self):
+        return "classes={}, ignore_index={}, thresh={}, min_kept={}, keep_fraction={}".format(
+            None if self.weight is None else self.weight.numel(), self.ignore_index, self.thresh, self.min_kept,
+            self.keep_fraction)
