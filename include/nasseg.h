@@ -458,6 +458,42 @@ int nasseg_ce_sel_bwd(const float* logits, const void* target, int elem_size, co
                       const float* pixel_loss, const float* stats, const float* gscale, int64_t P, int C, int ignore,
                       float* dlogits, void* stream);
 
+/* The same cross-entropy plus a region-overlap term (soft Jaccard / Dice / Tversky; absent from the reference, whose
+ * reward is the mean IoU this term is the differentiable form of), computed in the two passes over the logits the
+ * cross-entropy makes anyway.  Valid pixels as above; q_p = softmax(x_p) in fp32 from the cross-entropy's own max
+ * and exp values.  Over ALL valid pixels (selection does not thin the term, class weights do not enter it):
+ *   I_c = sum_p q_pc [t_p == c],  S_c = sum_p q_pc,  N_c = sum_p [t_p == c]
+ *   D_c = (1 - alpha - beta) I_c + alpha S_c + beta N_c + smooth,  T_c = (I_c + smooth) / D_c
+ *   K = {c : N_c > 0} (all_classes != 0: every class; needs smooth > 0)
+ *   loss_region = 1 - sum_{c in K} T_c / |K|   (K empty: exactly 0, and an exactly zero gradient)
+ *   loss = loss_ce + region_weight * loss_region   (with_ce == 0: region_weight * loss_region; weight, stats, counts,
+ *                                                   pixel_loss may then be null and select must be 0)
+ * alpha = beta = 1: Jaccard; 0.5, 0.5: Dice; alpha, beta, smooth >= 0, alpha + beta > 0.  loss_ce, stats, counts,
+ * pixel_loss: bit-identical to nasseg_ce_sel_fwd's loss, stats, counts, pixel_loss.  The sums come from
+ * per-workgroup fp64 rows added in fp64 in a fixed order by one finalize launch (no atomics), which also writes
+ *   sums = {I_c} | {S_c} (fp32 [2C]);  ncls = {N_c} | |K| (int64 [C + 1])
+ *   coef = {-a_c / |K|} | {-b_c / |K| - m} (fp32 [2C]; a_c = b_c = 0 outside K),  a_c = dT_c/dI_c = (D_c -
+ *   (I_c + smooth) (1 - alpha - beta)) / D_c^2,  b_c = dT_c/dS_c = -(I_c + smooth) alpha / D_c^2,  m = the mean of the
+ *   -b_c / |K| over the C classes: a constant added to every G_pc leaves the gradient below as it is (sum_c q_pc
+ *   = 1), and without their mean the fp32 terms have less to cancel.
+ * Backward, with G_pc = coef[C + c] + [t_p == c] coef[c]:
+ *   dlogits = gscale * (cross-entropy part as nasseg_ce_sel_bwd, kept pixels only
+ *                       + region_weight * q_pj (G_pj - sum_c G_pc q_pc), every valid pixel)
+ * exact zeros on invalid pixels, written once; at region_weight = 0 bit-identical to nasseg_ce_sel_bwd's.
+ * The logits are read once per direction.  Any C (C <= 63 and 16-byte aligned logits: the LDS-tiled kernels).
+ * No host synchronisation, no allocation: capturable.  ws: nasseg_ce_region_workspace(C) floats, 8-byte aligned. */
+int64_t nasseg_ce_region_workspace(int C);
+int nasseg_ce_region_fwd(const float* logits, const void* target, int elem_size, const float* weight, int64_t P,
+                         int C, int ignore, int with_ce, int select, float t_loss, int64_t min_kept,
+                         double keep_fraction, double alpha, double beta, double smooth, int all_classes,
+                         double region_weight, float* loss, float* loss_ce, float* loss_region, float* stats,
+                         int64_t* counts, float* pixel_loss, float* coef, float* sums, int64_t* ncls, float* ws,
+                         void* stream);
+int nasseg_ce_region_bwd(const float* logits, const void* target, int elem_size, const float* weight,
+                         const float* pixel_loss, const float* stats, const float* coef, const float* gscale,
+                         int with_ce, double region_weight, int64_t P, int C, int ignore, float* dlogits,
+                         void* stream);
+
 /* berHu loss of the depth head (BASELINE config 5; absent from the reference - Laina et al.
  * 2016 eq. 2, "parity unpinned") */
 int nasseg_berhu_fwd(const float* pred, const float* target, int64_t n, float* out, float* ws,
@@ -732,6 +768,16 @@ int nasseg_bf16_ce_sel_fwd(const nasseg_bf16_t* logits, const void* target, int 
 int nasseg_bf16_ce_sel_bwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* weight,
                            const float* pixel_loss, const float* stats, const float* gscale, int64_t P, int C,
                            int ignore, nasseg_bf16_t* dlogits, void* stream);
+int nasseg_bf16_ce_region_fwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* weight,
+                              int64_t P, int C, int ignore, int with_ce, int select, float t_loss, int64_t min_kept,
+                              double keep_fraction, double alpha, double beta, double smooth, int all_classes,
+                              double region_weight, float* loss, float* loss_ce, float* loss_region, float* stats,
+                              int64_t* counts, float* pixel_loss, float* coef, float* sums, int64_t* ncls, float* ws,
+                              void* stream);
+int nasseg_bf16_ce_region_bwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* weight,
+                              const float* pixel_loss, const float* stats, const float* coef, const float* gscale,
+                              int with_ce, double region_weight, int64_t P, int C, int ignore,
+                              nasseg_bf16_t* dlogits, void* stream);
 int nasseg_bf16_berhu_fwd(const nasseg_bf16_t* pred, const nasseg_bf16_t* target, int64_t n, float* out, float* ws,
                      void* stream);
 int nasseg_bf16_berhu_bwd(const nasseg_bf16_t* pred, const nasseg_bf16_t* target, const float* stats,

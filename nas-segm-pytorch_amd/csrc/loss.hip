@@ -569,6 +569,453 @@ __global__ __launch_bounds__(256) void ce_sel_finalize_kernel(const float* __res
 }
 
 // ---------------------------------------------------------------------------
+// Region-overlap term (soft Jaccard / Dice / Tversky; nasseg_ce_region_fwd / _bwd, definition: include/nasseg.h)
+// computed in the two passes over the logits the cross-entropy makes anyway.  Over the valid pixels, with
+// q = softmax(x): I_c = sum q_pc [t_p == c], S_c = sum q_pc, N_c = sum [t_p == c].
+// Forward: a workgroup adds the three rows of its pixels - fp32 within a tile of 256 pixels, fp64 across its tiles -
+// and writes them as row blockIdx.x of part[3][C][kRegionRows] (fp64); region_finalize_kernel adds the rows in fp64 in
+// a fixed order.  No atomics anywhere: deterministic, capturable.
+// Kernels of their own (not further flags of ce_tile_kernel / ce_fwd_kernel / ce_bwd_kernel), so that what the
+// existing entry points compute cannot move; pixel -> (workgroup, thread) mapping, the per-pixel max / exp / sum
+// arithmetic and the cross-entropy gradient expression are copied from them, so that pixel_loss and, at
+// region_weight = 0, dlogits are bit-identical to nasseg_ce_sel_fwd's / _bwd's.
+// ---------------------------------------------------------------------------
+constexpr int kRegionRows = 1024;  // (= the cap of ce_grid)
+
+// One [np][C] tile of logits into LDS rows of stride CS: the staging loops of ce_tile_kernel.
+__device__ __forceinline__ void region_stage(const act_t* __restrict__ src, float* __restrict__ tile, int nel, int C,
+                                             int CS, int tid) {
+  const int nel4 = nel >> 2;
+  for (int i = tid; i < nel4; i += 256) {
+    const float4 v = lda4(src + 4 * i);
+    int pix = (4 * i) / C;
+    int c = 4 * i - pix * C;
+    const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      tile[pix * CS + c] = e[r];
+      if (++c == C) {
+        c = 0;
+        ++pix;
+      }
+    }
+  }
+  for (int i = 4 * nel4 + tid; i < nel; i += 256) {
+    const int pix = i / C;
+    tile[pix * CS + (i - pix * C)] = lda1(src + i);
+  }
+}
+
+// C <= 63, aligned logits.  LDS: the [256][C | 1] tile of ce_tile_kernel and nothing else (C = 19: 19,456 bytes).
+// Each lane turns its pixel's row into q in place (zeros for a pixel that is not valid) and marks the label's entry
+// with the sign bit (q >= 0, and -0 keeps the mark): the class sums are then column sums of the tile - thread
+// (seg, col) adds the rows of segment seg (256 / C segments) in order, the segments' sums pass through the head of
+// the tile (free by then) and thread c < C adds them in order.
+// (amdgpu_waves_per_eu: 8 workgroups per CU, as many as the LDS tile allows at C = 19 and as ce_tile_kernel runs.)
+template <typename TL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void region_tile_fwd_kernel(
+    const act_t* __restrict__ logits, const TL* __restrict__ target, int64_t P, int C, int ignore,
+    float* __restrict__ pixel_loss, uint32_t* __restrict__ sel_hist, double* __restrict__ part) {
+  if (sel_hist) sel_clear(sel_hist);
+  extern __shared__ float tile[];  // [256][C | 1]
+  const int CS = C | 1;
+  const int tid = threadIdx.x;
+  const int NS = 256 / C;              // row segments (>= 4)
+  const int RS = (256 + NS - 1) / NS;  // rows per segment
+  const int seg = tid / C, col = tid - seg * C;
+  const int64_t ntiles = (P + 255) / 256;
+  double accI = 0.0, accS = 0.0, accN = 0.0;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int64_t p0 = t * 256;
+    const int np = (int)((P - p0) < 256 ? (P - p0) : 256);
+    region_stage(logits + p0 * C, tile, np * C, C, CS, tid);
+    __syncthreads();
+    {
+      float* row = tile + tid * CS;
+      int64_t tg = -1;
+      bool valid = false;
+      if (tid < np) {
+        tg = (int64_t)target[p0 + tid];
+        valid = !(tg == ignore || tg < 0 || tg >= C);
+      }
+      if (valid) {
+        float m = row[0];
+        for (int c = 1; c < C; ++c) m = fmaxf(m, row[c]);
+        const float xt = row[tg];
+        float sum = 0.f;
+        for (int c = 0; c < C; ++c) {
+          const float e = expf(row[c] - m);
+          row[c] = e;
+          sum += e;
+        }
+        if (pixel_loss) pixel_loss[p0 + tid] = (m + logf(sum)) - xt;
+        const float inv = 1.f / sum;
+        for (int c = 0; c < C; ++c) row[c] *= inv;
+        row[tg] = -row[tg];
+      } else {
+        if (tid < np && pixel_loss) pixel_loss[p0 + tid] = -1.f;
+        for (int c = 0; c < C; ++c) row[c] = 0.f;  // (rows past the end of a ragged tile too)
+      }
+    }
+    __syncthreads();
+    float sI = 0.f, sS = 0.f, sN = 0.f;
+    if (seg < NS) {
+      const int r1 = (seg + 1) * RS < 256 ? (seg + 1) * RS : 256;
+      for (int r = seg * RS; r < r1; ++r) {
+        const float v = tile[r * CS + col];
+        const float a = fabsf(v);
+        const bool hit = (__float_as_uint(v) >> 31) != 0u;
+        sS += a;
+        sI += hit ? a : 0.f;
+        sN += hit ? 1.f : 0.f;
+      }
+    }
+    __syncthreads();
+    if (seg < NS) {
+      tile[(seg * 3 + 0) * C + col] = sI;
+      tile[(seg * 3 + 1) * C + col] = sS;
+      tile[(seg * 3 + 2) * C + col] = sN;
+    }
+    __syncthreads();
+    if (tid < C) {
+      float tI = 0.f, tS = 0.f, tN = 0.f;
+      for (int s = 0; s < NS; ++s) {
+        tI += tile[(s * 3 + 0) * C + tid];
+        tS += tile[(s * 3 + 1) * C + tid];
+        tN += tile[(s * 3 + 2) * C + tid];
+      }
+      accI += (double)tI;
+      accS += (double)tS;
+      accN += (double)tN;
+    }
+    __syncthreads();
+  }
+  if (tid < C) {
+    part[((int64_t)0 * C + tid) * kRegionRows + blockIdx.x] = accI;
+    part[((int64_t)1 * C + tid) * kRegionRows + blockIdx.x] = accS;
+    part[((int64_t)2 * C + tid) * kRegionRows + blockIdx.x] = accN;
+  }
+}
+
+__device__ __forceinline__ float wave_allsum(float v) {  // (a fixed butterfly: the same pairing every time)
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ double wave_allsum(double v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// Any C, any alignment: one lane per pixel straight from memory, as ce_fwd_kernel (same pixel mapping and per-pixel
+// arithmetic).  The class sums by another route: per class a butterfly over the wave, the four waves' sums through
+// 3 KB of LDS in chunks of 64 classes, and the workgroup's row of `part` is accumulated in place (each element by
+// the one thread that owns it, in tile order).
+template <typename TL>
+__global__ __launch_bounds__(256) void region_fwd_kernel(const act_t* __restrict__ logits,
+                                                         const TL* __restrict__ target, int64_t P, int C, int ignore,
+                                                         float* __restrict__ pixel_loss,
+                                                         uint32_t* __restrict__ sel_hist, double* __restrict__ part) {
+  if (sel_hist) sel_clear(sel_hist);
+  __shared__ float red[4][3][64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t ntiles = (P + 255) / 256;
+  bool first = true;
+  for (int64_t tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
+    const int64_t p = tl * 256 + tid;
+    const act_t* lp = logits + (p < P ? p : 0) * C;
+    int64_t t = -1;
+    bool valid = false;
+    float m = 0.f, inv = 0.f;
+    if (p < P) {
+      t = (int64_t)target[p];
+      valid = !(t == ignore || t < 0 || t >= C);  // out-of-range labels are skipped, never read
+      if (valid) {
+        m = lda1(lp);
+        for (int c = 1; c < C; ++c) m = fmaxf(m, lda1(lp + c));
+        float s = 0.f;
+        for (int c = 0; c < C; ++c) s += expf(lda1(lp + c) - m);
+        const float lse = m + logf(s);
+        if (pixel_loss) pixel_loss[p] = lse - lda1(lp + t);
+        inv = 1.f / s;
+      } else if (pixel_loss) {
+        pixel_loss[p] = -1.f;
+      }
+    }
+    for (int c0 = 0; c0 < C; c0 += 64) {
+      const int nc = C - c0 < 64 ? C - c0 : 64;
+      for (int j = 0; j < nc; ++j) {
+        const int c = c0 + j;
+        const float q = valid ? expf(lda1(lp + c) - m) * inv : 0.f;
+        const bool hit = valid && t == (int64_t)c;
+        const float vS = wave_allsum(q);
+        const float vI = wave_allsum(hit ? q : 0.f);
+        const float vN = (float)__popcll(__ballot(hit));
+        if (lane == 0) {
+          red[wave][0][j] = vI;
+          red[wave][1][j] = vS;
+          red[wave][2][j] = vN;
+        }
+      }
+      __syncthreads();
+      if (tid < 3 * nc) {
+        const int k = tid / nc, j = tid - k * nc;
+        const float v = ((red[0][k][j] + red[1][k][j]) + red[2][k][j]) + red[3][k][j];
+        double* dst = part + ((int64_t)k * C + c0 + j) * kRegionRows + blockIdx.x;
+        *dst = first ? (double)v : *dst + (double)v;
+      }
+      __syncthreads();
+    }
+    first = false;
+  }
+}
+
+// One workgroup of 1024 threads.  1. with_ce: the statements of ce_sel_finalize_kernel, by the first 256 threads, on
+// the sum pass's partials (lce, stats, counts: bit-identical to nasseg_ce_sel_fwd's).  2. wave w of 16 adds rows
+// 0 .. nblk-1 of part for the elements w, w + 16, ...: each lane its <= 16 rows, all loads in flight at once, added
+// in row order, then the butterfly -> tot[3][C].  3. per class T_c and the members of K; sum T and |K| by a tree;
+// lreg = 1 - sum T / |K| (0 when K is empty), loss = [lce +] rweight * lreg, and for backward
+// coef = {-a_c / |K|} | {-b_c / |K| - their mean over the C classes} (outside K: a_c = b_c = 0).  All in fp64.
+__global__ __launch_bounds__(1024) void region_finalize_kernel(const float* __restrict__ partial,
+                                                               const double* __restrict__ part, int nblk, int C,
+                                                               int with_ce, int selected, double alpha, double beta,
+                                                               double smooth, int all_classes, double rweight,
+                                                               float* __restrict__ loss, float* __restrict__ lce,
+                                                               float* __restrict__ lreg, float* __restrict__ stats,
+                                                               int64_t* __restrict__ counts, float* __restrict__ coef,
+                                                               float* __restrict__ sums, int64_t* __restrict__ ncls,
+                                                               double* tot) {
+  __shared__ double red_l[256];
+  __shared__ double red_w[256];
+  __shared__ double red_n[256];
+  const int tid = threadIdx.x;
+  const bool head = tid < 256;
+  if (with_ce) {
+    if (head) {
+      double l = 0.0, w = 0.0, n = 0.0;
+      for (int b = tid; b < nblk; b += 256) {
+        l += (double)partial[b * 3];
+        w += (double)partial[b * 3 + 1];
+        n += (double)partial[b * 3 + 2];
+      }
+      red_l[tid] = l;
+      red_w[tid] = w;
+      red_n[tid] = n;
+    }
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (tid < s) {
+        red_l[tid] += red_l[tid + s];
+        red_w[tid] += red_w[tid + s];
+        red_n[tid] += red_n[tid + s];
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      lce[0] = (float)(red_l[0] / red_w[0]);
+      stats[0] = (float)red_w[0];
+      counts[2] = (int64_t)red_n[0];
+      if (!selected) {
+        stats[1] = -__builtin_inff();
+        counts[0] = counts[1] = (int64_t)red_n[0];
+      }
+    }
+    __syncthreads();
+  } else if (tid == 0) {
+    lce[0] = 0.f;
+  }
+  const int lane = tid & 63, wave = tid >> 6;
+  for (int e = wave; e < 3 * C; e += 16) {
+    const double* src = part + (int64_t)e * kRegionRows;
+    double r[kRegionRows / 64];
+#pragma unroll
+    for (int i = 0; i < kRegionRows / 64; ++i) r[i] = lane + 64 * i < nblk ? src[lane + 64 * i] : 0.0;
+    double v = 0.0;
+#pragma unroll
+    for (int i = 0; i < kRegionRows / 64; ++i) v += r[i];
+    v = wave_allsum(v);
+    if (lane == 0) tot[e] = v;
+  }
+  __syncthreads();
+  const double gamma = 1.0 - alpha - beta;
+  double tsum = 0.0, bsum = 0.0, kcnt = 0.0;
+  if (head) {
+    for (int c = tid; c < C; c += 256) {
+      const double I = tot[c], S = tot[C + c], N = tot[2 * C + c];
+      if (all_classes || N > 0.0) {
+        const double D = gamma * I + alpha * S + beta * N + smooth;
+        tsum += (I + smooth) / D;
+        bsum += (I + smooth) * alpha / (D * D);
+        kcnt += 1.0;
+      }
+    }
+    red_l[tid] = tsum;
+    red_w[tid] = bsum;
+    red_n[tid] = kcnt;
+  }
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) {
+      red_l[tid] += red_l[tid + s];
+      red_w[tid] += red_w[tid + s];
+      red_n[tid] += red_n[tid + s];
+    }
+    __syncthreads();
+  }
+  const double K = red_n[0];
+  // The gradient q_j (G_j - sum_c G_c q_c) does not change when a constant is added to every G_c (sum_c q_c = 1):
+  // the -b_c / |K| are stored minus their mean over the C classes, so that fp32 does not have to cancel it.
+  const double bmean = K > 0.0 ? red_w[0] / K / (double)C : 0.0;
+  if (head) {
+    for (int c = tid; c < C; c += 256) {
+      const double I = tot[c], S = tot[C + c], N = tot[2 * C + c];
+      float ca = 0.f;
+      double cb = 0.0;
+      if (all_classes || N > 0.0) {
+        const double D = gamma * I + alpha * S + beta * N + smooth;
+        ca = (float)(-((D - (I + smooth) * gamma) / (D * D)) / K);
+        cb = ((I + smooth) * alpha / (D * D)) / K;
+      }
+      coef[c] = ca;
+      coef[C + c] = (float)(cb - bmean);
+      sums[c] = (float)I;
+      sums[C + c] = (float)S;
+      ncls[c] = (int64_t)N;
+    }
+  }
+  if (tid == 0) {
+    const float lr = K > 0.0 ? (float)(1.0 - red_l[0] / K) : 0.f;
+    lreg[0] = lr;
+    ncls[C] = (int64_t)K;
+    loss[0] = (float)((with_ce ? (double)lce[0] : 0.0) + rweight * (double)lr);
+  }
+}
+
+// dlogits = gscale * [cross-entropy part of nasseg_ce_sel_bwd (kept pixels) + rweight * q (G - sum_c G_c q_c)] with
+// G_c = coef[C + c] + [c == t] coef[c] (G up to a constant, which cancels), on every valid pixel; exact zeros on the
+// others; written once.  Tiled form:
+// staging, softmax and the coalesced store of ce_tile_kernel<BWD, SEL>.
+template <typename TL>
+__global__ __launch_bounds__(256) void region_tile_bwd_kernel(const act_t* __restrict__ logits,
+                                                              const TL* __restrict__ target, int64_t P, int C,
+                                                              int ignore, const float* __restrict__ weight,
+                                                              const float* __restrict__ pixel_loss,
+                                                              const float* __restrict__ stats,
+                                                              const float* __restrict__ coef,
+                                                              const float* __restrict__ gscale, int with_ce,
+                                                              float rweight, act_t* __restrict__ dlogits) {
+  extern __shared__ float tile[];  // [256][C | 1]
+  const int CS = C | 1;
+  const int tid = threadIdx.x;
+  const int64_t ntiles = (P + 255) / 256;
+  const float g = gscale ? gscale[0] : 1.f;
+  const float gr = g * rweight;
+  const float sumw = with_ce ? stats[0] : 1.f, tau = with_ce ? stats[1] : 0.f;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int64_t p0 = t * 256;
+    const int np = (int)((P - p0) < 256 ? (P - p0) : 256);
+    const int nel = np * C;
+    const int nel4 = nel >> 2;
+    float pl = -1.f;
+    if (with_ce && tid < np) pl = pixel_loss[p0 + tid];
+    region_stage(logits + p0 * C, tile, nel, C, CS, tid);
+    __syncthreads();
+    if (tid < np) {
+      float* row = tile + tid * CS;
+      const int64_t tg = (int64_t)target[p0 + tid];
+      if (tg == ignore || tg < 0 || tg >= C) {
+        for (int c = 0; c < C; ++c) row[c] = 0.f;
+      } else {
+        const bool kept = with_ce && sel_kept(pl, tau);
+        const float gp = kept ? (g * (weight ? weight[tg] : 1.f)) / sumw : 0.f;
+        float m = row[0];
+        for (int c = 1; c < C; ++c) m = fmaxf(m, row[c]);
+        float sum = 0.f, dot = 0.f;
+        for (int c = 0; c < C; ++c) {
+          const float e = expf(row[c] - m);
+          row[c] = e;
+          sum += e;
+          dot = fmaf(coef[C + c], e, dot);
+        }
+        const float inv = 1.f / sum;
+        dot = fmaf(coef[tg], row[tg], dot) * inv;
+        for (int c = 0; c < C; ++c) {
+          const bool y = (int64_t)c == tg;
+          // (fmaf: the contraction the compiler makes of ce_tile_kernel's `row[c] * inv - onehot`)
+          const float ce = kept ? gp * fmaf(row[c], inv, y ? -1.f : -0.f) : 0.f;
+          const float G = coef[C + c] + (y ? coef[c] : 0.f);
+          row[c] = fmaf(gr, (row[c] * inv) * (G - dot), ce);
+        }
+      }
+    }
+    __syncthreads();
+    act_t* dst = dlogits + p0 * C;
+    for (int i = tid; i < nel4; i += 256) {
+      int pix = (4 * i) / C;
+      int c = 4 * i - pix * C;
+      float e[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        e[r] = tile[pix * CS + c];
+        if (++c == C) {
+          c = 0;
+          ++pix;
+        }
+      }
+      sta4(dst + 4 * i, make_float4(e[0], e[1], e[2], e[3]));
+    }
+    for (int i = 4 * nel4 + tid; i < nel; i += 256) {
+      const int pix = i / C;
+      sta1(dst + i, tile[pix * CS + (i - pix * C)]);
+    }
+    __syncthreads();
+  }
+}
+
+// ... and one lane per pixel, as ce_bwd_kernel<SEL>.
+template <typename TL>
+__global__ __launch_bounds__(256) void region_bwd_kernel(const act_t* __restrict__ logits,
+                                                         const TL* __restrict__ target, int64_t P, int C, int ignore,
+                                                         const float* __restrict__ weight,
+                                                         const float* __restrict__ pixel_loss,
+                                                         const float* __restrict__ stats,
+                                                         const float* __restrict__ coef,
+                                                         const float* __restrict__ gscale, int with_ce, float rweight,
+                                                         act_t* __restrict__ dlogits) {
+  const float g = gscale ? gscale[0] : 1.f;
+  const float gr = g * rweight;
+  const float sumw = with_ce ? stats[0] : 1.f, tau = with_ce ? stats[1] : 0.f;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
+    const int64_t t = (int64_t)target[p];
+    const act_t* lp = logits + p * C;
+    act_t* dp = dlogits + p * C;
+    if (t == ignore || t < 0 || t >= C) {
+      for (int c = 0; c < C; ++c) sta1(dp + c, 0.f);
+      continue;
+    }
+    const bool kept = with_ce && sel_kept(pixel_loss[p], tau);
+    const float gp = kept ? (g * (weight ? weight[t] : 1.f)) / sumw : 0.f;
+    float m = lda1(lp);
+    for (int c = 1; c < C; ++c) m = fmaxf(m, lda1(lp + c));
+    float s = 0.f, dot = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float e = expf(lda1(lp + c) - m);
+      s += e;
+      dot = fmaf(coef[C + c], e, dot);
+    }
+    const float inv = 1.f / s;
+    dot = fmaf(coef[t], expf(lda1(lp + t) - m), dot) * inv;
+    for (int c = 0; c < C; ++c) {
+      const bool y = (int64_t)c == t;
+      const float e = expf(lda1(lp + c) - m);
+      const float sm = e * inv;
+      const float ce = kept ? gp * fmaf(e, inv, y ? -1.f : -0.f) : 0.f;  // (as above, for ce_bwd_kernel)
+      const float G = coef[C + c] + (y ? coef[c] : 0.f);
+      sta1(dp + c, fmaf(gr, sm * (G - dot), ce));
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // berHu (reverse Huber) loss for the depth head (BASELINE config 5).  Not present in
 // the reference ("parity unpinned"): Laina et al. 2016, eq. 2 -
 //   B(d) = |d| if |d| <= c else (d^2 + c^2) / (2c),  c = 0.2 * max|d| over the batch,
@@ -785,6 +1232,110 @@ int NASSEG_FN(ce_sel_bwd)(const act_t* logits, const void* target, int elem_size
                        (const uint8_t*)target, stats, gscale, P, C, ignore, dlogits, nullptr, nullptr, weight,
                        pixel_loss);
   NASSEG_LAUNCH_CHECK("ce_sel_bwd");
+  return NASSEG_OK;
+}
+
+// Cross-entropy of nasseg_ce_sel_fwd plus the region-overlap term (include/nasseg.h), the logits read once.
+// ws: nasseg_ce_region_workspace(C) floats = nasseg_ce_sel_workspace()'s | fp64 part[3][C][1024] | fp64 tot[3][C].
+#if NASSEG_FP32_ONLY
+int64_t nasseg_ce_region_workspace(int C) {
+  if (C < 1) return 0;
+  return 3 * 1024 + kSelWsWords + 2 * ((int64_t)3 * C * kRegionRows + (int64_t)3 * C);
+}
+#endif
+
+int NASSEG_FN(ce_region_fwd)(const act_t* logits, const void* target, int elem_size, const float* weight, int64_t P,
+                             int C, int ignore, int with_ce, int select, float t_loss, int64_t min_kept,
+                             double keep_fraction, double alpha, double beta, double smooth, int all_classes,
+                             double region_weight, float* loss, float* loss_ce, float* loss_region, float* stats,
+                             int64_t* counts, float* pixel_loss, float* coef, float* sums, int64_t* ncls, float* ws,
+                             void* stream) {
+  NASSEG_REQUIRE(P > 0 && P < ((int64_t)1 << 32) && C > 0, "ce_region_fwd: bad shape");
+  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_region_fwd: elem_size %d not supported", elem_size);
+  NASSEG_REQUIRE(logits && target && loss && loss_ce && loss_region && coef && sums && ncls && ws,
+                 "ce_region_fwd: null pointer");
+  NASSEG_REQUIRE(!with_ce || (stats && counts && pixel_loss), "ce_region_fwd: null pointer");
+  NASSEG_REQUIRE(with_ce || !select, "ce_region_fwd: selection without the cross-entropy");
+  NASSEG_REQUIRE(!select || (min_kept >= 1 && keep_fraction >= 0.0 && keep_fraction <= 1.0),
+                 "ce_region_fwd: selection needs min_kept >= 1 and 0 <= keep_fraction <= 1");
+  NASSEG_REQUIRE(alpha >= 0.0 && beta >= 0.0 && alpha + beta > 0.0 && smooth >= 0.0,
+                 "ce_region_fwd: alpha, beta, smooth >= 0 and alpha + beta > 0 expected");
+  NASSEG_REQUIRE(!all_classes || smooth > 0.0, "ce_region_fwd: all classes need smooth > 0");
+  static_assert((3 * 1024 + kSelWsWords) % 2 == 0, "the fp64 part of the workspace is 8-byte aligned");
+  NASSEG_REQUIRE(((uintptr_t)ws & 7) == 0, "ce_region_fwd: the workspace must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = ce_grid(P);  // (<= kRegionRows)
+  const size_t lds = (size_t)256 * (C | 1) * sizeof(float);
+  const bool tiled = C <= kCeTileMaxC && ((uintptr_t)logits & 15) == 0;
+  uint32_t* hist = select ? (uint32_t*)(ws + 3 * 1024) : nullptr;  // (cleared by the forward kernel on its way)
+  double* part = (double*)(ws + 3 * 1024 + kSelWsWords);
+  double* tot = part + (int64_t)3 * C * kRegionRows;
+  float* pl = with_ce ? pixel_loss : nullptr;
+  if (tiled && elem_size == 8)
+    hipLaunchKernelGGL(region_tile_fwd_kernel<int64_t>, dim3(grid), dim3(256), lds, s, logits,
+                       (const int64_t*)target, P, C, ignore, pl, hist, part);
+  else if (tiled)
+    hipLaunchKernelGGL(region_tile_fwd_kernel<uint8_t>, dim3(grid), dim3(256), lds, s, logits,
+                       (const uint8_t*)target, P, C, ignore, pl, hist, part);
+  else if (elem_size == 8)
+    hipLaunchKernelGGL(region_fwd_kernel<int64_t>, dim3(grid), dim3(256), 0, s, logits, (const int64_t*)target, P, C,
+                       ignore, pl, hist, part);
+  else
+    hipLaunchKernelGGL(region_fwd_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)target, P, C,
+                       ignore, pl, hist, part);
+  NASSEG_LAUNCH_CHECK("ce_region_fwd");
+  if (with_ce) {
+    if (select) {
+      const int rc =
+          sel_launch(pixel_loss, P, t_loss, min_kept, keep_fraction, stats + 1, counts, ws + 3 * 1024, true, s);
+      if (rc != NASSEG_OK) return rc;
+    }
+    const float* tau = select ? stats + 1 : nullptr;
+    if (elem_size == 8)
+      hipLaunchKernelGGL(ce_sel_sum_kernel<int64_t>, dim3(grid), dim3(256), 0, s, pixel_loss, (const int64_t*)target,
+                         weight, P, tau, ws);
+    else
+      hipLaunchKernelGGL(ce_sel_sum_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, pixel_loss, (const uint8_t*)target,
+                         weight, P, tau, ws);
+    NASSEG_LAUNCH_CHECK("ce_region_sum");
+  }
+  hipLaunchKernelGGL(region_finalize_kernel, dim3(1), dim3(1024), 0, s, ws, part, grid, C, with_ce, select, alpha, beta,
+                     smooth, all_classes, region_weight, loss, loss_ce, loss_region, stats, counts, coef, sums, ncls,
+                     tot);
+  NASSEG_LAUNCH_CHECK("ce_region_finalize");
+  return NASSEG_OK;
+}
+
+int NASSEG_FN(ce_region_bwd)(const act_t* logits, const void* target, int elem_size, const float* weight,
+                             const float* pixel_loss, const float* stats, const float* coef, const float* gscale,
+                             int with_ce, double region_weight, int64_t P, int C, int ignore, act_t* dlogits,
+                             void* stream) {
+  NASSEG_REQUIRE(P > 0 && C > 0, "ce_region_bwd: bad shape");
+  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_region_bwd: elem_size %d not supported", elem_size);
+  NASSEG_REQUIRE(logits && target && coef && dlogits, "ce_region_bwd: null pointer");
+  NASSEG_REQUIRE(!with_ce || (pixel_loss && stats), "ce_region_bwd: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = ce_grid(P) * 2;
+  const size_t lds = (size_t)256 * (C | 1) * sizeof(float);
+  int64_t tiles = (P + 255) / 256;
+  if (tiles > 4096) tiles = 4096;
+  const bool tiled = C <= kCeTileMaxC && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0;
+  const float rw = (float)region_weight;
+  if (tiled && elem_size == 8)
+    hipLaunchKernelGGL(region_tile_bwd_kernel<int64_t>, dim3((unsigned)tiles), dim3(256), lds, s, logits,
+                       (const int64_t*)target, P, C, ignore, weight, pixel_loss, stats, coef, gscale, with_ce, rw,
+                       dlogits);
+  else if (tiled)
+    hipLaunchKernelGGL(region_tile_bwd_kernel<uint8_t>, dim3((unsigned)tiles), dim3(256), lds, s, logits,
+                       (const uint8_t*)target, P, C, ignore, weight, pixel_loss, stats, coef, gscale, with_ce, rw,
+                       dlogits);
+  else if (elem_size == 8)
+    hipLaunchKernelGGL(region_bwd_kernel<int64_t>, dim3(grid), dim3(256), 0, s, logits, (const int64_t*)target, P, C,
+                       ignore, weight, pixel_loss, stats, coef, gscale, with_ce, rw, dlogits);
+  else
+    hipLaunchKernelGGL(region_bwd_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)target, P, C,
+                       ignore, weight, pixel_loss, stats, coef, gscale, with_ce, rw, dlogits);
+  NASSEG_LAUNCH_CHECK("ce_region_bwd");
   return NASSEG_OK;
 }
 

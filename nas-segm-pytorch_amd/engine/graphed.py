@@ -350,7 +350,7 @@ class GraphedSegmenterStep(_GraphedStep):
         depth_crit (an ``nn.BerHuLoss``): the depth step of ``train_segmenter`` - ``target`` is the fp32 (B, H, W)
         depth map at the image's size, the loss is ``task1_depth_loss`` (auxiliary heads included).
         segm_crit (an ``nn.SegmCrossEntropy``): the loss of every head instead of the plain softmax/NLL; its
-        threshold, ``min_kept`` and ``keep_fraction`` are recorded by value - a change needs a new stepper
+        threshold, ``min_kept``, ``keep_fraction`` and region term are recorded by value - a change needs a new stepper
         (engine/trainer.py's cache keys on them)."""
         model = inner(segmenter)
         self.optim_enc, self.optim_dec = optim_enc, optim_dec

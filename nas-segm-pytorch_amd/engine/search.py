@@ -53,8 +53,8 @@ def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", 
     task="depth": the masks are fp32 depth maps at the image's size (holes: 0 / NaN / inf), the decoder has one
     output channel, the loss is BerHuLoss(valid_min=0) and the reward comes from ``validate_depth``
     (``min_depth`` / ``max_depth``: its valid range).
-    ``segm_crit`` (task="segm"): the training criterion, e.g. an nn.SegmCrossEntropy with class weights or
-    hard-example mining; None: LogSoftmax + NLL with ignore index 255."""
+    ``segm_crit`` (task="segm"): the training criterion, e.g. an nn.SegmCrossEntropy with class weights,
+    hard-example mining or a region-overlap (soft Jaccard / Dice) term; None: LogSoftmax + NLL with ignore index 255."""
     if _task(task) == "depth":
         return _evaluate_depth_candidate(config, train_batches, val_batches, ctrl_version, agg_size, aux_cell,
                                          repeats, epochs, aux_weight, device, stats, graphed, min_depth, max_depth)

@@ -86,13 +86,13 @@ _MAPPED_CRITS = weakref.WeakKeyDictionary()  # nn.NLLLoss with class weights -> 
 
 def _segm_crit(segm_crit, device=None):
     """the criterion that replaces the plain softmax/NLL of every head, else None (F.log_softmax_nll with the
-    criterion's ``ignore_index``, as ever).  An nn.SegmCrossEntropy with class weights or hard-example selection is
-    that criterion itself; an nn.NLLLoss (nn.NLLLoss2d where torch has it) with ``weight`` and mean reduction - the
-    one-line change to src/main_search.py:435 - is mapped to the equivalent SegmCrossEntropy, once per criterion
-    and weight tensor.  ``device``: the weights are made fp32 there now (not inside a step being recorded)."""
+    criterion's ``ignore_index``, as ever).  An nn.SegmCrossEntropy with class weights, hard-example selection or a
+    region-overlap term is that criterion itself; an nn.NLLLoss (nn.NLLLoss2d where torch has it) with ``weight`` and
+    mean reduction - the one-line change to src/main_search.py:435 - is mapped to the equivalent SegmCrossEntropy,
+    once per criterion and weight tensor.  ``device``: the weights are made fp32 there now (not inside a step being recorded)."""
     crit = None
     if isinstance(segm_crit, SegmCrossEntropy):
-        if segm_crit.weight is not None or segm_crit.selects:
+        if segm_crit.weight is not None or segm_crit.selects or segm_crit.region is not None:
             crit = segm_crit
     elif (isinstance(segm_crit, nn.NLLLoss) and segm_crit.weight is not None
           and getattr(segm_crit, "reduction", "mean") == "mean"):
@@ -393,7 +393,7 @@ def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255
     batch (one kernel per cache entry), decoder forward, bilinear resize to ``out_size``,
     softmax/NLL [+ kd_coeff * MSE to the cached teacher logits, one fused kernel] (+ aux heads),
     backward, [all-reduce], clip, optimiser.
-    ``segm_crit`` (``_segm_crit``'s: class weights / hard-example selection) is the loss of every head; with
+    ``segm_crit`` (``_segm_crit``'s: class weights / hard-example selection / region term): the loss of every head; with
     distillation as well the step is launched from the host and ``kd_crit`` is called as written."""
     decoder = _inner(segmenter).decoder
     feat = Xy_train[cache_feature_keys(Xy_train)[0]]
@@ -480,7 +480,7 @@ def segmenter_step(segmenter, image, target, optim_enc, optim_dec, ignore_index=
     -> per-sub-module norm clipping -> optimiser steps.
     ``depth_crit`` (an nn.BerHuLoss): the depth step instead - ``target`` is the fp32 (B, H, W) depth map and the
     loss is the masked berHu of every head against it (trainer_common.task1_depth_loss).
-    ``segm_crit``: any segmentation criterion - one with class weights or hard-example selection (``_segm_crit``)
+    ``segm_crit``: any segmentation criterion - one with class weights, selection or a region term (``_segm_crit``)
     is the loss of every head, anything else leaves the plain softmax/NLL with ``ignore_index``.
     """
     segm_crit = _segm_crit(segm_crit, image.device)

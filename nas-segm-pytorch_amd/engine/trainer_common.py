@@ -38,8 +38,8 @@ def _heads(output):
 
 
 def _head_loss(logits, target, ignore_index, segm_crit):
-    """the loss of one head: F.log_softmax_nll, or ``segm_crit`` (an nn.SegmCrossEntropy with class weights or
-    hard-example selection - every head selects among its own pixels)"""
+    """the loss of one head: F.log_softmax_nll, or ``segm_crit`` (an nn.SegmCrossEntropy with class weights,
+    hard-example selection or a region-overlap term - every head selects among, and sums over, its own pixels)"""
     if segm_crit is None:
         return F.log_softmax_nll(logits, target, ignore_index)
     return segm_crit(logits, target)

@@ -2606,8 +2606,114 @@ class _CrossEntropySelect(torch.autograd.Function):
         return d, None, None, None, None
 
 
+def _region_config(who, region, smooth=1.0, classes="present", region_weight=1.0):
+    """(alpha, beta, smooth, all_classes, region_weight) of a region-overlap term; ValueError where the definition
+    ("Losses") has no meaning.  ``region``: "jaccard" | "dice" | ("tversky", alpha, beta)"""
+    if isinstance(region, str) and region in ("jaccard", "dice"):
+        alpha = beta = 1.0 if region == "jaccard" else 0.5
+    elif isinstance(region, (tuple, list)) and len(region) == 3 and region[0] == "tversky":
+        try:
+            alpha, beta = float(region[1]), float(region[2])
+        except (TypeError, ValueError):
+            raise ValueError("{}: (\"tversky\", alpha, beta) needs two numbers (got {!r})".format(who, region))
+    else:
+        raise ValueError("{}: region must be \"jaccard\", \"dice\" or (\"tversky\", alpha, beta) (got {!r})".format(
+            who, region))
+    smooth, region_weight = float(smooth), float(region_weight)
+    if not (alpha >= 0.0 and beta >= 0.0 and alpha + beta > 0.0) or alpha + beta == float("inf"):
+        raise ValueError("{}: alpha, beta >= 0 with alpha + beta > 0 expected (got {}, {})".format(who, alpha, beta))
+    if not 0.0 <= smooth < float("inf"):
+        raise ValueError("{}: smooth must be finite and not negative (got {})".format(who, smooth))
+    if classes not in ("present", "all"):
+        raise ValueError("{}: classes must be \"present\" or \"all\" (got {!r})".format(who, classes))
+    if classes == "all" and smooth == 0.0:
+        raise ValueError("{}: classes=\"all\" needs smooth > 0 (an absent class would be 0 / 0)".format(who))
+    if region_weight != region_weight or abs(region_weight) == float("inf"):
+        raise ValueError("{}: region_weight must be finite (got {})".format(who, region_weight))
+    return alpha, beta, smooth, int(classes == "all"), region_weight
+
+
+class _CrossEntropyRegion(torch.autograd.Function):
+    """nasseg_ce_region_fwd / _bwd.  ``cfg``: the selection of _CrossEntropySelect, or None - the region term alone
+    (no weights, no pixel_loss).  Outputs: the loss (a scalar of its own), and - not differentiable - loss_ce,
+    loss_region, pixel_loss, tau, counts, sums = I | S (2C,), ncls = N | |K| (C + 1,) int64."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, cfg, rcfg):
+        logits = _cl(logits)
+        B, C, H, W = logits.shape
+        target, esz = _label_tensor(target)
+        if tuple(target.shape) != (B, H, W):
+            raise NassegError("cross_entropy_select: target {} does not match logits {}".format(
+                tuple(target.shape), tuple(logits.shape)))
+        with_ce = cfg is not None
+        if weight is not None:
+            require_device(weight)
+            if weight.dtype != torch.float32 or tuple(weight.shape) != (C,):
+                raise NassegError("cross_entropy_select: the class weights must be fp32 of shape ({},) (got {} {})"
+                                  .format(C, weight.dtype, tuple(weight.shape)))
+            weight = weight.contiguous()
+        alpha, beta, smooth, all_classes, region_weight = rcfg
+        dev = logits.device
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        loss_ce = torch.empty((), device=dev, dtype=torch.float32)
+        loss_region = torch.empty((), device=dev, dtype=torch.float32)
+        coef, sums = _vec(logits, 2 * C), _vec(logits, 2 * C)
+        ncls = torch.empty((C + 1,), device=dev, dtype=torch.int64)
+        stats = counts = pixel_loss = tau = None
+        if with_ce:
+            stats = _vec(logits, 2)
+            counts = torch.empty((3,), device=dev, dtype=torch.int64)
+            pixel_loss = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+            tau = _own_scalar(stats, 1)
+        ws = _ws(logits, lib.query("nasseg_ce_region_workspace", C))
+        lib.call(_k("nasseg_ce_region_fwd", logits), ptr(logits), ptr(target), esz, ptr(weight), B * H * W, C,
+                 int(ignore_index), int(with_ce), *(cfg if with_ce else (0, float("inf"), 0, 0.0)), alpha, beta,
+                 smooth, all_classes, region_weight, ptr(loss), ptr(loss_ce), ptr(loss_region), ptr(stats),
+                 ptr(counts), ptr(pixel_loss), ptr(coef), ptr(sums), ptr(ncls), ptr(ws), current_stream())
+        ctx.save_for_backward(logits, target, weight, pixel_loss, stats, coef)
+        ctx.cfg = (esz, int(ignore_index), int(with_ce), region_weight)
+        outs = (loss, loss_ce, loss_region, pixel_loss, tau, counts, sums, ncls)
+        ctx.mark_non_differentiable(*[o for o in outs[1:] if o is not None])
+        return outs
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        logits, target, weight, pixel_loss, stats, coef = ctx.saved_tensors
+        esz, ignore, with_ce, region_weight = ctx.cfg
+        B, C, H, W = logits.shape
+        g = g.to(torch.float32).contiguous().view(1)
+        d = torch.empty_like(logits)
+        lib.call(_k("nasseg_ce_region_bwd", logits), ptr(logits), ptr(target), esz, ptr(weight), ptr(pixel_loss),
+                 ptr(stats), ptr(coef), ptr(g), with_ce, region_weight, B * H * W, C, ignore, ptr(d),
+                 current_stream())
+        return d, None, None, None, None, None
+
+
+def region_overlap_loss(logits, target, region="jaccard", smooth=1.0, classes="present", ignore_index=255,
+                        return_parts=False):
+    """Soft Jaccard / Dice / Tversky loss of (B, C, H, W) logits -> 0-dim loss of its own storage (INTEGRATION.md,
+    "Losses"): the region term of ``cross_entropy_select(region=...)`` alone, bit for bit.
+
+    Over the valid pixels (label != ignore_index, in [0, C)), with q = softmax(logits): I_c = sum q_c [t == c],
+    S_c = sum q_c, N_c = sum [t == c]; T_c = (I_c + smooth) / ((1 - a - b) I_c + a S_c + b N_c + smooth);
+    loss = 1 - mean of T_c over the classes with N_c > 0 (``classes="all"``: over every class; needs smooth > 0);
+    exactly 0 with a zero gradient when there is no such class.  ``region``: "jaccard" (a = b = 1), "dice"
+    (a = b = 0.5) or ("tversky", a, b) with a, b >= 0, a + b > 0.
+    ``return_parts``: (loss, I (C,) fp32, S (C,) fp32, N (C,) int64, |K| 0-dim int64).
+    Deterministic, no host synchronisation: capturable."""
+    rcfg = _region_config("region_overlap_loss", region, smooth, classes)
+    out = _CrossEntropyRegion.apply(logits, target, None, ignore_index, None, rcfg)
+    if not return_parts:
+        return out[0]
+    sums, ncls = out[6], out[7]
+    C = sums.numel() // 2
+    return out[0], sums[:C], sums[C:], ncls[:C], ncls[C]
+
+
 def cross_entropy_select(logits, target, weight=None, ignore_index=255, thresh=None, min_kept=0, keep_fraction=0.0,
-                         return_parts=False):
+                         return_parts=False, region=None, region_weight=1.0, region_smooth=1.0,
+                         region_classes="present"):
     """Class-weighted cross-entropy of (B, C, H, W) logits with online hard-example selection -> 0-dim loss of its
     own storage ("Losses").
 
@@ -2619,10 +2725,18 @@ def cross_entropy_select(logits, target, weight=None, ignore_index=255, thresh=N
     ``thresh=0.7, min_kept=100000``: the usual OHEM cross-entropy; ``keep_fraction=0.25`` alone (with min_kept=1):
     top-k bootstrapping; nothing but ``weight``: torch's ``cross_entropy(weight=..., ignore_index=...)``.
     ``return_parts``: (loss, pixel_loss (B, H, W) with -1 on invalid pixels, tau, counts = [k, n_valid, n_kept]).
-    No host synchronisation: capturable."""
+    ``region`` ("jaccard" | "dice" | ("tversky", a, b); ``region_smooth``, ``region_classes``: the ``smooth`` and
+    ``classes`` of ``region_overlap_loss``): loss = the above + ``region_weight`` * that region term over ALL valid
+    pixels (selection does not thin it, the weights do not enter it), from the same two passes over the logits;
+    ``return_parts`` then also returns the two component losses: (loss, pixel_loss, tau, counts, loss_ce,
+    loss_region).  No host synchronisation: capturable."""
     cfg = _select_config("cross_entropy_select", thresh, min_kept, keep_fraction)
-    out = _CrossEntropySelect.apply(logits, target, weight, ignore_index, cfg)
-    return out if return_parts else out[0]
+    if region is None:
+        out = _CrossEntropySelect.apply(logits, target, weight, ignore_index, cfg)
+        return out if return_parts else out[0]
+    rcfg = _region_config("cross_entropy_select", region, region_smooth, region_classes, region_weight)
+    out = _CrossEntropyRegion.apply(logits, target, weight, ignore_index, cfg, rcfg)
+    return (out[0], out[3], out[4], out[5], out[1], out[2]) if return_parts else out[0]
 
 
 def ohem_threshold(pixel_loss, thresh=None, min_kept=1, keep_fraction=0.0, t_loss=None):

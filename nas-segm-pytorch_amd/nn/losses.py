@@ -34,9 +34,14 @@ class SegmCrossEntropy(nn.Module):
     ``keep_fraction=0.25, min_kept=1``: top-k bootstrapping.  Handed to ``engine.trainer.train_segmenter`` /
     ``train_task0`` as ``segm_crit`` it is the loss of every head; with neither weights nor selection those steps
     run the plain ``F.log_softmax_nll`` as ever.  ``thresh``, ``min_kept`` and ``keep_fraction`` may be changed
-    between steps."""
+    between steps.
+    ``region`` ("jaccard" | "dice" | ("tversky", alpha, beta)): ``region_weight`` times the soft Jaccard / Dice /
+    Tversky loss over all valid pixels is added (``F.region_overlap_loss`` with ``smooth=region_smooth,
+    classes=region_classes``), computed by the same two passes over the logits - the usual ``CE + lambda * Dice``.
+    Such a criterion is the loss of every head even without weights or selection."""
 
-    def __init__(self, weight=None, ignore_index=255, thresh=None, min_kept=0, keep_fraction=0.0):
+    def __init__(self, weight=None, ignore_index=255, thresh=None, min_kept=0, keep_fraction=0.0, region=None,
+                 region_weight=1.0, region_smooth=1.0, region_classes="present"):
         super(SegmCrossEntropy, self).__init__()
         if weight is not None:
             weight = torch.as_tensor(weight)
@@ -49,6 +54,13 @@ class SegmCrossEntropy(nn.Module):
         self.thresh = thresh
         self.min_kept = min_kept
         self.keep_fraction = keep_fraction
+        if region is not None:
+            F._region_config("SegmCrossEntropy", region, region_smooth, region_classes, region_weight)
+            region = tuple(region) if isinstance(region, list) else region
+        self.region = region
+        self.region_weight = region_weight
+        self.region_smooth = region_smooth
+        self.region_classes = region_classes
 
     @property
     def selects(self):
@@ -56,8 +68,11 @@ class SegmCrossEntropy(nn.Module):
 
     def config(self):
         """what a recorded step carries by value or by address (the stepper caches' key, engine/trainer.py)"""
-        return ("ce_sel", id(self.weight) if self.weight is not None else None, self.ignore_index, self.thresh,
-                self.min_kept, self.keep_fraction)
+        cfg = ("ce_sel", id(self.weight) if self.weight is not None else None, self.ignore_index, self.thresh,
+               self.min_kept, self.keep_fraction)
+        if self.region is not None:  # (the term's four values are kernel arguments: recorded by value)
+            cfg = cfg + (("region", self.region, self.region_weight, self.region_smooth, self.region_classes),)
+        return cfg
 
     def prepare(self, device):
         """the weights as the kernels read them: fp32, on ``device`` (a float64 or host vector is converted once,
@@ -69,10 +84,18 @@ class SegmCrossEntropy(nn.Module):
 
     def forward(self, logits, target):
         self.prepare(logits.device)
+        if self.region is None:
+            return F.cross_entropy_select(logits, target, self.weight, self.ignore_index, self.thresh, self.min_kept,
+                                          self.keep_fraction)
         return F.cross_entropy_select(logits, target, self.weight, self.ignore_index, self.thresh, self.min_kept,
-                                      self.keep_fraction)
+                                      self.keep_fraction, region=self.region, region_weight=self.region_weight,
+                                      region_smooth=self.region_smooth, region_classes=self.region_classes)
 
     def extra_repr(self):
-        return "classes={}, ignore_index={}, thresh={}, min_kept={}, keep_fraction={}".format(
+        s = "classes={}, ignore_index={}, thresh={}, min_kept={}, keep_fraction={}".format(
             None if self.weight is None else self.weight.numel(), self.ignore_index, self.thresh, self.min_kept,
             self.keep_fraction)
+        if self.region is not None:
+            s += ", region={!r}, region_weight={}, region_smooth={}, region_classes={!r}".format(
+                self.region, self.region_weight, self.region_smooth, self.region_classes)
+        return s
