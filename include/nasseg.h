@@ -101,9 +101,15 @@ int nasseg_sepconv_fwd(const float* x, const float* wdw, const float* wpw, float
  * pad 1, stride 1 | 2, with statistics rows of z2; nasseg_irdw_bwd: nasseg_dwconv_bwd_bn with z1 rebuilt from x.
  * w1: (C, K, 1, 1) as PyTorch stores it; wdw: packed [9][C] (nasseg_dw_pack_weight; wdw_flipped != 0: its rotated
  * packing); pro(x) = in_act(in_scale * x + in_shift) (null: none).  Rows (workgroups) of statistics [r][2][C] and of
- * weight-gradient partials [r][9][C]: nasseg_irdw_rows(.., backward); 0 = geometry not served (K % 4 == 0, K <= 32,
- * C % 16 == 0, C <= 192: MobileNetV2's 16 -> 96, 24 -> 144, 32 -> 192). */
+ * weight-gradient partials [r][9][C]: nasseg_irdw_rows(.., backward); 0 = geometry not served.  These two kernels serve
+ * K % 4 == 0, 4 <= K <= 32, C % 16 == 0, 16 <= C <= 192, stride 1 | 2 (MobileNetV2's 16 -> 96, 24 -> 144, 32 -> 192
+ * among them).  That is NOT the envelope of the whole form: the expansion's own backward must rebuild z1 as well -
+ * nasseg_conv_pw_bwd_kernel_id(.., z_null = 1) >= 0 - which excludes 32 -> 192, for one.
+ * nasseg_irdw_config: how the two kernels are launched, 1000 waves + 10 groups + kt (workgroups of 64 * waves threads,
+ * waves = 4 | 3 | 2 | 1 by the divisibility of C / 16; grid (rows, groups = C / 16 / waves); kt = 1 | 2 16-wide tiles
+ * of K); 0 = not served.  For tests: together with the stride and the prologue it names the kernel that runs. */
 int64_t nasseg_irdw_rows(int B, int H, int W, int K, int C, int stride, int backward);
+int64_t nasseg_irdw_config(int B, int H, int W, int K, int C, int stride, int backward);
 /* Training-mode BatchNorm statistics of z1 = W1 pro(x) WITHOUT computing z1: z1 is linear in pro(x), so its first and
  * second moments per output channel follow from the K-vector and K x K matrix of moments of pro(x) (one pass over the
  * block's input).  Writes what nasseg_bn_finalize writes for the stored map (to the rounding of the sums).
@@ -256,9 +262,17 @@ int64_t nasseg_conv_pw_bwd_slabs(int B, int H, int W, int K, int N);
 /* 1: nasseg_conv_pw_bwd_bn loads z for this geometry; 0: it rebuilds z = W x from the input tile it stages anyway (the
  * narrow kernel with its weight in LDS: same operand mapping and accumulation order as the forward kernels, the same
  * bits) and z is not read.  A z that is passed must BE the conv's raw output; z == NULL says it was never stored
- * (nasseg_irdw_fwd) and forces the rebuild - an error where no kernel can (K > 32, N > 144).  For measurement tools
- * and tests. */
+ * (nasseg_irdw_fwd) and forces the rebuild - an error where no kernel can: ask nasseg_conv_pw_bwd_kernel_id with
+ * z_null = 1.  For measurement tools and tests. */
 int64_t nasseg_conv_pw_bwd_reads_z(int B, int H, int W, int K, int N);
+/* The kernel nasseg_conv_pw_bwd_bn launches for this geometry under the current nasseg_conv_pw_bwd_rz_min_pixels; -1:
+ * none, the call fails.  10000 + KC: the wide kernel, KC = 2 .. 6 chunks of 64 input channels; otherwise
+ * 100 nt + 10 kt + rz: the narrow kernel holding nt x kt 16-wide tiles of N x K per wave, rz = 1: it rebuilds z,
+ * rz = 0: it loads z.  z_null != 0: what a call with z == NULL launches - a kernel that rebuilds z (rz = 1) or none.
+ * Kernels that rebuild z exist for K <= 32 with N <= 96 (nt <= 6) and for 16 < K <= 32 with 96 < N <= 144 (nt = 9,
+ * kt = 2: 24 -> 144) - not for K <= 16 with N > 96, nor for N > 144.  Whoever drops z (functional._irdw_ok) asks here
+ * first.  The launch itself selects through the same table. */
+int64_t nasseg_conv_pw_bwd_kernel_id(int B, int H, int W, int K, int N, int z_null);
 /* pixels from which nasseg_conv_pw_bwd_bn rebuilds z (where it can: K <= 32, N <= 96): 2^18 initially; 0: every
  * supported geometry, a huge value: none.  v < 0 only queries.  Returns the previous setting. */
 int64_t nasseg_conv_pw_bwd_rz_min_pixels(int64_t v);

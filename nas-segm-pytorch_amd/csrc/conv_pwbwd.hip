@@ -760,8 +760,36 @@ inline PwPlan pw_plan(int64_t M, int N, int K) {
   return p;
 }
 
+// The instantiations, in one place: the launch and the host query (nasseg_conv_pw_bwd_kernel_id) both go through
+// pw_kernel_id, so that what is asked and what runs cannot drift apart.  PW_NARROW: the (NT, KT) of the kernel that
+// loads z; PW_REBUILD: those that also exist in the form that rebuilds it (9, 2 - 24 -> 144 - is slower than loading z
+// by itself, faster than storing z for it: only when z == NULL).  Each entry is three kernels (PRO false | true, DXS).
+#define PW_NARROW(X) \
+  X(2, 1) X(3, 1) X(4, 1) X(6, 1) X(9, 1) X(12, 1) X(2, 2) X(3, 2) X(4, 2) X(6, 2) X(9, 2) X(12, 2) X(2, 4) X(3, 4) X(4, 4) X(6, 4)
+#define PW_REBUILD(X) X(2, 1) X(3, 1) X(4, 1) X(6, 1) X(2, 2) X(3, 2) X(4, 2) X(6, 2) X(9, 2)
+constexpr int kPwIdWide = 10000;  // + KC
+constexpr int pw_id(int nt, int kt, int rz) { return nt * 100 + kt * 10 + rz; }
+// the kernel that serves a plan (include/nasseg.h: nasseg_conv_pw_bwd_kernel_id), -1: none.  z_null: the conv's output
+// was never stored - only a rebuilding kernel will do, whatever the plan prefers.
+inline int pw_kernel_id(const PwPlan& p, bool z_null) {
+  if (!p.ok) return -1;
+  if (p.wide) return (z_null || p.kt > 6) ? -1 : kPwIdWide + (p.kt <= 2 ? 2 : p.kt);
+  const int id = pw_id(p.nt, p.kt, (p.rz || z_null) ? 1 : 0);
+  switch (id) {
+#define X(NT_, KT_) case pw_id(NT_, KT_, 1):
+    PW_REBUILD(X)
+#undef X
+#define X(NT_, KT_) case pw_id(NT_, KT_, 0):
+    PW_NARROW(X)
+#undef X
+      return id;
+    default: return -1;
+  }
+}
+
 template <int NT, int KT, bool RZ = false>
 void pw_launch(const PwArgs& a, int nslab, bool pro, hipStream_t s) {
+  static_assert(!RZ || pw_weight_in_lds(NT, KT), "the kernel rebuilds z only with its weight in LDS: it would read a.z");
   constexpr size_t lds = (size_t)pw_lds_floats(NT, KT, pw_weight_in_lds(NT, KT)) * sizeof(float);
   constexpr size_t lds_dxs = lds + (size_t)kPwTile * pw_lsk(KT) * sizeof(float);  // (+ the raw input tile)
   if (lds_dxs > (64 << 10)) {  // above the default limit of dynamic LDS (per device: set on every launch)
@@ -798,6 +826,13 @@ int64_t nasseg_conv_pw_bwd_slabs(int B, int H, int W, int K, int N) {
 int64_t nasseg_conv_pw_bwd_reads_z(int B, int H, int W, int K, int N) {
   const PwPlan p = pw_plan((int64_t)B * H * W, N, K);
   return (p.ok && p.rz) ? 0 : 1;
+}
+// The kernel nasseg_conv_pw_bwd_bn launches for this geometry, -1: none (the call fails).  10000 + KC: the wide kernel
+// with KC 64-channel chunks of K; else 100 nt + 10 kt + rz: the narrow kernel with nt / kt 16-wide tiles of N / K that
+// loads z (rz 0) or rebuilds it (rz 1).  z_null != 0: what a call with z == NULL launches - a rebuilding kernel or none.
+int64_t nasseg_conv_pw_bwd_kernel_id(int B, int H, int W, int K, int N, int z_null) {
+  if (B <= 0 || H <= 0 || W <= 0) return -1;
+  return pw_kernel_id(pw_plan((int64_t)B * H * W, N, K), z_null != 0);
 }
 // maps of at least this many pixels have z rebuilt (where the kernel can: K <= 32, N <= 96): 2^18 initially - below,
 // the launches are not bound by their bytes and the extra MFMAs lose (32 -> 32 at 4x128x256: 15.8 -> 16.9 us); 0: every
@@ -842,14 +877,13 @@ int NASSEG_FN(conv_pw_bwd_bn)(const act_t* x, const act_t* g, const act_t* z, co
                  "conv_pw_bwd_bn: missing BatchNorm tensors");
   NASSEG_REQUIRE(B > 0 && H > 0 && W > 0, "conv_pw_bwd_bn: bad geometry");
   const int64_t M = (int64_t)B * H * W;
-  PwPlan p = pw_plan(M, N, K);
+  const PwPlan p = pw_plan(M, N, K);
   NASSEG_REQUIRE(p.ok, "conv_pw_bwd_bn: no fused kernel for K=%d N=%d", K, N);
-  if (!z) {
-    // the conv's output was never stored (nasseg_irdw_fwd): the kernel must rebuild it, whatever the plan prefers
-    NASSEG_REQUIRE(!p.wide && p.kt <= 2 && p.nt <= 9 && pw_weight_in_lds(p.nt, p.kt),
-                   "conv_pw_bwd_bn: z == NULL, but K=%d N=%d has no kernel that rebuilds z", K, N);
-    p.rz = 1;
-  }
+  // (z == NULL: the conv's output was never stored - nasseg_irdw_fwd - and only a kernel that rebuilds it will do)
+  const int id = pw_kernel_id(p, !z);
+  NASSEG_REQUIRE(z || id >= 0, "conv_pw_bwd_bn: z == NULL, but K=%d N=%d has no kernel that rebuilds z", K, N);
+  if (id < 0)
+    return nasseg_fail(NASSEG_ERR_UNSUPPORTED, "conv_pw_bwd_bn: no kernel for nt=%d kt=%d rz=%d", p.nt, p.kt, p.rz);
   PwArgs a = {};
   a.x = x; a.g = g; a.z = z; a.dx = dx; a.partial = ws; a.wb = wb;
   a.in_scale = in_scale; a.in_shift = in_shift; a.in_act = in_act;
@@ -878,11 +912,14 @@ int NASSEG_FN(conv_pw_bwd_bn)(const act_t* x, const act_t* g, const act_t* z, co
     if (pro) hipLaunchKernelGGL((conv_pw_bwd_wide_kernel<KC_, true>), dim3(p.nslab), dim3(256), ldsw2, s, a); \
     else hipLaunchKernelGGL((conv_pw_bwd_wide_kernel<KC_, false>), dim3(p.nslab), dim3(256), ldsw2, s, a);    \
   } while (0)
-    if (p.kt <= 2) PW_WIDE(2);
-    else if (p.kt == 3) PW_WIDE(3);
-    else if (p.kt == 4) PW_WIDE(4);
-    else if (p.kt == 5) PW_WIDE(5);
-    else PW_WIDE(6);
+    switch (id - kPwIdWide) {
+      case 2: PW_WIDE(2); break;
+      case 3: PW_WIDE(3); break;
+      case 4: PW_WIDE(4); break;
+      case 5: PW_WIDE(5); break;
+      case 6: PW_WIDE(6); break;
+      default: return nasseg_fail(NASSEG_ERR_UNSUPPORTED, "conv_pw_bwd_bn: no kernel with id %d", id);
+    }
 #undef PW_WIDE
     NASSEG_LAUNCH_CHECK("conv_pw_bwd_wide_kernel");
     if (!dw) return NASSEG_OK;
@@ -891,16 +928,15 @@ int NASSEG_FN(conv_pw_bwd_bn)(const act_t* x, const act_t* g, const act_t* z, co
     const int dims_w[5] = {p.nslab, 1, N, K, 0};
     return nasseg_wgrad_finalize_many(1, parts_w, outs_w, dims_w, stream);
   }
-#define PW_CASE(NT_, KT_) if (p.nt == NT_ && p.kt == KT_ && p.rz) pw_launch<NT_, KT_, true>(a, p.nslab, pro, s); else
-  PW_CASE(2, 1) PW_CASE(3, 1) PW_CASE(4, 1) PW_CASE(6, 1) PW_CASE(2, 2) PW_CASE(3, 2) PW_CASE(4, 2) PW_CASE(6, 2)
-  PW_CASE(9, 2)  // (24 -> 144: slower than loading z by itself, faster than storing z for it - only when z == NULL)
-#undef PW_CASE
-#define PW_CASE(NT_, KT_) if (p.nt == NT_ && p.kt == KT_) pw_launch<NT_, KT_>(a, p.nslab, pro, s); else
-  PW_CASE(2, 1) PW_CASE(3, 1) PW_CASE(4, 1) PW_CASE(6, 1) PW_CASE(9, 1) PW_CASE(12, 1)
-  PW_CASE(2, 2) PW_CASE(3, 2) PW_CASE(4, 2) PW_CASE(6, 2) PW_CASE(9, 2) PW_CASE(12, 2)
-  PW_CASE(2, 4) PW_CASE(3, 4) PW_CASE(4, 4) PW_CASE(6, 4)
-  return nasseg_fail(NASSEG_ERR_UNSUPPORTED, "conv_pw_bwd_bn: no kernel for nt=%d kt=%d", p.nt, p.kt);
-#undef PW_CASE
+  switch (id) {
+#define X(NT_, KT_) case pw_id(NT_, KT_, 1): pw_launch<NT_, KT_, true>(a, p.nslab, pro, s); break;
+    PW_REBUILD(X)
+#undef X
+#define X(NT_, KT_) case pw_id(NT_, KT_, 0): pw_launch<NT_, KT_>(a, p.nslab, pro, s); break;
+    PW_NARROW(X)
+#undef X
+    default: return nasseg_fail(NASSEG_ERR_UNSUPPORTED, "conv_pw_bwd_bn: no kernel with id %d", id);
+  }
   NASSEG_LAUNCH_CHECK("conv_pw_bwd_kernel");
   if (!dw) return NASSEG_OK;
   const float* parts[1] = {ws};

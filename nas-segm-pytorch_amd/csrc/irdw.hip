@@ -728,6 +728,13 @@ int64_t nasseg_irdw_rows(int B, int H, int W, int K, int C, int stride, int back
   const IrPlan p = ir_plan(B, H, W, K, C, stride, backward != 0);
   return p.ok ? p.grid : 0;
 }
+// how nasseg_irdw_fwd / nasseg_irdw_bwd are launched for this geometry: 1000 waves + 10 groups + kt - workgroups of
+// 64 * waves threads, grid (rows, groups), kt 16-wide tiles of K - with the stride and the prologue that is the kernel
+// that runs; 0: geometry not served
+int64_t nasseg_irdw_config(int B, int H, int W, int K, int C, int stride, int backward) {
+  const IrPlan p = ir_plan(B, H, W, K, C, stride, backward != 0);
+  return p.ok ? 1000 * p.waves + 10 * p.groups + p.kt : 0;
+}
 #endif
 
 #if NASSEG_FP32_ONLY

@@ -957,16 +957,22 @@ def _irdw_ok(ops, i, weights, cur, pend, needs_in_grad, need_w, training):
     if not (needs_in_grad and need_w):  # (the one-kernel backwards need both gradients)
         return False
     B, _, H, W = cur.shape
-    if B * H * W < _IRDW_MIN_PIXELS or not (N > K and K % 4 == 0):
-        return False
-    if not ((stride2 == 1 and N <= 144) or (stride2 == 2 and K <= _IRDW_S2_MAX_K)):
-        return False
     if pend is not None and pend[0] is None and pend[1] is None and not pend[2]:
         return False
-    return (lib.query("nasseg_irdw_rows", B, H, W, K, N, stride2, 0) > 0
-            and lib.query("nasseg_irdw_rows", B, H, W, K, N, stride2, 1) > 0
-            and lib.query("nasseg_conv_pw_bwd_slabs", B, H, W, K, N) > 0
-            and lib.query("nasseg_dwconv_bwd_bn_rows", B, N, H, W, 3, stride2, 1, 1) > 0)
+    return _irdw_geometry_ok(B, H, W, K, N, stride2)
+
+
+def _irdw_geometry_ok(B, H, W, K, N, stride):
+    """the part of _irdw_ok that is a function of the geometry alone: the form pays there AND every kernel involved
+    exists - the forward drops z1 only where the expansion's backward has a kernel that rebuilds it (z == NULL)"""
+    if B * H * W < _IRDW_MIN_PIXELS or not (N > K and K % 4 == 0):
+        return False
+    if not ((stride == 1 and N <= 144) or (stride == 2 and K <= _IRDW_S2_MAX_K)):
+        return False
+    return (lib.query("nasseg_irdw_config", B, H, W, K, N, stride, 0) > 0
+            and lib.query("nasseg_irdw_config", B, H, W, K, N, stride, 1) > 0
+            and lib.query("nasseg_conv_pw_bwd_kernel_id", B, H, W, K, N, 1) >= 0
+            and lib.query("nasseg_dwconv_bwd_bn_rows", B, N, H, W, 3, stride, 1, 1) > 0)
 
 
 # A chain's config (conv_chain): in_act0 = activation applied to the input on load, one _ChainOp per conv, the CALLER's

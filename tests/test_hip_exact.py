@@ -868,17 +868,49 @@ def test_depthwise_backward_between_batchnorms_is_exact(geom, act, tie, dtype):
     E.assert_bitwise(rows_sum64(part, rows, 2 * C), sums_ref, "rows of the BatchNorm in front")
 
 
-@pytest.mark.parametrize("geom", [
+_T, _E = (2, 8, 16), (3, 9, 11)  # 256 pixels (a power of two: training-mode BatchNorm) / 297 (a ragged last tile)
+PW_BWD_CASES = [
     # train, (B, H, W, K, N), prologue
     (1, (2, 4, 8, 16, 96), 0), (1, (4, 16, 16, 24, 144), 2), (1, (2, 16, 16, 32, 32), 1), (0, (1, 31, 33, 32, 192), 2),
-    (0, (3, 9, 11, 24, 64), 0), (1, (1, 1, 1, 16, 32), 0), (0, (2, 16, 20, 224, 64), 1), (1, (2, 8, 8, 128, 32), 0)],
-    ids=lambda g: "B{}_{}x{}_K{}N{}_pro{}".format(*g[1], g[2]))
+    (0, (3, 9, 11, 24, 64), 0), (1, (1, 1, 1, 16, 32), 0), (0, (2, 16, 20, 224, 64), 1), (1, (2, 8, 8, 128, 32), 0),
+    # Every instantiation of csrc/conv_pwbwd.hip (tests/test_dispatch_host.py holds this list to that), on the smallest
+    # maps with several tiles and slabs.  The narrow kernel holds nt x kt 16-wide tiles of N x K per wave; per (nt, kt)
+    # one channel pair with a prologue (the PRO and the DXS kernels) and one without, none a multiple of 16:
+    # (2, 1), (3, 1), (4, 1), (6, 1), (9, 1), (12, 1)
+    (1, _T + (8, 20), 1), (1, _T + (8, 36), 2), (0, _E + (4, 40), 0), (1, _T + (12, 52), 1), (0, _E + (16, 56), 0),
+    (0, _E + (12, 84), 2), (1, _T + (16, 128), 2), (0, _E + (8, 112), 0), (0, _E + (12, 148), 1), (1, _T + (16, 180), 0),
+    # (2, 2), (3, 2), (4, 2), (6, 2), (9, 2), (12, 2)
+    (0, _E + (28, 20), 0), (1, _T + (20, 36), 1), (0, _E + (32, 44), 0), (1, _T + (28, 52), 2), (1, _T + (20, 68), 1),
+    (0, _E + (24, 92), 0), (0, _E + (20, 132), 0), (0, _E + (20, 180), 0),
+    # (2, 4), (3, 4), (4, 4), (6, 4)
+    (1, _T + (36, 20), 2), (0, _E + (64, 28), 0), (0, _E + (40, 36), 1), (1, _T + (52, 44), 0), (1, _T + (52, 52), 1),
+    (0, _E + (36, 60), 0), (0, _E + (60, 84), 2), (1, _T + (36, 68), 0),
+    # the wide kernel, 2 .. 6 chunks of 64 input channels, its four waves splitting N: one N tile (three waves idle),
+    # two, three and four
+    (1, _T + (68, 12), 1), (0, _E + (132, 12), 2), (1, _T + (164, 52), 0), (0, _E + (196, 36), 0), (1, _T + (260, 20), 1),
+    (0, _E + (320, 64), 0), (0, _E + (324, 52), 2), (1, _T + (384, 28), 0)]
+
+
+def pw_bwd_kernel_ids(lib, geom):
+    """{(id, prologue != 0)}: the kernels nasseg_conv_pw_bwd_bn launches over the test below for one case - z loaded
+    and z rebuilt where the plan can, and the call with z == NULL where a kernel serves it"""
+    _, (B, H, W, K, N), pro = geom
+    ids = set()
+    for rz in (0, HUGE):
+        with knobs(conv_pw_bwd_rz_min_pixels=rz):
+            ids.add(lib.query("nasseg_conv_pw_bwd_kernel_id", B, H, W, K, N, 0))
+            ids.add(lib.query("nasseg_conv_pw_bwd_kernel_id", B, H, W, K, N, 1))
+    return {(i, bool(pro)) for i in ids if i >= 0}
+
+
+@pytest.mark.parametrize("geom", PW_BWD_CASES, ids=lambda g: "B{}_{}x{}_K{}N{}_pro{}".format(*g[1], g[2]))
 @pytest.mark.parametrize("act,tie", ACT_TIE)
 @pytest.mark.parametrize("rz", [0, HUGE], ids=["rebuild_z", "load_z"])
 @pytest.mark.parametrize("dtype", DTYPES, ids=_dt)
 def test_pointwise_backward_with_bn_in_one_kernel_is_exact(geom, act, tie, rz, dtype):
     """nasseg_conv_pw_bwd_bn: dx, dw, the partial rows finished by nasseg_wgrad_finalize_many (dw == NULL), z == NULL
-    (forces the rebuild where a kernel can), dx_res, dx_stats - z loaded and z rebuilt"""
+    (forces the rebuild where nasseg_conv_pw_bwd_kernel_id names a kernel that can, an error elsewhere), dx_res,
+    dx_stats - z loaded and z rebuilt"""
     f = F()
     lib, ptr = f.lib, f.ptr
     train, (B, H, W, K, N), pro = geom
@@ -940,7 +972,10 @@ def test_pointwise_backward_with_bn_in_one_kernel_is_exact(geom, act, tie, rz, d
         parts, outs = (ctypes.c_void_p * 1)(ptr(ws)), (ctypes.c_void_p * 1)(ptr(dw))
         lib.call("nasseg_wgrad_finalize_many", 1, parts, outs, (ctypes.c_int * 5)(nsl, 1, N, K, 0), st)
         E.assert_bitwise(dw, dw_ref, "nasseg_wgrad_finalize_many over the partial rows")
-        if K <= 32 and N <= 144:
+        kid, kid_null = [lib.query("nasseg_conv_pw_bwd_kernel_id", B, H, W, K, N, zn) for zn in (0, 1)]
+        assert kid >= 0 and (kid < 10000 and kid % 10 == 1) == (not reads_z)  # (the launch asks the same table)
+        if kid_null >= 0:
+            assert kid_null < 10000 and kid_null % 10 == 1  # (a kernel that rebuilds z)
             call(None, torch.full((N, K, 1, 1), NAN, device=DEV), 0, what="z == NULL")
         else:
             with pytest.raises(RuntimeError):  # (no kernel can rebuild z there)
@@ -1015,7 +1050,14 @@ def test_sepconv_stage_is_exact(case, pro, tie, dtype):
 IRDW_CASES = [
     # train of the BatchNorm behind the depthwise conv (then B * Ho * Wo is a power of two), (B, K, C, H, W, stride)
     (1, (2, 16, 96, 15, 31, 2)), (1, (2, 24, 144, 8, 16, 1)), (0, (1, 32, 192, 19, 33, 1)), (0, (2, 24, 144, 17, 23, 2)),
-    (0, (1, 16, 96, 1, 1, 1)), (1, (1, 8, 48, 16, 64, 1)), (0, (2, 4, 16, 9, 29, 2))]
+    (0, (1, 16, 96, 1, 1, 1)), (1, (1, 8, 48, 16, 64, 1)), (0, (2, 4, 16, 9, 29, 2)),
+    # Off MobileNetV2's expansions (tests/test_dispatch_host.py holds this list to every launch shape of csrc/irdw.hip):
+    # a workgroup is 64 * waves threads, waves = 4 | 3 | 2 | 1 by the divisibility of C / 16, the grid (rows, groups).
+    # Two waves with one group and with five; one wave with five groups and with seven; four waves with one group and
+    # with two - each at both strides, K <= 16 and K > 16; two chunks of rows and two strips of columns in either
+    # direction (16 x 16 and 9 x 17 at stride 1, 31 x 31 and 17 x 33 at stride 2)
+    (1, (1, 8, 32, 16, 16, 1)), (0, (1, 20, 160, 17, 33, 2)), (0, (2, 16, 80, 9, 17, 1)), (1, (1, 20, 112, 31, 31, 2)),
+    (1, (1, 24, 64, 31, 31, 2)), (0, (2, 16, 128, 9, 17, 1))]
 _irdw_id = lambda g: "B{}_{}to{}_{}x{}_s{}".format(*g[1])  # noqa: E731
 
 
@@ -1122,7 +1164,8 @@ def _ulps(got, ref64):
 
 
 @pytest.mark.parametrize("geom", [(2, 16, 96, 8, 16), (1, 24, 144, 16, 32), (4, 32, 192, 4, 4), (1, 8, 48, 1, 2),
-                                  (2, 4, 16, 32, 64)], ids=lambda g: "B{}_{}to{}_{}x{}".format(*g))
+                                  (2, 4, 16, 32, 64), (1, 20, 160, 16, 16), (2, 12, 80, 8, 16)],
+                         ids=lambda g: "B{}_{}to{}_{}x{}".format(*g))
 @pytest.mark.parametrize("pro,tie", [(0, True), (1, True), (2, False)])
 @pytest.mark.parametrize("dtype", DTYPES, ids=_dt)
 def test_irdw_statistics_from_the_moments_of_the_input(geom, pro, tie, dtype):
