@@ -508,6 +508,47 @@ int nasseg_ce_region_bwd(const float* logits, const void* target, int elem_size,
                          int with_ce, double region_weight, int64_t P, int C, int ignore, float* dlogits,
                          void* stream);
 
+/* Lovasz-Softmax term (Berman, Triggs, Blaschko, CVPR 2018; absent from the reference): the convex extension of the
+ * Jaccard loss, the surrogate of the mean IoU the reward is built from.  Logits [P][C], labels [P]; pixel p is valid
+ * iff its label t != ignore and 0 <= t < C; n = valid pixels, y_pc = [t_p == c], N_c = sum_p y_pc.
+ * q_p = softmax(x_p) in fp32 exactly as the region term and nasseg_ce_fwd compute it (the same max, the same expf
+ * values, the same 1 / s): a function of the pixel's own row alone.
+ *   errors  e_pc = fabsf(y_pc - q_pc) in fp32 on valid pixels (written as -1 on the others)
+ *   order   per class c: the valid pixels by e_pc DESCENDING on the fp32 values, ties by ASCENDING flat index p - a
+ *           total order, so every result is a function of the inputs alone.  Position i = 1 .. n; F_i = foreground
+ *           (y = 1) pixels among the first i, B_i = i - F_i.
+ *   Lovasz gradient of position i, in double from those integers, U = N_c + B_i:
+ *           foreground: g = 1 / U;  background: g = (N_c - F_i) / ((U - 1) U), and g = 1 where U - 1 = 0 (N_c = 0,
+ *           i = 1) - that is J_i - J_(i-1) with J_i = 1 - (N_c - F_i) / (N_c + B_i), J_0 = 0
+ *   loss_c = sum_i e_(i) g_i in double, per-workgroup partials added in index order (no float atomics)
+ *   K = {c : N_c > 0} (all_classes != 0: every class; an absent class then costs max_p q_pc, by the formulas alone)
+ *   L = sum_{c in K} loss_c / |K|;  exactly 0 with an exactly zero gradient when n = 0
+ * Gradient, the order and the g held constant: G_pc = s_pc g_(c, rank(p)) / |K|, s = -1 on foreground and +1 on
+ * background (by label, also at e = 0), G_pc = 0 for c outside K and on invalid pixels;
+ *   dL/dx_pj = q_pj (G_pj - sum_c G_pc q_pc) on valid pixels, exact zeros on all others.
+ * nasseg_lovasz_coef is the sort-and-scan half over ANY non-negative fp32 error array [P][C] (validity from the
+ * labels): loss = L, coef = G [P][C], rank [P][C] = the 0-based position of every valid pixel in its class's order
+ * (-1 on invalid pixels and for classes outside K; rank may be null), ncls = {N_c} | |K| (int64 [C + 1]).
+ * nasseg_lovasz_fwd makes the errors from the logits, then runs the above;
+ *   loss = base_loss[0] + lovasz_weight * L (base_loss null: lovasz_weight * L), loss_lovasz = L (may be null).
+ * nasseg_lovasz_bwd: dlogits = gscale * lovasz_weight * q (G - sum_c G_c q_c), q recomputed from the logits
+ * (gscale: device scalar, null = 1); accumulate != 0: added onto what dlogits holds - the gradient nasseg_ce_sel_bwd /
+ * nasseg_ce_region_bwd has just written there - instead of written (invalid pixels are then left as they are).
+ * The order comes from a stable least-significant-digit radix sort on the device (4 passes of 8 bits over the
+ * complemented bit pattern, classes as grid rows, ranks from wave ballots - never from the arrival order of
+ * atomics), F_i from an integer scan.  The caller owns all memory; no allocation, no host synchronisation, no float
+ * atomics, a launch geometry that depends on (P, C) alone: capturable, and bit-reproducible.
+ * 2 <= C <= 65535, P * C < 2^31.  ws: nasseg_lovasz_workspace(P, C) 4-byte words, 8-byte aligned (0: bad shape). */
+int64_t nasseg_lovasz_workspace(int64_t P, int C);
+int nasseg_lovasz_coef(const float* errors, const void* target, int elem_size, int64_t P, int C, int ignore,
+                       int all_classes, float* loss, float* coef, int* rank, int64_t* ncls, float* ws, void* stream);
+int nasseg_lovasz_fwd(const float* logits, const void* target, int elem_size, int64_t P, int C, int ignore,
+                      int all_classes, double lovasz_weight, const float* base_loss, float* loss, float* loss_lovasz,
+                      float* errors, float* coef, int* rank, int64_t* ncls, float* ws, void* stream);
+int nasseg_lovasz_bwd(const float* logits, const void* target, int elem_size, const float* coef, const float* gscale,
+                      double lovasz_weight, int accumulate, int64_t P, int C, int ignore, float* dlogits,
+                      void* stream);
+
 /* berHu loss of the depth head (BASELINE config 5; absent from the reference - Laina et al.
  * 2016 eq. 2, "parity unpinned") */
 int nasseg_berhu_fwd(const float* pred, const float* target, int64_t n, float* out, float* ws,
@@ -792,6 +833,13 @@ int nasseg_bf16_ce_region_bwd(const nasseg_bf16_t* logits, const void* target, i
                               const float* pixel_loss, const float* stats, const float* coef, const float* gscale,
                               int with_ce, double region_weight, int64_t P, int C, int ignore,
                               nasseg_bf16_t* dlogits, void* stream);
+int nasseg_bf16_lovasz_fwd(const nasseg_bf16_t* logits, const void* target, int elem_size, int64_t P, int C,
+                           int ignore, int all_classes, double lovasz_weight, const float* base_loss, float* loss,
+                           float* loss_lovasz, float* errors, float* coef, int* rank, int64_t* ncls, float* ws,
+                           void* stream);
+int nasseg_bf16_lovasz_bwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* coef,
+                           const float* gscale, double lovasz_weight, int accumulate, int64_t P, int C, int ignore,
+                           nasseg_bf16_t* dlogits, void* stream);
 int nasseg_bf16_berhu_fwd(const nasseg_bf16_t* pred, const nasseg_bf16_t* target, int64_t n, float* out, float* ws,
                      void* stream);
 int nasseg_bf16_berhu_bwd(const nasseg_bf16_t* pred, const nasseg_bf16_t* target, const float* stats,

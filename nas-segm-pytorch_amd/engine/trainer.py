@@ -86,13 +86,14 @@ _MAPPED_CRITS = weakref.WeakKeyDictionary()  # nn.NLLLoss with class weights -> 
 
 def _segm_crit(segm_crit, device=None):
     """the criterion that replaces the plain softmax/NLL of every head, else None (F.log_softmax_nll with the
-    criterion's ``ignore_index``, as ever).  An nn.SegmCrossEntropy with class weights, hard-example selection or a
-    region-overlap term is that criterion itself; an nn.NLLLoss (nn.NLLLoss2d where torch has it) with ``weight`` and
+    criterion's ``ignore_index``, as ever).  An nn.SegmCrossEntropy with class weights, hard-example selection, a
+    region-overlap term or a Lovasz-Softmax term is that criterion itself; an nn.NLLLoss (nn.NLLLoss2d where torch has it) with ``weight`` and
     mean reduction - the one-line change to src/main_search.py:435 - is mapped to the equivalent SegmCrossEntropy,
     once per criterion and weight tensor.  ``device``: the weights are made fp32 there now (not inside a step being recorded)."""
     crit = None
     if isinstance(segm_crit, SegmCrossEntropy):
-        if segm_crit.weight is not None or segm_crit.selects or segm_crit.region is not None:
+        if (segm_crit.weight is not None or segm_crit.selects or segm_crit.region is not None
+                or segm_crit.lovasz_weight is not None):
             crit = segm_crit
     elif (isinstance(segm_crit, nn.NLLLoss) and segm_crit.weight is not None
           and getattr(segm_crit, "reduction", "mean") == "mean"):

@@ -2696,6 +2696,193 @@ class _CrossEntropyRegion(torch.autograd.Function):
         return d, None, None, None, None, None
 
 
+def _lovasz_config(who, lovasz_weight=1.0, classes="present"):
+    """(lovasz_weight, all_classes) of a Lovasz-Softmax term; ValueError where the definition (INTEGRATION.md,
+    "Losses") has no meaning"""
+    try:
+        lovasz_weight = float(lovasz_weight)
+    except (TypeError, ValueError):
+        raise ValueError("{}: lovasz_weight must be a number (got {!r})".format(who, lovasz_weight))
+    if lovasz_weight != lovasz_weight or abs(lovasz_weight) == float("inf"):
+        raise ValueError("{}: lovasz_weight must be finite (got {})".format(who, lovasz_weight))
+    if classes not in ("present", "all"):
+        raise ValueError("{}: lovasz_classes must be \"present\" or \"all\" (got {!r})".format(who, classes))
+    return lovasz_weight, int(classes == "all")
+
+
+def _lovasz_forward(logits, target, esz, ignore_index, lcfg, base, want_parts):
+    """nasseg_lovasz_fwd on checked inputs -> (loss, L_lovasz, errors, G, rank, ncls); the errors and the ranks are
+    kept only for ``want_parts`` (the errors are the launch's scratch otherwise, the ranks are not written)"""
+    B, C, H, W = logits.shape
+    dev = logits.device
+    lovasz_weight, all_classes = lcfg
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    llov = torch.empty((), device=dev, dtype=torch.float32)
+    errors = torch.empty((B, H, W, C), device=dev, dtype=torch.float32)
+    coef = torch.empty((B, H, W, C), device=dev, dtype=torch.float32)
+    rank = torch.empty((B, H, W, C), device=dev, dtype=torch.int32) if want_parts else None
+    ncls = torch.empty((C + 1,), device=dev, dtype=torch.int64)
+    ws = _ws(logits, lib.query("nasseg_lovasz_workspace", B * H * W, C))
+    lib.call(_k("nasseg_lovasz_fwd", logits), ptr(logits), ptr(target), esz, B * H * W, C, int(ignore_index),
+             all_classes, lovasz_weight, ptr(base), ptr(loss), ptr(llov), ptr(errors), ptr(coef), ptr(rank), ptr(ncls),
+             ptr(ws), current_stream())
+    return loss, llov, (errors if want_parts else None), coef, rank, ncls
+
+
+def _lovasz_backward(logits, target, esz, ignore, coef, g, lovasz_weight, accumulate, d):
+    B, C, H, W = logits.shape
+    lib.call(_k("nasseg_lovasz_bwd", logits), ptr(logits), ptr(target), esz, ptr(coef), ptr(g), lovasz_weight,
+             int(accumulate), B * H * W, C, ignore, ptr(d), current_stream())
+    return d
+
+
+class _LovaszSoftmax(torch.autograd.Function):
+    """nasseg_lovasz_fwd / _bwd alone.  Outputs: the loss (a scalar of its own), and - not differentiable, None
+    unless ``want_parts`` - errors (B, H, W, C), rank (B, H, W, C) int32, ncls = N | |K| (C + 1,) int64.  Kept for
+    backward beyond the logits and labels: G, one fp32 [P][C] tensor."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, lcfg, want_parts):
+        logits = _cl(logits)
+        B, C, H, W = logits.shape
+        target, esz = _label_tensor(target)
+        if tuple(target.shape) != (B, H, W):
+            raise NassegError("lovasz_softmax_loss: target {} does not match logits {}".format(
+                tuple(target.shape), tuple(logits.shape)))
+        loss, _, errors, coef, rank, ncls = _lovasz_forward(logits, target, esz, ignore_index, (1.0, lcfg[1]), None,
+                                                            want_parts)
+        ctx.save_for_backward(logits, target, coef)
+        ctx.cfg = (esz, int(ignore_index))
+        if not want_parts:
+            return loss, None, None, None
+        ctx.mark_non_differentiable(errors, rank, ncls)
+        return loss, errors, rank, ncls
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        logits, target, coef = ctx.saved_tensors
+        esz, ignore = ctx.cfg
+        g = g.to(torch.float32).contiguous().view(1)
+        d = _lovasz_backward(logits, target, esz, ignore, coef, g, 1.0, False, torch.empty_like(logits))
+        return d, None, None, None, None
+
+
+def lovasz_softmax_loss(logits, target, classes="present", ignore_index=255, return_parts=False):
+    """Lovasz-Softmax loss (Berman, Triggs, Blaschko, CVPR 2018) of (B, C, H, W) logits -> 0-dim loss of its own
+    storage ("Losses"): the Lovasz term of ``cross_entropy_select(lovasz_weight=...)`` alone, bit for
+    bit.
+
+    Over the valid pixels (label != ignore_index, in [0, C)), with q = softmax(logits): e_pc = |[t_p == c] - q_pc| in
+    fp32; per class the pixels sorted by e descending, ties by ascending pixel index; loss_c = sum_i e_(i) g_i with
+    g the Lovasz gradient of the Jaccard loss (in double, from integer counts); loss = mean of loss_c over the classes
+    with a pixel (``classes="all"``: over every class); exactly 0 with a zero gradient when no pixel is valid.  The
+    order and g are constants in backward.
+    ``return_parts``: (loss, errors (B, H, W, C) fp32 with -1 on invalid pixels, rank (B, H, W, C) int32: the 0-based
+    position of each valid pixel in its class's order (-1 on invalid pixels and for classes that do not take part),
+    N (C,) int64, |K| 0-dim int64).
+    The sort runs on the device (a stable radix sort): deterministic, no host synchronisation: capturable."""
+    lcfg = _lovasz_config("lovasz_softmax_loss", 1.0, classes)
+    loss, errors, rank, ncls = _LovaszSoftmax.apply(logits, target, ignore_index, lcfg, bool(return_parts))
+    if not return_parts:
+        return loss
+    C = ncls.numel() - 1
+    return loss, errors, rank, ncls[:C], ncls[C]
+
+
+def lovasz_from_errors(errors, target, classes="present", ignore_index=255):
+    """The sort-and-scan half of ``lovasz_softmax_loss`` over any non-negative fp32 ``errors`` (..., C) with labels
+    ``target`` (...) -> (loss 0-dim, coef = G fp32 like ``errors``, rank int32 like ``errors``, N (C,) int64, |K| 0-dim
+    int64); not differentiable.  loss = mean over K of sum_i e_(i) g_i, G_pc = -+ g / |K| ("Losses")."""
+    _, all_classes = _lovasz_config("lovasz_from_errors", 1.0, classes)
+    require_device(errors)
+    target, esz = _label_tensor(target)
+    if errors.dtype != torch.float32 or errors.dim() < 2 or tuple(errors.shape[:-1]) != tuple(target.shape):
+        raise NassegError("lovasz_from_errors: fp32 errors (..., C) and labels (...) expected (got {} {} and {})".format(
+            errors.dtype, tuple(errors.shape), tuple(target.shape)))
+    errors = errors.detach().contiguous()
+    C = errors.shape[-1]
+    P = errors.numel() // max(C, 1)
+    dev = errors.device
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    coef = torch.empty_like(errors)
+    rank = torch.empty(errors.shape, device=dev, dtype=torch.int32)
+    ncls = torch.empty((C + 1,), device=dev, dtype=torch.int64)
+    ws = _ws(errors, lib.query("nasseg_lovasz_workspace", P, C))
+    lib.call("nasseg_lovasz_coef", ptr(errors), ptr(target), esz, P, C, int(ignore_index), all_classes, ptr(loss),
+             ptr(coef), ptr(rank), ptr(ncls), ptr(ws), current_stream())
+    return loss, coef, rank, ncls[:C], ncls[C]
+
+
+class _CrossEntropyLovasz(torch.autograd.Function):
+    """The cross-entropy of _CrossEntropySelect (``rcfg`` None) or _CrossEntropyRegion, by the very launches of those
+    nodes, plus ``lovasz_weight`` times the Lovasz-Softmax term: one node, one dlogits.  nasseg_lovasz_fwd adds its
+    term onto the base loss on the device; nasseg_lovasz_bwd adds its gradient onto what the base's backward launch
+    has just written.  Outputs: the loss (a scalar of its own), and - not differentiable - pixel_loss, tau, counts,
+    loss_ce, loss_region (None without a region term), loss_lovasz."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, cfg, rcfg, lcfg):
+        logits = _cl(logits)
+        B, C, H, W = logits.shape
+        target, esz = _label_tensor(target)
+        if tuple(target.shape) != (B, H, W):
+            raise NassegError("cross_entropy_select: target {} does not match logits {}".format(
+                tuple(target.shape), tuple(logits.shape)))
+        if weight is not None:
+            require_device(weight)
+            if weight.dtype != torch.float32 or tuple(weight.shape) != (C,):
+                raise NassegError("cross_entropy_select: the class weights must be fp32 of shape ({},) (got {} {})"
+                                  .format(C, weight.dtype, tuple(weight.shape)))
+            weight = weight.contiguous()
+        dev = logits.device
+        base = torch.empty((), device=dev, dtype=torch.float32)
+        stats = _vec(logits, 2)
+        counts = torch.empty((3,), device=dev, dtype=torch.int64)
+        pixel_loss = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+        rcoef = loss_region = None
+        if rcfg is None:
+            ws = _ws(logits, lib.query("nasseg_ce_sel_workspace"))
+            lib.call(_k("nasseg_ce_sel_fwd", logits), ptr(logits), ptr(target), esz, ptr(weight), B * H * W, C,
+                     int(ignore_index), *cfg, ptr(base), ptr(stats), ptr(counts), ptr(pixel_loss), ptr(ws),
+                     current_stream())
+            loss_ce = base
+        else:
+            alpha, beta, smooth, all_classes, region_weight = rcfg
+            loss_ce = torch.empty((), device=dev, dtype=torch.float32)
+            loss_region = torch.empty((), device=dev, dtype=torch.float32)
+            rcoef, sums = _vec(logits, 2 * C), _vec(logits, 2 * C)
+            ncls = torch.empty((C + 1,), device=dev, dtype=torch.int64)
+            ws = _ws(logits, lib.query("nasseg_ce_region_workspace", C))
+            lib.call(_k("nasseg_ce_region_fwd", logits), ptr(logits), ptr(target), esz, ptr(weight), B * H * W, C,
+                     int(ignore_index), 1, *cfg, alpha, beta, smooth, all_classes, region_weight, ptr(base),
+                     ptr(loss_ce), ptr(loss_region), ptr(stats), ptr(counts), ptr(pixel_loss), ptr(rcoef), ptr(sums),
+                     ptr(ncls), ptr(ws), current_stream())
+        loss, llov, _, coef, _, _ = _lovasz_forward(logits, target, esz, ignore_index, lcfg, base, False)
+        ctx.save_for_backward(logits, target, weight, pixel_loss, stats, rcoef, coef)
+        ctx.cfg = (esz, int(ignore_index), None if rcfg is None else rcfg[4], lcfg[0])
+        tau = _own_scalar(stats, 1)
+        outs = (loss, pixel_loss, tau, counts, loss_ce, loss_region, llov)
+        ctx.mark_non_differentiable(*[o for o in outs[1:] if o is not None])
+        return outs
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        logits, target, weight, pixel_loss, stats, rcoef, coef = ctx.saved_tensors
+        esz, ignore, region_weight, lovasz_weight = ctx.cfg
+        B, C, H, W = logits.shape
+        g = g.to(torch.float32).contiguous().view(1)
+        d = torch.empty_like(logits)
+        if rcoef is None:
+            lib.call(_k("nasseg_ce_sel_bwd", logits), ptr(logits), ptr(target), esz, ptr(weight), ptr(pixel_loss),
+                     ptr(stats), ptr(g), B * H * W, C, ignore, ptr(d), current_stream())
+        else:
+            lib.call(_k("nasseg_ce_region_bwd", logits), ptr(logits), ptr(target), esz, ptr(weight), ptr(pixel_loss),
+                     ptr(stats), ptr(rcoef), ptr(g), 1, region_weight, B * H * W, C, ignore, ptr(d),
+                     current_stream())
+        _lovasz_backward(logits, target, esz, ignore, coef, g, lovasz_weight, True, d)
+        return d, None, None, None, None, None, None
+
+
 def region_overlap_loss(logits, target, region="jaccard", smooth=1.0, classes="present", ignore_index=255,
                         return_parts=False):
     """Soft Jaccard / Dice / Tversky loss of (B, C, H, W) logits -> 0-dim loss of its own storage (INTEGRATION.md,
@@ -2719,7 +2906,7 @@ def region_overlap_loss(logits, target, region="jaccard", smooth=1.0, classes="p
 
 def cross_entropy_select(logits, target, weight=None, ignore_index=255, thresh=None, min_kept=0, keep_fraction=0.0,
                          return_parts=False, region=None, region_weight=1.0, region_smooth=1.0,
-                         region_classes="present"):
+                         region_classes="present", lovasz_weight=None, lovasz_classes="present"):
     """Class-weighted cross-entropy of (B, C, H, W) logits with online hard-example selection -> 0-dim loss of its
     own storage ("Losses").
 
@@ -2735,12 +2922,23 @@ def cross_entropy_select(logits, target, weight=None, ignore_index=255, thresh=N
     ``classes`` of ``region_overlap_loss``): loss = the above + ``region_weight`` * that region term over ALL valid
     pixels (selection does not thin it, the weights do not enter it), from the same two passes over the logits;
     ``return_parts`` then also returns the two component losses: (loss, pixel_loss, tau, counts, loss_ce,
-    loss_region).  No host synchronisation: capturable."""
+    loss_region).
+    ``lovasz_weight`` (a number; None: no such term, and nothing here changes): ``lovasz_weight`` *
+    ``lovasz_softmax_loss(logits, target, lovasz_classes, ignore_index)`` is added, over ALL valid pixels and without
+    the class weights, in the same autograd node; ``return_parts`` then ends with loss_ce (where it was absent) and
+    loss_lovasz: (loss, pixel_loss, tau, counts, loss_ce[, loss_region], loss_lovasz).
+    No host synchronisation: capturable."""
     cfg = _select_config("cross_entropy_select", thresh, min_kept, keep_fraction)
-    if region is None:
+    rcfg = None
+    if region is not None:
+        rcfg = _region_config("cross_entropy_select", region, region_smooth, region_classes, region_weight)
+    if lovasz_weight is not None:
+        lcfg = _lovasz_config("cross_entropy_select", lovasz_weight, lovasz_classes)
+        out = _CrossEntropyLovasz.apply(logits, target, weight, ignore_index, cfg, rcfg, lcfg)
+        return tuple(o for i, o in enumerate(out) if i != 5 or rcfg is not None) if return_parts else out[0]
+    if rcfg is None:
         out = _CrossEntropySelect.apply(logits, target, weight, ignore_index, cfg)
         return out if return_parts else out[0]
-    rcfg = _region_config("cross_entropy_select", region, region_smooth, region_classes, region_weight)
     out = _CrossEntropyRegion.apply(logits, target, weight, ignore_index, cfg, rcfg)
     return (out[0], out[3], out[4], out[5], out[1], out[2]) if return_parts else out[0]
 

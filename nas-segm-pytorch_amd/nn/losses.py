@@ -38,10 +38,14 @@ class SegmCrossEntropy(nn.Module):
     ``region`` ("jaccard" | "dice" | ("tversky", alpha, beta)): ``region_weight`` times the soft Jaccard / Dice /
     Tversky loss over all valid pixels is added (``F.region_overlap_loss`` with ``smooth=region_smooth,
     classes=region_classes``), computed by the same two passes over the logits - the usual ``CE + lambda * Dice``.
-    Such a criterion is the loss of every head even without weights or selection."""
+    Such a criterion is the loss of every head even without weights or selection.
+    ``lovasz_weight`` (a number; None: no such term): ``lovasz_weight`` times the Lovasz-Softmax loss over all valid
+    pixels is added (``F.lovasz_softmax_loss`` with ``classes=lovasz_classes``), sorted on the device inside the same
+    autograd node - the usual ``CE + Lovasz``.  Such a criterion, too, is the loss of every head."""
 
     def __init__(self, weight=None, ignore_index=255, thresh=None, min_kept=0, keep_fraction=0.0, region=None,
-                 region_weight=1.0, region_smooth=1.0, region_classes="present"):
+                 region_weight=1.0, region_smooth=1.0, region_classes="present", lovasz_weight=None,
+                 lovasz_classes="present"):
         super(SegmCrossEntropy, self).__init__()
         if weight is not None:
             weight = torch.as_tensor(weight)
@@ -61,6 +65,13 @@ class SegmCrossEntropy(nn.Module):
         self.region_weight = region_weight
         self.region_smooth = region_smooth
         self.region_classes = region_classes
+        if lovasz_weight is not None:
+            F._lovasz_config("SegmCrossEntropy", lovasz_weight, lovasz_classes)
+        elif lovasz_classes not in ("present", "all"):
+            raise ValueError("SegmCrossEntropy: lovasz_classes must be \"present\" or \"all\" (got {!r})".format(
+                lovasz_classes))
+        self.lovasz_weight = lovasz_weight
+        self.lovasz_classes = lovasz_classes
 
     @property
     def selects(self):
@@ -72,6 +83,8 @@ class SegmCrossEntropy(nn.Module):
                self.min_kept, self.keep_fraction)
         if self.region is not None:  # (the term's four values are kernel arguments: recorded by value)
             cfg = cfg + (("region", self.region, self.region_weight, self.region_smooth, self.region_classes),)
+        if self.lovasz_weight is not None:
+            cfg = cfg + (("lovasz", self.lovasz_weight, self.lovasz_classes),)
         return cfg
 
     def prepare(self, device):
@@ -84,12 +97,14 @@ class SegmCrossEntropy(nn.Module):
 
     def forward(self, logits, target):
         self.prepare(logits.device)
-        if self.region is None:
-            return F.cross_entropy_select(logits, target, self.weight, self.ignore_index, self.thresh, self.min_kept,
-                                          self.keep_fraction)
+        terms = {}
+        if self.region is not None:
+            terms.update(region=self.region, region_weight=self.region_weight, region_smooth=self.region_smooth,
+                         region_classes=self.region_classes)
+        if self.lovasz_weight is not None:
+            terms.update(lovasz_weight=self.lovasz_weight, lovasz_classes=self.lovasz_classes)
         return F.cross_entropy_select(logits, target, self.weight, self.ignore_index, self.thresh, self.min_kept,
-                                      self.keep_fraction, region=self.region, region_weight=self.region_weight,
-                                      region_smooth=self.region_smooth, region_classes=self.region_classes)
+                                      self.keep_fraction, **terms)
 
     def extra_repr(self):
         s = "classes={}, ignore_index={}, thresh={}, min_kept={}, keep_fraction={}".format(
@@ -98,4 +113,6 @@ class SegmCrossEntropy(nn.Module):
         if self.region is not None:
             s += ", region={!r}, region_weight={}, region_smooth={}, region_classes={!r}".format(
                 self.region, self.region_weight, self.region_smooth, self.region_classes)
+        if self.lovasz_weight is not None:
+            s += ", lovasz_weight={}, lovasz_classes={!r}".format(self.lovasz_weight, self.lovasz_classes)
         return s
