@@ -508,6 +508,39 @@ int nasseg_ce_region_bwd(const float* logits, const void* target, int elem_size,
                          int with_ce, double region_weight, int64_t P, int C, int ignore, float* dlogits,
                          void* stream);
 
+/* Full-size cross-entropy: the criterion of nasseg_ce_sel_fwd taken at the LABELS' size, the bilinear up-sampling of
+ * the logits fused in.  It replaces, for a caller who asks for it, the label resize of src/engine/trainer.py:141-143,
+ * 236-238 (labels nearest-resized down to the logits) and the up-sampling of the auxiliary heads of :245-250 - the
+ * loss is then taken where validate() (src/engine/inference.py:55-66) scores: on the logits resized to the labels.
+ * logits [B][h][w][C], labels [B][H][W] (uint8 / int64) at ANY size, larger than, equal to or smaller than (h, w), per
+ * axis.  For label pixel (b, Y, X): ly = lin_coeff(Y, h/H, h, H), lx = lin_coeff(X, w/W, w, W) (bilinear,
+ * align_corners = False, torch's source index in fp32) and for every channel
+ *   top = l0x x00 + l1x x01,  bot = l0x x10 + l1x x11,  v_c = l0y top + l1y bot
+ * with every product and every sum rounded to fp32 on its own - bit for bit the row nasseg_argmax_cm takes its argmax
+ * of; equal sizes are the identity.  A label pixel is valid iff t != ignore and 0 <= t < C;
+ * l_p = logsumexp(v) - v_t with max, expf and logf as nasseg_ce_fwd.  Selection, loss, stats, counts and the NaN rule
+ * are literally nasseg_ce_sel_fwd's over the P = B*H*W label pixels (the selection IS nasseg_ohem_threshold run over
+ * pixel_loss).  Per pixel nothing but pixel_loss[p] (-1 where not valid) and lse[p] = logsumexp(v) is written: no
+ * tensor of B*H*W*C elements exists in either direction.
+ * Backward (tau and the kept set are constants): with g_pc = gscale * w[t_p] * (exp(v_pc - lse_p) - [c == t_p]) /
+ * stats[0] on kept pixels and 0 elsewhere,
+ *   dlogits[b][i][j][c] = sum_{Y, X} Wy(Y, i) Wx(X, j) g_(b,Y,X),c,   Wy(Y, i) = l0y [i0(Y) == i] + l1y [i1(Y) == i]
+ * (Wx alike), a gather in a fixed order (Y, then X, ascending) in fp32; a logit no label pixel touches gets an exact
+ * zero; stored in the logits' type, written once.  Sums over pixels: per-workgroup partial rows added in fp64 in a
+ * fixed order by one finalize launch.  No float atomics, no host synchronisation, no allocation, a launch geometry
+ * that depends on the shapes alone: capturable and bit-reproducible.
+ * B*H*W < 2^32, B*h*w*C < 2^31, C >= 2, and B * ceil(h/8) * ceil(w/8) * ceil(C/64) < 2^24 (the backward's workgroups:
+ * one per 8 x 8 tile of logits and 64 channels - a limit that only maps thinner than a tile can reach before the others).
+ * ws: nasseg_ce_up_workspace floats (0: bad shape) - a function of the grid alone, not of the pixel count. */
+int64_t nasseg_ce_up_workspace(int B, int h, int w, int C, int H, int W);
+int nasseg_ce_up_fwd(const float* logits, const void* target, int elem_size, const float* weight, int B, int h, int w,
+                     int C, int H, int W, int ignore, int select, float t_loss, int64_t min_kept, double keep_fraction,
+                     float* loss, float* stats, int64_t* counts, float* pixel_loss, float* lse, float* ws,
+                     void* stream);
+int nasseg_ce_up_bwd(const float* logits, const void* target, int elem_size, const float* weight,
+                     const float* pixel_loss, const float* lse, const float* stats, const float* gscale, int B, int h,
+                     int w, int C, int H, int W, int ignore, float* dlogits, void* stream);
+
 /* Lovasz-Softmax term (Berman, Triggs, Blaschko, CVPR 2018; absent from the reference): the convex extension of the
  * Jaccard loss, the surrogate of the mean IoU the reward is built from.  Logits [P][C], labels [P]; pixel p is valid
  * iff its label t != ignore and 0 <= t < C; n = valid pixels, y_pc = [t_p == c], N_c = sum_p y_pc.
@@ -833,6 +866,13 @@ int nasseg_bf16_ce_region_bwd(const nasseg_bf16_t* logits, const void* target, i
                               const float* pixel_loss, const float* stats, const float* coef, const float* gscale,
                               int with_ce, double region_weight, int64_t P, int C, int ignore,
                               nasseg_bf16_t* dlogits, void* stream);
+int nasseg_bf16_ce_up_fwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* weight, int B,
+                          int h, int w, int C, int H, int W, int ignore, int select, float t_loss, int64_t min_kept,
+                          double keep_fraction, float* loss, float* stats, int64_t* counts, float* pixel_loss,
+                          float* lse, float* ws, void* stream);
+int nasseg_bf16_ce_up_bwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* weight,
+                          const float* pixel_loss, const float* lse, const float* stats, const float* gscale, int B,
+                          int h, int w, int C, int H, int W, int ignore, nasseg_bf16_t* dlogits, void* stream);
 int nasseg_bf16_lovasz_fwd(const nasseg_bf16_t* logits, const void* target, int elem_size, int64_t P, int C,
                            int ignore, int all_classes, double lovasz_weight, const float* base_loss, float* loss,
                            float* loss_lovasz, float* errors, float* coef, int* rank, int64_t* ncls, float* ws,

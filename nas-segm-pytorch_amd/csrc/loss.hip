@@ -17,6 +17,7 @@ namespace {
 // Is a per-pixel loss that takes part (l >= 0; -1 marks the others) kept at threshold tau?  l >= tau on the fp32
 // values, compared through their bit patterns (for non-negative floats the order of the patterns is the order of
 // the values) so that the answer is the same integer comparison the radix selection below made, denormals included.
+// (csrc/loss_up.hip holds a copy, up_kept, and copies of ce_sel_sum_kernel / ce_sel_finalize_kernel: change them together.)
 __device__ __forceinline__ bool sel_kept(float l, float tau) {
   if (l < 0.f) return false;
   return !(tau > 0.f) || __float_as_uint(l) >= __float_as_uint(tau);

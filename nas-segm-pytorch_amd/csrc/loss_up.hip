@@ -1,0 +1,383 @@
+// Cross-entropy of low-resolution logits against FULL-SIZE labels, the bilinear up-sampling fused in (definition:
+// include/nasseg.h, "full-size cross-entropy"; INTEGRATION.md, "Losses").
+//
+// Reference: src/engine/trainer.py:141-146,236-250 resize the labels DOWN to the logits (nearest) before the loss,
+// while validate() (src/engine/inference.py:55-66) scores the logits resized UP to the labels.  The remedy of DeepLab /
+// torchvision / mmseg - up-sample the logits, take the loss at the labels' size - composed from nasseg_bilinear_fwd +
+// nasseg_ce_sel_fwd writes, keeps and reads back a [B][H][W][C] tensor in each direction.  Here the interpolated row of
+// a label pixel lives in registers only:
+//   forward   one lane per label pixel: the four neighbour rows of the logits through L1 / L2 (lanes next to each other
+//             share them), v_c = the row nasseg_argmax_cm takes its argmax of, bit for bit; pixel_loss and lse are the
+//             only per-pixel outputs.  Selection: nasseg_ohem_threshold over pixel_loss.  Then one sum pass and one
+//             fp64 finalize launch, the arithmetic of nasseg_ce_sel_fwd's.
+//   backward  a gather (as nasseg_bilinear_bwd): a workgroup owns a tile of kUpTile x kUpTile logits pixels and a chunk
+//             of <= kUpChunk channels, stages tile + halo of the logits in LDS (row stride cn | 1 floats: odd), and every
+//             thread walks the label pixels of ITS (pixel, channel) in a fixed order: re-interpolates its channel,
+//             exp(v - lse) - onehot, times the pixel's factor and Wy Wx.  dlogits is written once; no atomics.
+#include <math.h>
+
+#include "common.h"
+#include "resize_index.h"
+
+namespace {
+
+constexpr int kUpGridCap = 1024;  // workgroups of the forward and of the sum pass (= rows of the partials)
+constexpr int kUpTile = 8;        // backward: logits pixels per tile side
+constexpr int kUpPatch = kUpTile + 2;
+constexpr int kUpChunk = 64;      // backward: channels per workgroup
+
+// A copy of csrc/loss.hip's sel_kept (and, below, of its ce_sel_sum_kernel / ce_sel_finalize_kernel: loss.hip keeps them
+// in its unnamed namespace and points here) - it must stay the compare of the radix selection, bit for bit: is a
+// per-pixel loss that takes part (l >= 0) kept at tau?  On the bit patterns, as the radix selection compares them.
+__device__ __forceinline__ bool up_kept(float l, float tau) {
+  if (l < 0.f) return false;
+  return !(tau > 0.f) || __float_as_uint(l) >= __float_as_uint(tau);
+}
+
+// v = ly.l0 * (lx.l0 * x00 + lx.l1 * x01) + ly.l1 * (lx.l0 * x10 + lx.l1 * x11), every product and sum rounded on
+// its own (csrc/miou.hip: argmax_cm_kernel)
+__device__ __forceinline__ float up_interp(float x00, float x01, float x10, float x11, const Lin& ly, const Lin& lx) {
+  const float top = __fadd_rn(__fmul_rn(lx.l0, x00), __fmul_rn(lx.l1, x01));
+  const float bot = __fadd_rn(__fmul_rn(lx.l0, x10), __fmul_rn(lx.l1, x11));
+  return __fadd_rn(__fmul_rn(ly.l0, top), __fmul_rn(ly.l1, bot));
+}
+
+template <typename TL>
+__global__ __launch_bounds__(256) void ce_up_fwd_kernel(const act_t* __restrict__ logits, const TL* __restrict__ target,
+                                                        int B, int h, int w, int C, int H, int W, float sh, float sw,
+                                                        int ignore, float* __restrict__ pixel_loss,
+                                                        float* __restrict__ lse_out) {
+  const int64_t P = (int64_t)B * H * W;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
+    const int64_t t = (int64_t)target[p];
+    if (t == ignore || t < 0 || t >= C) {  // out-of-range labels are skipped, never read
+      pixel_loss[p] = -1.f;
+      lse_out[p] = 0.f;
+      continue;
+    }
+    const int X = (int)(p % W);
+    const int64_t q = p / W;
+    const int Y = (int)(q % H);
+    const int b = (int)(q / H);
+    const Lin ly = lin_coeff(Y, sh, h, H);
+    const Lin lx = lin_coeff(X, sw, w, W);
+    const act_t* lb = logits + (int64_t)b * h * w * C;
+    const act_t* p00 = lb + ((int64_t)ly.i0 * w + lx.i0) * C;
+    const act_t* p01 = lb + ((int64_t)ly.i0 * w + lx.i1) * C;
+    const act_t* p10 = lb + ((int64_t)ly.i1 * w + lx.i0) * C;
+    const act_t* p11 = lb + ((int64_t)ly.i1 * w + lx.i1) * C;
+    float m = up_interp(lda1(p00), lda1(p01), lda1(p10), lda1(p11), ly, lx);
+    for (int c = 1; c < C; ++c)
+      m = fmaxf(m, up_interp(lda1(p00 + c), lda1(p01 + c), lda1(p10 + c), lda1(p11 + c), ly, lx));
+    float s = 0.f;
+    for (int c = 0; c < C; ++c)
+      s += expf(up_interp(lda1(p00 + c), lda1(p01 + c), lda1(p10 + c), lda1(p11 + c), ly, lx) - m);
+    const float lse = m + logf(s);
+    pixel_loss[p] = lse - up_interp(lda1(p00 + t), lda1(p01 + t), lda1(p10 + t), lda1(p11 + t), ly, lx);
+    lse_out[p] = lse;
+  }
+}
+
+// partial[b] = {sum w l, sum w, count} over the kept pixels of workgroup b: the statements of csrc/loss.hip's
+// ce_sel_sum_kernel (tau == nullptr: every valid pixel is kept)
+template <typename TL>
+__global__ __launch_bounds__(256) void ce_up_sum_kernel(const float* __restrict__ pixel_loss,
+                                                        const TL* __restrict__ target,
+                                                        const float* __restrict__ weight, int64_t P,
+                                                        const float* __restrict__ tau, float* __restrict__ partial) {
+  __shared__ float red_l[256];
+  __shared__ float red_w[256];
+  __shared__ float red_n[256];
+  const float t = tau ? tau[0] : 0.f;
+  float loss = 0.f, sw = 0.f, cnt = 0.f;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
+    const float l = pixel_loss[p];
+    if (!up_kept(l, t)) continue;
+    const float wt = weight ? weight[(int64_t)target[p]] : 1.f;  // (l >= 0: the label is in [0, C))
+    loss += wt * l;
+    sw += wt;
+    cnt += 1.f;
+  }
+  red_l[threadIdx.x] = loss;
+  red_w[threadIdx.x] = sw;
+  red_n[threadIdx.x] = cnt;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      red_l[threadIdx.x] += red_l[threadIdx.x + s];
+      red_w[threadIdx.x] += red_w[threadIdx.x + s];
+      red_n[threadIdx.x] += red_n[threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x * 3] = red_l[0];
+    partial[blockIdx.x * 3 + 1] = red_w[0];
+    partial[blockIdx.x * 3 + 2] = red_n[0];
+  }
+}
+
+// loss = sum w l / sum w, stats = {sum w, tau}, counts[2] = kept pixels (selected: counts[0..1] and stats[1] are the
+// selection's; else k = n = kept and tau = -inf): the statements of ce_sel_finalize_kernel, fp64, fixed order
+__global__ __launch_bounds__(256) void ce_up_finalize_kernel(const float* __restrict__ partial, int nblk, int selected,
+                                                             float* __restrict__ loss, float* __restrict__ stats,
+                                                             int64_t* __restrict__ counts) {
+  __shared__ double red_l[256];
+  __shared__ double red_w[256];
+  __shared__ double red_n[256];
+  double l = 0.0, w = 0.0, n = 0.0;
+  for (int b = threadIdx.x; b < nblk; b += 256) {
+    l += (double)partial[b * 3];
+    w += (double)partial[b * 3 + 1];
+    n += (double)partial[b * 3 + 2];
+  }
+  red_l[threadIdx.x] = l;
+  red_w[threadIdx.x] = w;
+  red_n[threadIdx.x] = n;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      red_l[threadIdx.x] += red_l[threadIdx.x + s];
+      red_w[threadIdx.x] += red_w[threadIdx.x + s];
+      red_n[threadIdx.x] += red_n[threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    loss[0] = (float)(red_l[0] / red_w[0]);
+    stats[0] = (float)red_w[0];
+    counts[2] = (int64_t)red_n[0];
+    if (!selected) {
+      stats[1] = -__builtin_inff();
+      counts[0] = counts[1] = (int64_t)red_n[0];
+    }
+  }
+}
+
+// conservative range [lo, hi] of label coordinates whose footprint can touch logits index i (csrc/resize.hip's
+// dst_range: a coordinate inside it that does not touch i has weight exactly 0)
+__device__ __forceinline__ void up_dst_range(int i, float scale, int in_size, int out_size, int& lo, int& hi) {
+  if (in_size == out_size) {
+    lo = hi = i;
+    return;
+  }
+  // src(o) in [i-1, i+1)  <=>  o in [(i-0.5)/scale - 0.5, (i+1.5)/scale - 0.5)
+  const float inv = 1.0f / scale;
+  lo = (int)floorf(((float)i - 0.5f) * inv - 0.5f) - 1;
+  hi = (int)ceilf(((float)i + 1.5f) * inv - 0.5f) + 1;
+  if (lo < 0) lo = 0;
+  if (hi > out_size - 1) hi = out_size - 1;
+}
+__device__ __forceinline__ float up_weight(const Lin& l, int i) {
+  float wt = 0.f;
+  if (l.i0 == i) wt += l.l0;
+  if (l.i1 == i) wt += l.l1;
+  return wt;
+}
+
+// grid: (channel chunk, tile x, tile y, image), flattened, chunk fastest.  VEC: the patch is staged with 16-byte
+// (bf16: 8-byte) loads - one chunk (C <= kUpChunk) and 16-byte aligned logits; else element by element.
+// LDS: patch[kUpPatch][kUpPatch][cn | 1] floats.
+template <typename TL, bool VEC>
+__global__ __launch_bounds__(256) void ce_up_bwd_kernel(const act_t* __restrict__ logits, const TL* __restrict__ target,
+                                                        const float* __restrict__ weight,
+                                                        const float* __restrict__ pixel_loss,
+                                                        const float* __restrict__ lse, const float* __restrict__ stats,
+                                                        const float* __restrict__ gscale, int B, int h, int w, int C,
+                                                        int H, int W, float sh, float sw, int tiles_y, int tiles_x,
+                                                        int nchunk, act_t* __restrict__ dlogits) {
+  extern __shared__ float patch[];
+  const int tid = threadIdx.x;
+  int wi = blockIdx.x;
+  const int ch = wi % nchunk;
+  wi /= nchunk;
+  const int tx = wi % tiles_x;
+  wi /= tiles_x;
+  const int ty = wi % tiles_y;
+  const int b = wi / tiles_y;
+  const int c0 = ch * kUpChunk;
+  const int cn = C - c0 < kUpChunk ? C - c0 : kUpChunk;
+  const int CS = cn | 1;
+  const int y0 = ty * kUpTile, x0 = tx * kUpTile;
+  const int ny = h - y0 < kUpTile ? h - y0 : kUpTile;  // the tile's own pixels
+  const int nx = w - x0 < kUpTile ? w - x0 : kUpTile;
+  const int oy = y0 > 0 ? y0 - 1 : 0, ox = x0 > 0 ? x0 - 1 : 0;  // origin of the patch: one pixel of halo, inside the map
+  const int py = (y0 + ny < h ? y0 + ny : h - 1) - oy + 1;         // its rows (<= kUpPatch)
+  const int px = (x0 + nx < w ? x0 + nx : w - 1) - ox + 1;         // its pixels per row (<= kUpPatch)
+  if (VEC) {  // (cn == C) a patch row is px * C contiguous elements: whole aligned vectors around it, inside the buffer
+    const int64_t total4 = ((int64_t)B * h * w * C) & ~(int64_t)3;
+    const int n = px * C;
+    const int nvmax = (n + 3) / 4 + 1;
+    for (int j = tid; j < py * nvmax; j += 256) {
+      const int r = j / nvmax, i = j - r * nvmax;
+      const int64_t g0 = (((int64_t)b * h + oy + r) * w + ox) * C;
+      const int64_t a = (g0 & ~(int64_t)3) + 4 * (int64_t)i;
+      if (a >= g0 + n) continue;
+      float* prow = patch + r * kUpPatch * CS;
+      const int rel = (int)(a - g0);  // (-3 .. n - 1)
+      if (a + 4 <= total4) {
+        const float4 v = lda4(logits + a);
+        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int q = rel + k;
+          if (q >= 0 && q < n) {
+            const int xx = q / C;
+            prow[xx * CS + (q - xx * C)] = e[k];
+          }
+        }
+      } else {  // (the last, incomplete vector of the buffer)
+        for (int k = 0; k < 4; ++k) {
+          const int q = rel + k;
+          if (q >= 0 && q < n) {
+            const int xx = q / C;
+            prow[xx * CS + (q - xx * C)] = lda1(logits + a + k);
+          }
+        }
+      }
+    }
+  } else {
+    const int n = px * cn;
+    for (int j = tid; j < py * n; j += 256) {
+      const int r = j / n, q = j - r * n;
+      const int xx = q / cn, c = q - xx * cn;
+      patch[(r * kUpPatch + xx) * CS + c] = lda1(logits + (((int64_t)b * h + oy + r) * w + ox + xx) * C + c0 + c);
+    }
+  }
+  __syncthreads();
+  const float g = gscale ? gscale[0] : 1.f;
+  const float sumw = stats[0], tau = stats[1];
+  for (int item = tid; item < ny * nx * cn; item += 256) {
+    const int pix = item / cn, c = item - pix * cn;
+    const int iy = pix / nx, jx = pix - iy * nx;
+    const int i = y0 + iy, j = x0 + jx;
+    int ylo, yhi, xlo, xhi;
+    up_dst_range(i, sh, h, H, ylo, yhi);
+    up_dst_range(j, sw, w, W, xlo, xhi);
+    float acc = 0.f;
+    for (int Y = ylo; Y <= yhi; ++Y) {
+      const Lin ly = lin_coeff(Y, sh, h, H);
+      const float wy = up_weight(ly, i);
+      if (wy == 0.f) continue;  // (so ly.i0, ly.i1 lie in [i - 1, i + 1]: inside the patch)
+      const float* r0 = patch + (ly.i0 - oy) * kUpPatch * CS + c;
+      const float* r1 = patch + (ly.i1 - oy) * kUpPatch * CS + c;
+      const int64_t prow = ((int64_t)b * H + Y) * W;
+      for (int X = xlo; X <= xhi; ++X) {
+        const Lin lx = lin_coeff(X, sw, w, W);
+        const float wx = up_weight(lx, j);
+        if (wx == 0.f) continue;
+        const int64_t p = prow + X;
+        if (!up_kept(pixel_loss[p], tau)) continue;  // (-1 on pixels that are not valid)
+        const int64_t t = (int64_t)target[p];
+        const float gp = (g * (weight ? weight[t] : 1.f)) / sumw;
+        const int a0 = (lx.i0 - ox) * CS, a1 = (lx.i1 - ox) * CS;
+        const float v = up_interp(r0[a0], r0[a1], r1[a0], r1[a1], ly, lx);
+        const float d = gp * (expf(v - lse[p]) - ((int64_t)(c0 + c) == t ? 1.f : 0.f));
+        acc = fmaf(wy * wx, d, acc);
+      }
+    }
+    sta1(dlogits + (((int64_t)b * h + i) * w + j) * C + c0 + c, acc);
+  }
+}
+
+inline int up_grid(int64_t P) {
+  int64_t b = (P + 255) / 256;
+  if (b > kUpGridCap) b = kUpGridCap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+inline bool up_shape_ok(int B, int h, int w, int C, int H, int W) {
+  if (B <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || C < 2) return false;
+  if ((int64_t)B * H * W >= ((int64_t)1 << 32)) return false;
+  if ((int64_t)B * h * w * C >= ((int64_t)1 << 31)) return false;
+  // the backward's grid: one workgroup of 256 threads per (tile, channel chunk), and a grid holds fewer than 2^32 threads
+  if ((int64_t)B * cdiv(h, kUpTile) * cdiv(w, kUpTile) * cdiv(C, kUpChunk) >= ((int64_t)1 << 24)) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+#if NASSEG_FP32_ONLY
+// floats: [kUpGridCap][3] partials | the selection's words.  A function of the grid alone.
+int64_t nasseg_ce_up_workspace(int B, int h, int w, int C, int H, int W) {
+  if (!up_shape_ok(B, h, w, C, H, W)) return 0;
+  return 3 * kUpGridCap + nasseg_ohem_workspace();
+}
+#endif
+
+int NASSEG_FN(ce_up_fwd)(const act_t* logits, const void* target, int elem_size, const float* weight, int B, int h,
+                         int w, int C, int H, int W, int ignore, int select, float t_loss, int64_t min_kept,
+                         double keep_fraction, float* loss, float* stats, int64_t* counts, float* pixel_loss,
+                         float* lse, float* ws, void* stream) {
+  NASSEG_REQUIRE(up_shape_ok(B, h, w, C, H, W), "ce_up_fwd: bad shape (C >= 2, B*H*W < 2^32, B*h*w*C < 2^31, fewer than 2^24 backward tiles)");
+  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_up_fwd: elem_size %d not supported", elem_size);
+  NASSEG_REQUIRE(logits && target && loss && stats && counts && pixel_loss && lse && ws, "ce_up_fwd: null pointer");
+  NASSEG_REQUIRE(!select || (min_kept >= 1 && keep_fraction >= 0.0 && keep_fraction <= 1.0),
+                 "ce_up_fwd: selection needs min_kept >= 1 and 0 <= keep_fraction <= 1");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t P = (int64_t)B * H * W;
+  const int grid = up_grid(P);
+  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
+  if (elem_size == 8)
+    hipLaunchKernelGGL(ce_up_fwd_kernel<int64_t>, dim3(grid), dim3(256), 0, s, logits, (const int64_t*)target, B, h,
+                       w, C, H, W, sh, sw, ignore, pixel_loss, lse);
+  else
+    hipLaunchKernelGGL(ce_up_fwd_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)target, B, h,
+                       w, C, H, W, sh, sw, ignore, pixel_loss, lse);
+  NASSEG_LAUNCH_CHECK("ce_up_fwd");
+  if (select) {
+    const int rc = nasseg_ohem_threshold(pixel_loss, P, t_loss, min_kept, keep_fraction, stats + 1, counts,
+                                         ws + 3 * kUpGridCap, stream);
+    if (rc != NASSEG_OK) return rc;
+  }
+  const float* tau = select ? stats + 1 : nullptr;
+  if (elem_size == 8)
+    hipLaunchKernelGGL(ce_up_sum_kernel<int64_t>, dim3(grid), dim3(256), 0, s, pixel_loss, (const int64_t*)target,
+                       weight, P, tau, ws);
+  else
+    hipLaunchKernelGGL(ce_up_sum_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, pixel_loss, (const uint8_t*)target,
+                       weight, P, tau, ws);
+  NASSEG_LAUNCH_CHECK("ce_up_sum");
+  hipLaunchKernelGGL(ce_up_finalize_kernel, dim3(1), dim3(256), 0, s, ws, grid, select, loss, stats, counts);
+  NASSEG_LAUNCH_CHECK("ce_up_finalize");
+  return NASSEG_OK;
+}
+
+int NASSEG_FN(ce_up_bwd)(const act_t* logits, const void* target, int elem_size, const float* weight,
+                         const float* pixel_loss, const float* lse, const float* stats, const float* gscale, int B,
+                         int h, int w, int C, int H, int W, int ignore, act_t* dlogits, void* stream) {
+  (void)ignore;  // (validity is pixel_loss >= 0: the forward decided it)
+  NASSEG_REQUIRE(up_shape_ok(B, h, w, C, H, W), "ce_up_bwd: bad shape (C >= 2, B*H*W < 2^32, B*h*w*C < 2^31, fewer than 2^24 backward tiles)");
+  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_up_bwd: elem_size %d not supported", elem_size);
+  NASSEG_REQUIRE(logits && target && pixel_loss && lse && stats && dlogits, "ce_up_bwd: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const int tiles_y = cdiv(h, kUpTile), tiles_x = cdiv(w, kUpTile), nchunk = cdiv(C, kUpChunk);
+  const int64_t nwg = (int64_t)B * tiles_y * tiles_x * nchunk;  // (< 2^24: up_shape_ok)
+  const int cmax = C < kUpChunk ? C : kUpChunk;
+  const size_t lds = (size_t)kUpPatch * kUpPatch * (cmax | 1) * sizeof(float);
+  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
+  const bool vec = nchunk == 1 && ((uintptr_t)logits & 15) == 0;
+#define NASSEG_UP_BWD(TL, VEC)                                                                                       \
+  hipLaunchKernelGGL((ce_up_bwd_kernel<TL, VEC>), dim3((unsigned)nwg), dim3(256), lds, s, logits, (const TL*)target, \
+                     weight, pixel_loss, lse, stats, gscale, B, h, w, C, H, W, sh, sw, tiles_y, tiles_x, nchunk,    \
+                     dlogits)
+  if (elem_size == 8) {
+    if (vec)
+      NASSEG_UP_BWD(int64_t, true);
+    else
+      NASSEG_UP_BWD(int64_t, false);
+  } else {
+    if (vec)
+      NASSEG_UP_BWD(uint8_t, true);
+    else
+      NASSEG_UP_BWD(uint8_t, false);
+  }
+#undef NASSEG_UP_BWD
+  NASSEG_LAUNCH_CHECK("ce_up_bwd");
+  return NASSEG_OK;
+}
+
+}  // extern "C"

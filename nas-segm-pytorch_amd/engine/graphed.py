@@ -403,6 +403,9 @@ class GraphedTask0Step(_GraphedStep):
                  aux_weight=0, capture_optimisers=False, warmup=2, kd_coeff=None, segm_crit=None):
         if kd_coeff is not None and segm_crit is not None:
             raise ValueError("GraphedTask0Step: the fused distillation term exists for the plain softmax/NLL only")
+        if getattr(segm_crit, "full_size", False):
+            raise ValueError("GraphedTask0Step: a full-size criterion (SegmCrossEntropy(full_size=True)) is for the "
+                             "end-to-end step only - the task0 cache holds labels at the logits' size")
         model = inner(segmenter)
         self.cache = Xy_train
         self.optim_dec = optim_dec

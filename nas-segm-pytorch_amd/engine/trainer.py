@@ -87,13 +87,14 @@ _MAPPED_CRITS = weakref.WeakKeyDictionary()  # nn.NLLLoss with class weights -> 
 def _segm_crit(segm_crit, device=None):
     """the criterion that replaces the plain softmax/NLL of every head, else None (F.log_softmax_nll with the
     criterion's ``ignore_index``, as ever).  An nn.SegmCrossEntropy with class weights, hard-example selection, a
-    region-overlap term or a Lovasz-Softmax term is that criterion itself; an nn.NLLLoss (nn.NLLLoss2d where torch has it) with ``weight`` and
+    region-overlap term or a Lovasz-Softmax term, or one that takes the loss at the labels' full size
+    (``full_size=True``), is that criterion itself; an nn.NLLLoss (nn.NLLLoss2d where torch has it) with ``weight`` and
     mean reduction - the one-line change to src/main_search.py:435 - is mapped to the equivalent SegmCrossEntropy,
     once per criterion and weight tensor.  ``device``: the weights are made fp32 there now (not inside a step being recorded)."""
     crit = None
     if isinstance(segm_crit, SegmCrossEntropy):
         if (segm_crit.weight is not None or segm_crit.selects or segm_crit.region is not None
-                or segm_crit.lovasz_weight is not None):
+                or segm_crit.lovasz_weight is not None or segm_crit.full_size):
             crit = segm_crit
     elif (isinstance(segm_crit, nn.NLLLoss) and segm_crit.weight is not None
           and getattr(segm_crit, "reduction", "mean") == "mean"):
@@ -440,6 +441,9 @@ def train_task0(Xy_train, segmenter, optim_dec, epoch, segm_crit, kd_crit, batch
     if _depth_crit(segm_crit) is not None:
         raise ValueError("train_task0: depth candidates are trained end to end only (train_segmenter) - the task0 "
                          "cache holds class labels, not depth maps")
+    if getattr(segm_crit, "full_size", False):
+        raise ValueError("train_task0: a full-size criterion (SegmCrossEntropy(full_size=True)) is for the end-to-end "
+                         "step only (train_segmenter) - the task0 cache holds labels at the logits' size")
     decoder = _inner(segmenter).decoder
     # (data parallel the cache is sharded: every rank must issue the same number of gradient
     #  all-reduces, so the shards agree on the smallest of their sizes first)

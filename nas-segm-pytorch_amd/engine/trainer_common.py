@@ -45,22 +45,32 @@ def _head_loss(logits, target, ignore_index, segm_crit):
     return segm_crit(logits, target)
 
 
+def _full_size(segm_crit):
+    """does the criterion take the loss at the labels' own size (nn.SegmCrossEntropy(full_size=True))?"""
+    return bool(getattr(segm_crit, "full_size", False))
+
+
 def segmentation_loss(output, aux_outs, target, ignore_index, aux_weight, loss=None, segm_crit=None):
     """LogSoftmax + NLL of the main head (``loss``: that term already computed, with the distillation term added)
-    + aux_weight * those of the auxiliary heads, each resized to the labels' size, when aux_weight > 0"""
+    + aux_weight * those of the auxiliary heads, each resized to the labels' size, when aux_weight > 0.
+    A full-size criterion (``_full_size``) up-samples inside its kernels: every head goes in at its own size against
+    the same label map, as in ``depth_loss``."""
     if loss is None:
         loss = _head_loss(output, target, ignore_index, segm_crit)
     if aux_weight > 0:
         for aux_out in aux_outs:
-            aux_out = F.bilinear_resize(aux_out, target.size()[1:])
+            if not _full_size(segm_crit):
+                aux_out = F.bilinear_resize(aux_out, target.size()[1:])
             loss = loss + _head_loss(aux_out, target, ignore_index, segm_crit) * aux_weight
     return loss
 
 
 def task1_loss(segmenter, image, target, ignore_index, aux_weight, segm_crit=None):
-    """forward + loss of the end-to-end step: the labels nearest-resized to the logits' size"""
+    """forward + loss of the end-to-end step: the labels nearest-resized to the logits' size - or, for a full-size
+    criterion, left as they are"""
     output, aux_outs = _heads(segmenter(image))
-    target = F.nearest_label_resize(target, output.size()[2:])
+    if not _full_size(segm_crit):
+        target = F.nearest_label_resize(target, output.size()[2:])
     return segmentation_loss(output, aux_outs, target, ignore_index, aux_weight, segm_crit=segm_crit)
 
 

@@ -2943,6 +2943,80 @@ def cross_entropy_select(logits, target, weight=None, ignore_index=255, thresh=N
     return (out[0], out[3], out[4], out[5], out[1], out[2]) if return_parts else out[0]
 
 
+class _CrossEntropyUpsampled(torch.autograd.Function):
+    """nasseg_ce_up_fwd / _bwd.  Outputs as _CrossEntropySelect's, pixel_loss at the labels' size (B, H, W)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, cfg):
+        logits = _cl(logits)
+        B, C, h, w = logits.shape
+        target, esz = _label_tensor(target)
+        if target.dim() != 3 or target.shape[0] != B or target.numel() == 0:
+            raise NassegError("cross_entropy_upsampled: the target must be uint8 or int64 of shape ({}, H, W) (got {})"
+                              .format(B, tuple(target.shape)))
+        if C < 2:
+            raise NassegError("cross_entropy_upsampled: at least two classes are expected (got logits {})".format(
+                tuple(logits.shape)))
+        if weight is not None:
+            require_device(weight)
+            if weight.dtype != torch.float32 or tuple(weight.shape) != (C,):
+                raise NassegError("cross_entropy_upsampled: the class weights must be fp32 of shape ({},) (got {} {})"
+                                  .format(C, weight.dtype, tuple(weight.shape)))
+            weight = weight.contiguous()
+        H, W = int(target.shape[1]), int(target.shape[2])
+        dims = (B, h, w, C, H, W)
+        n_ws = lib.query("nasseg_ce_up_workspace", *dims)
+        if n_ws <= 0:
+            raise NassegError("cross_entropy_upsampled: logits {} against labels {} exceed B*H*W < 2^32, "
+                              "B*h*w*C < 2^31 or 2^24 tiles of 8 x 8 logits and 64 channels".format(
+                                  tuple(logits.shape), tuple(target.shape)))
+        dev = logits.device
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        stats = _vec(logits, 2)
+        counts = torch.empty((3,), device=dev, dtype=torch.int64)
+        pixel_loss = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+        lse = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+        ws = _ws(logits, n_ws)
+        lib.call(_k("nasseg_ce_up_fwd", logits), ptr(logits), ptr(target), esz, ptr(weight), *dims,
+                 int(ignore_index), *cfg, ptr(loss), ptr(stats), ptr(counts), ptr(pixel_loss), ptr(lse), ptr(ws),
+                 current_stream())
+        ctx.save_for_backward(logits, target, weight, pixel_loss, lse, stats)
+        ctx.cfg = (esz, int(ignore_index), dims)
+        tau = _own_scalar(stats, 1)
+        ctx.mark_non_differentiable(pixel_loss, tau, counts)
+        return loss, pixel_loss, tau, counts
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        logits, target, weight, pixel_loss, lse, stats = ctx.saved_tensors
+        esz, ignore, dims = ctx.cfg
+        g = g.to(torch.float32).contiguous().view(1)
+        d = torch.empty_like(logits)
+        lib.call(_k("nasseg_ce_up_bwd", logits), ptr(logits), ptr(target), esz, ptr(weight), ptr(pixel_loss),
+                 ptr(lse), ptr(stats), ptr(g), *dims, ignore, ptr(d), current_stream())
+        return d, None, None, None, None
+
+
+def cross_entropy_upsampled(logits, target, weight=None, ignore_index=255, thresh=None, min_kept=0,
+                            keep_fraction=0.0, return_parts=False):
+    """``cross_entropy_select`` taken at the LABELS' size: the cross-entropy of (B, C, h, w) logits, up-sampled
+    bilinearly (align_corners=False) to the (B, H, W) labels inside the kernels -> 0-dim loss of its own storage
+    (INTEGRATION.md, "Losses").
+
+    The labels may be larger than, equal to or smaller than the logits, per axis; equal sizes give
+    ``cross_entropy_select``'s per-pixel losses bit for bit.  The row the loss sees at a label pixel is the row
+    ``argmax_confusion`` takes its argmax of in validation.  Class weights, ``ignore_index``, ``thresh`` /
+    ``min_kept`` / ``keep_fraction`` (over the B*H*W label pixels) and the ``ValueError``s are those of
+    ``cross_entropy_select``.  Nothing of B*H*W*C elements is allocated in either direction: per label pixel the
+    loss and the log-sum-exp are kept, the gradient is gathered straight into the logits' shape (exact zeros where
+    no kept label pixel reaches a logit).
+    ``return_parts``: (loss, pixel_loss (B, H, W) with -1 on invalid pixels, tau, counts = [k, n_valid, n_kept]).
+    No host synchronisation: capturable."""
+    cfg = _select_config("cross_entropy_upsampled", thresh, min_kept, keep_fraction)
+    out = _CrossEntropyUpsampled.apply(logits, target, weight, ignore_index, cfg)
+    return out if return_parts else out[0]
+
+
 def ohem_threshold(pixel_loss, thresh=None, min_kept=1, keep_fraction=0.0, t_loss=None):
     """The selection of ``cross_entropy_select`` alone, over any fp32 tensor: entries < 0 do not take part.
     Returns (tau, counts): tau = min(t_loss, k-th largest entry) as a 0-dim fp32 tensor, counts = int64

@@ -41,11 +41,17 @@ class SegmCrossEntropy(nn.Module):
     Such a criterion is the loss of every head even without weights or selection.
     ``lovasz_weight`` (a number; None: no such term): ``lovasz_weight`` times the Lovasz-Softmax loss over all valid
     pixels is added (``F.lovasz_softmax_loss`` with ``classes=lovasz_classes``), sorted on the device inside the same
-    autograd node - the usual ``CE + Lovasz``.  Such a criterion, too, is the loss of every head."""
+    autograd node - the usual ``CE + Lovasz``.  Such a criterion, too, is the loss of every head.
+    ``full_size=True``: ``F.cross_entropy_upsampled`` instead - ``target`` comes at ANY size (the full-size label
+    map), the logits are up-sampled bilinearly to it inside the kernels and the loss, class weights and selection
+    included, is taken over the label pixels: the resolution ``validate`` scores at.  The training steps then hand
+    every head, at its own size, the labels as they are (nothing is resized).  Such a criterion is the loss of every
+    head even without weights or selection; it has no region or Lovasz term, and ``train_task0`` refuses it (its
+    cache holds labels at the logits' size)."""
 
     def __init__(self, weight=None, ignore_index=255, thresh=None, min_kept=0, keep_fraction=0.0, region=None,
                  region_weight=1.0, region_smooth=1.0, region_classes="present", lovasz_weight=None,
-                 lovasz_classes="present"):
+                 lovasz_classes="present", full_size=False):
         super(SegmCrossEntropy, self).__init__()
         if weight is not None:
             weight = torch.as_tensor(weight)
@@ -72,6 +78,10 @@ class SegmCrossEntropy(nn.Module):
                 lovasz_classes))
         self.lovasz_weight = lovasz_weight
         self.lovasz_classes = lovasz_classes
+        if full_size and (region is not None or lovasz_weight is not None):
+            raise ValueError("SegmCrossEntropy: full_size=True has no region or Lovasz term (those terms are defined "
+                             "at the logits' size only)")
+        self.full_size = bool(full_size)
 
     @property
     def selects(self):
@@ -85,6 +95,8 @@ class SegmCrossEntropy(nn.Module):
             cfg = cfg + (("region", self.region, self.region_weight, self.region_smooth, self.region_classes),)
         if self.lovasz_weight is not None:
             cfg = cfg + (("lovasz", self.lovasz_weight, self.lovasz_classes),)
+        if self.full_size:  # (another loss kind: other launches, labels at another size)
+            cfg = cfg + (("full_size",),)
         return cfg
 
     def prepare(self, device):
@@ -97,6 +109,9 @@ class SegmCrossEntropy(nn.Module):
 
     def forward(self, logits, target):
         self.prepare(logits.device)
+        if self.full_size:
+            return F.cross_entropy_upsampled(logits, target, self.weight, self.ignore_index, self.thresh,
+                                             self.min_kept, self.keep_fraction)
         terms = {}
         if self.region is not None:
             terms.update(region=self.region, region_weight=self.region_weight, region_smooth=self.region_smooth,
@@ -115,4 +130,6 @@ class SegmCrossEntropy(nn.Module):
                 self.region, self.region_weight, self.region_smooth, self.region_classes)
         if self.lovasz_weight is not None:
             s += ", lovasz_weight={}, lovasz_classes={!r}".format(self.lovasz_weight, self.lovasz_classes)
+        if self.full_size:
+            s += ", full_size=True"
         return s
