@@ -696,6 +696,22 @@ int nasseg_graph_run(int n_ops, const int64_t* ops, void* stream);
  * (NHWC) and mask uint8 [B][Ho][Wo] (mask null: no mask is written). */
 int nasseg_augment(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps, const float* lut,
                    float* image, uint8_t* mask, int B, int Ho, int Wo, void* stream);
+/* The same launch for a metric depth target instead of a label map (data/device.py: run_depth_batch).  The image
+ * half - src, desc, taps, lut, image - is nasseg_augment's, bit for bit.  The "mask" windows of src hold LITTLE-ENDIAN
+ * 16-BIT COUNTS: h rows of w counts, the mask row stride of desc in BYTES and at least 2 w; desc's mask fill is not
+ * read.  params fp32 [B][2] = {zoom, fill} per sample; depth_scale: metres per count, one value per launch.  Writes
+ * target fp32 [B][Ho][Wo] whatever the image's storage type:
+ *   both nearest indices >= 0:  target = fdiv_rn(fmul_rn((float)count, depth_scale), zoom[b]) - two correctly rounded
+ *                               fp32 operations, no contraction, no reciprocal: numpy's float32 product and quotient
+ *                               (data/datasets.py: _load_depth, DepthResizeScale), bit for bit; zoom 1.0 is exact;
+ *   a fill pixel (an index -1, or a window that does not lie inside src):  target = fill[b], written as it is and NOT
+ *                               divided (host pipelines pad after the resize).
+ * Every load stays inside src whatever desc holds.  A packed target window may start at an odd byte (after an image
+ * of odd 3 h w bytes): the kernel reads a count as two byte loads, so offsets and strides need no alignment and no
+ * 16-bit load of a count is ever issued.  One thread per output pixel, blockIdx.y = sample, 256 threads. */
+int nasseg_augment_depth(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
+                         const float* lut, const float* params, float depth_scale, float* image, float* target,
+                         int B, int Ho, int Wo, void* stream);
 
 /* ---- prediction post-processing: cv2.resize(logits, dsize, interpolation=INTER_CUBIC) (float branch) of the
  * reference's inference notebooks, then argmax for segmentation (engine/predict.py) ------------------------------
@@ -948,6 +964,9 @@ int nasseg_bf16_conv_wgrad(const nasseg_bf16_t* x, int ldx, const nasseg_bf16_t*
 int nasseg_bf16_augment(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
                         const nasseg_bf16_t* lut, nasseg_bf16_t* image, uint8_t* mask, int B, int Ho, int Wo,
                         void* stream);
+int nasseg_bf16_augment_depth(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
+                              const nasseg_bf16_t* lut, const float* params, float depth_scale, nasseg_bf16_t* image,
+                              float* target, int B, int Ho, int Wo, void* stream);
 int nasseg_bf16_resize_cubic(const nasseg_bf16_t* x, int B, int h, int w, int C, const int* taps, const float* coef,
                              float* y, int H, int W, void* stream);
 int nasseg_bf16_resize_cubic_argmax(const nasseg_bf16_t* x, int B, int h, int w, int C, const int* taps,

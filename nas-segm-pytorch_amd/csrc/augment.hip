@@ -5,6 +5,14 @@
 // the uploaded source window, so the kernel only adds integers: the result is exact by construction, whatever the
 // summation order.  The uint8 result v of channel c becomes lut[c][v] (Normalise evaluated by the host in float64
 // and cast to act_t there).
+//
+// augment_depth_kernel is the same launch for a metric depth target instead of a label map: the image half is the
+// one function both kernels call (augment_image); the target windows hold little-endian 16-bit counts and the output
+// is fp32 metres, count * depth_scale / zoom[b], each operation rounded once as numpy's float32 product and quotient
+// are (__fmul_rn, __fdiv_rn: no contraction, no reciprocal), or the sample's fill, written as it is.  A packed target
+// window may start at any byte (an image of odd 3 h w bytes precedes it), so a count is read as TWO BYTE LOADS and
+// put together in a register: the target half issues no 16-bit load, aligned or not, and the host packs without
+// padding.
 #include "common.h"
 
 namespace {
@@ -12,41 +20,19 @@ namespace {
 // per-sample descriptor: int64 [AUG_DESC]
 enum { AUG_IMG_OFF, AUG_MSK_OFF, AUG_H, AUG_W, AUG_IMG_LD, AUG_MSK_LD, AUG_IMG_FILL, AUG_MSK_FILL, AUG_DESC };
 
-// one thread per output pixel of one sample (blockIdx.y), the pixels of a sample in row-major order: a wave writes
-// 64 consecutive pixels (768 contiguous bytes of fp32 image, 64 of mask), and the few output rows a workgroup
-// covers read the same four source rows, which stay in L1 / L2 between the lanes that share them.
-__global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
-                                                      const int64_t* __restrict__ desc,
-                                                      const int* __restrict__ taps,
-                                                      const act_t* __restrict__ lut, act_t* __restrict__ image,
-                                                      uint8_t* __restrict__ mask, int Ho, int Wo) {
-  __shared__ act_t slut[3 * 256];
-  for (int i = threadIdx.x; i < 3 * 256; i += 256) slut[i] = lut[i];
-  __syncthreads();
-
-  const int b = blockIdx.y;
-  const int64_t npix = (int64_t)Ho * Wo;
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= npix) return;
-  const int oy = (int)(p / Wo), ox = (int)(p - (int64_t)oy * Wo);
-
-  const int64_t* d = desc + (int64_t)b * AUG_DESC;
-  const int64_t img_off = d[AUG_IMG_OFF], msk_off = d[AUG_MSK_OFF];
-  const int h = (int)d[AUG_H], w = (int)d[AUG_W];
-  const int64_t img_ld = d[AUG_IMG_LD], msk_ld = d[AUG_MSK_LD];
-  const int img_fill = (int)d[AUG_IMG_FILL], msk_fill = (int)d[AUG_MSK_FILL];
+// The image half of one output pixel (oy, ox) of a sample (its image window: the descriptor's img_off, h, w, img_ld
+// and img_fill; its tables t): OpenCV's fixed-point bicubic of the four by four taps (or the fill), through the table
+// in LDS, to the pixel's three values at o.  Every kernel of this file calls it.
+__device__ __forceinline__ void augment_image(const uint8_t* __restrict__ src, int64_t src_bytes, int64_t img_off,
+                                              int h, int w, int64_t img_ld, int img_fill, const int* __restrict__ t,
+                                              const act_t* slut, act_t* __restrict__ o, int oy, int ox, int Ho) {
   // a window that does not lie inside the buffer is read as fill (the host checks before it launches; this
   // keeps every load in bounds whatever it is handed)
   const bool img_ok = h > 0 && w > 0 && img_off >= 0 && img_ld >= 3 * (int64_t)w &&
                       img_off + (h - 1) * img_ld + 3 * (int64_t)w <= src_bytes;
-  const bool msk_ok = h > 0 && w > 0 && msk_off >= 0 && msk_ld >= w &&
-                      msk_off + (h - 1) * msk_ld + w <= src_bytes;
 
-  // tables of the sample: rows [Ho][8], columns [Wo][8] (4 indices, 4 coefficients), mask rows [Ho], columns [Wo]
-  const int* t = taps + (int64_t)b * (9 * (Ho + Wo));
   const int* ty = t + oy * 8;
   const int* tx = t + Ho * 8 + ox * 8;
-  const int my = t[8 * (Ho + Wo) + oy], mx = t[8 * (Ho + Wo) + Ho + ox];
 
   int v[3];
   if (ty[0] < 0 || tx[0] < 0 || !img_ok) {
@@ -82,15 +68,96 @@ __global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict_
       v[c] = (int)(r < 0 ? 0 : (r > 255 ? 255 : r));
     }
   }
-  act_t* o = image + ((int64_t)b * npix + p) * 3;
   o[0] = slut[v[0]];
   o[1] = slut[256 + v[1]];
   o[2] = slut[512 + v[2]];
+}
+
+// one thread per output pixel of one sample (blockIdx.y), the pixels of a sample in row-major order: a wave writes
+// 64 consecutive pixels (768 contiguous bytes of fp32 image, 64 of mask), and the few output rows a workgroup
+// covers read the same four source rows, which stay in L1 / L2 between the lanes that share them.
+__global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                      const int64_t* __restrict__ desc,
+                                                      const int* __restrict__ taps,
+                                                      const act_t* __restrict__ lut, act_t* __restrict__ image,
+                                                      uint8_t* __restrict__ mask, int Ho, int Wo) {
+  __shared__ act_t slut[3 * 256];
+  for (int i = threadIdx.x; i < 3 * 256; i += 256) slut[i] = lut[i];
+  __syncthreads();
+
+  const int b = blockIdx.y;
+  const int64_t npix = (int64_t)Ho * Wo;
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= npix) return;
+  const int oy = (int)(p / Wo), ox = (int)(p - (int64_t)oy * Wo);
+
+  const int64_t* d = desc + (int64_t)b * AUG_DESC;
+  const int64_t img_off = d[AUG_IMG_OFF], msk_off = d[AUG_MSK_OFF];
+  const int h = (int)d[AUG_H], w = (int)d[AUG_W];
+  const int64_t img_ld = d[AUG_IMG_LD], msk_ld = d[AUG_MSK_LD];
+  const int img_fill = (int)d[AUG_IMG_FILL], msk_fill = (int)d[AUG_MSK_FILL];
+  const bool msk_ok = h > 0 && w > 0 && msk_off >= 0 && msk_ld >= w &&
+                      msk_off + (h - 1) * msk_ld + w <= src_bytes;
+
+  // tables of the sample: rows [Ho][8], columns [Wo][8] (4 indices, 4 coefficients), mask rows [Ho], columns [Wo]
+  const int* t = taps + (int64_t)b * (9 * (Ho + Wo));
+  const int my = t[8 * (Ho + Wo) + oy], mx = t[8 * (Ho + Wo) + Ho + ox];
+
+  augment_image(src, src_bytes, img_off, h, w, img_ld, img_fill, t, slut, image + ((int64_t)b * npix + p) * 3, oy, ox,
+                Ho);
 
   if (!mask) return;  // (an image without a mask: F.prepare_image)
   int m = msk_fill & 255;
   if (my >= 0 && mx >= 0 && msk_ok) m = src[msk_off + (int64_t)min(my, h - 1) * msk_ld + min(mx, w - 1)];
   mask[(int64_t)b * npix + p] = (uint8_t)m;
+}
+
+// The same launch for a depth target (see the head of the file): the target window of sample b holds h rows of w
+// little-endian 16-bit counts, msk_ld BYTES apart (>= 2 w); params [B][2] = {zoom, fill} in fp32.  A wave writes 64
+// consecutive floats of the target (256 contiguous bytes) next to its 768 bytes of fp32 image.  The descriptor's
+// mask fill is not read.
+__global__ __launch_bounds__(256) void augment_depth_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                            const int64_t* __restrict__ desc,
+                                                            const int* __restrict__ taps,
+                                                            const act_t* __restrict__ lut,
+                                                            const float* __restrict__ params, float depth_scale,
+                                                            act_t* __restrict__ image, float* __restrict__ target,
+                                                            int Ho, int Wo) {
+  __shared__ act_t slut[3 * 256];
+  for (int i = threadIdx.x; i < 3 * 256; i += 256) slut[i] = lut[i];
+  __syncthreads();
+
+  const int b = blockIdx.y;
+  const int64_t npix = (int64_t)Ho * Wo;
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= npix) return;
+  const int oy = (int)(p / Wo), ox = (int)(p - (int64_t)oy * Wo);
+
+  const int64_t* d = desc + (int64_t)b * AUG_DESC;
+  const int64_t img_off = d[AUG_IMG_OFF], msk_off = d[AUG_MSK_OFF];
+  const int h = (int)d[AUG_H], w = (int)d[AUG_W];
+  const int64_t img_ld = d[AUG_IMG_LD], msk_ld = d[AUG_MSK_LD];
+  const int img_fill = (int)d[AUG_IMG_FILL];
+  // (the last byte read is the high byte of the last count of the last row)
+  const bool msk_ok = h > 0 && w > 0 && msk_off >= 0 && msk_off <= src_bytes && msk_ld >= 2 * (int64_t)w &&
+                      msk_ld <= src_bytes && msk_off + (h - 1) * msk_ld + 2 * (int64_t)w <= src_bytes;
+  const int* t = taps + (int64_t)b * (9 * (Ho + Wo));
+  const int my = t[8 * (Ho + Wo) + oy], mx = t[8 * (Ho + Wo) + Ho + ox];
+
+  augment_image(src, src_bytes, img_off, h, w, img_ld, img_fill, t, slut, image + ((int64_t)b * npix + p) * 3, oy, ox,
+                Ho);
+
+  float v = params[2 * b + 1];  // the fill: a pad comes after the resize on the host, so it is not divided
+  if (my >= 0 && mx >= 0 && msk_ok) {
+    const uint8_t* c = src + msk_off + (int64_t)min(my, h - 1) * msk_ld + 2 * (int64_t)min(mx, w - 1);
+    // two byte loads that stay two: the compiler fuses adjacent byte loads into one 16-bit load (here at an address
+    // that may be odd) when it can see that they are adjacent, so the high byte's offset passes through an empty asm
+    int hi_at = 1;
+    asm volatile("" : "+v"(hi_at));
+    const int count = (int)c[0] | ((int)c[hi_at] << 8);
+    v = __fdiv_rn(__fmul_rn((float)count, depth_scale), params[2 * b]);
+  }
+  target[(int64_t)b * npix + p] = v;
 }
 
 }  // namespace
@@ -106,6 +173,20 @@ int NASSEG_FN(augment)(const uint8_t* src, int64_t src_bytes, const int64_t* des
   hipLaunchKernelGGL(augment_kernel, dim3((unsigned)cdiv64(npix, 256), B), dim3(256), 0, (hipStream_t)stream, src,
                      src_bytes, desc, taps, lut, image, mask, Ho, Wo);
   NASSEG_LAUNCH_CHECK("augment");
+  return NASSEG_OK;
+}
+
+int NASSEG_FN(augment_depth)(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
+                             const act_t* lut, const float* params, float depth_scale, act_t* image, float* target,
+                             int B, int Ho, int Wo, void* stream) {
+  NASSEG_REQUIRE(B > 0 && B <= 65535 && Ho > 0 && Wo > 0 && src_bytes > 0, "augment_depth: bad shape");
+  NASSEG_REQUIRE(params != nullptr && target != nullptr, "augment_depth: params and target are required");
+  NASSEG_REQUIRE((int64_t)9 * (Ho + Wo) < ((int64_t)1 << 31), "augment_depth: output too large");
+  const int64_t npix = (int64_t)Ho * Wo;
+  NASSEG_REQUIRE(cdiv64(npix, 256) < ((int64_t)1 << 31), "augment_depth: output too large");
+  hipLaunchKernelGGL(augment_depth_kernel, dim3((unsigned)cdiv64(npix, 256), B), dim3(256), 0, (hipStream_t)stream,
+                     src, src_bytes, desc, taps, lut, params, depth_scale, image, target, Ho, Wo);
+  NASSEG_LAUNCH_CHECK("augment_depth");
   return NASSEG_OK;
 }
 

@@ -16,6 +16,12 @@ a resize after a window operation (crop, mirror, pad), more than one pad, ``Norm
 last two operations, an operation this module does not know.  Samples it cannot reproduce are refused when they
 arrive: images that are not 3-channel uint8 (the float branch of resize_cubic; RGBA), masks that are not 2-D uint8
 of the image's size.
+
+Depth (``create_device_depth_loaders``, the twin of ``loaders.create_depth_loaders``): the target is a map of 16-bit
+counts, shipped as little-endian bytes; ``functional.augment_depth`` gathers it with the mask's nearest indices and
+writes fp32 metres - count * depth_scale, divided by the fp32 zoom factor where the resize is a DepthResizeScale -
+with the two correctly rounded fp32 operations the host pipeline makes, so the targets are the host's bit for bit
+too.  ``plan_sample`` keeps refusing every mask that is not uint8; depth samples go through ``plan_depth_sample``.
 """
 import numpy as np
 import torch
@@ -42,6 +48,8 @@ class _Plan(object):
         self.cols = np.arange(width, dtype=np.int64)
         self.img_fill = np.zeros(3, np.uint8)
         self.msk_fill = 0
+        self.zoom = np.float32(1.0)  # what a depth target is divided by (a DepthResizeScale's factor, in fp32)
+        self.depth_fill = np.float32(0.0)  # a pad's fill of a depth target
         self.lut = None
 
     @property
@@ -67,6 +75,11 @@ def _plan_resize_scale(op, plan):
     if beyond:
         scale = op.resize_side * 1.0 / side
     plan.resize(scale)
+
+
+def _plan_depth_resize_scale(op, plan):
+    _plan_resize_scale(op, plan)
+    plan.zoom = np.float32(plan.scale)  # D.DepthResizeScale's divisor: the limited factor
 
 
 def _plan_resize_shorter(op, plan):
@@ -101,6 +114,7 @@ def _plan_pad(op, plan):
     # cast as D._framed casts: the image's fill per channel to uint8, the mask's to the mask's dtype (uint8)
     plan.img_fill = np.broadcast_to(np.asarray(op.img_val[:3]).astype(np.uint8), (3,)).copy()
     plan.msk_fill = int(np.asarray(op.msk_val).astype(np.uint8))
+    plan.depth_fill = np.float32(op.msk_val)  # (a float32 target: D._framed casts to float32)
 
 
 def normalise_table(op):
@@ -136,6 +150,7 @@ def _plan_to_tensor(op, plan):
 
 _PLANNERS = {
     D.ResizeScale: _plan_resize_scale,
+    D.DepthResizeScale: _plan_depth_resize_scale,
     D.ResizeShorter: _plan_resize_shorter,
     D.RandomMirror: _plan_mirror,
     D.RandomCrop: _plan_random_crop,
@@ -144,7 +159,7 @@ _PLANNERS = {
     D.Normalise: _plan_normalise,
     D.ToTensor: _plan_to_tensor,
 }
-_RESIZES = (D.ResizeScale, D.ResizeShorter)
+_RESIZES = (D.ResizeScale, D.DepthResizeScale, D.ResizeShorter)
 _WINDOWS = (D.RandomMirror, D.RandomCrop, D.CentralCrop, D.Pad)
 
 
@@ -169,12 +184,16 @@ def check_pipeline(pipeline):
     return ops
 
 
-def check_sample(image, mask):
-    """ValueError for samples the kernel does not reproduce"""
+def _check_image(image):
     if not isinstance(image, np.ndarray) or image.dtype != np.uint8:
         raise ValueError("device pipeline: images must be uint8 (got {})".format(getattr(image, "dtype", image)))
     if image.ndim != 3 or image.shape[2] != 3:
         raise ValueError("device pipeline: images must be HxWx3 (got {})".format(image.shape))
+
+
+def check_sample(image, mask):
+    """ValueError for samples the kernel does not reproduce"""
+    _check_image(image)
     if not isinstance(mask, np.ndarray) or mask.dtype != np.uint8:
         raise ValueError("device pipeline: masks must be uint8 (got {})".format(getattr(mask, "dtype", mask)))
     if mask.shape != image.shape[:2]:
@@ -230,6 +249,24 @@ def tables(p):
 # ---------------------------------------------------------------------------
 # dataset, batches, loader
 # ---------------------------------------------------------------------------
+class DeviceDepthDataset(D.DepthDataset):
+    """DepthDataset whose samples are plans (``plan_depth_sample``): the workers decode the image and the 16-bit
+    depth file - the counts stay integers; the metres are made on the GPU - and plan the stage's pipeline."""
+
+    def __init__(self, data_file, data_dir, transform_trn=None, transform_val=None, depth_scale=1e-3):
+        for pipeline in (transform_trn, transform_val):
+            if pipeline is not None:
+                check_pipeline(pipeline)
+        super(DeviceDepthDataset, self).__init__(data_file, data_dir, transform_trn, transform_val, depth_scale)
+
+    def __getitem__(self, idx):
+        image_file, depth_file = self._files(idx)
+        pipeline = getattr(self, self._PIPELINE_OF_STAGE.get(self.stage, ""), None)
+        if pipeline is None:
+            raise ValueError("device pipeline: stage {!r} has no pipeline".format(self.stage))
+        return plan_depth_sample(pipeline, D._load_rgb(image_file), D._load_depth_counts(depth_file))
+
+
 class DevicePascalDataset(D.PascalCustomDataset):
     """PascalCustomDataset whose samples are plans: ``__getitem__`` (in the DataLoader workers) decodes the files,
     plans the stage's pipeline and returns {"image": uint8 window of the source, "mask": its window, "taps",
@@ -264,6 +301,25 @@ def plan_sample(pipeline, image, mask):
             "lut": p.lut, "size": p.shape}
 
 
+def plan_depth_sample(pipeline, image, counts):
+    """the device sample of (image, 16-bit depth counts) under ``pipeline``: ``plan_sample``'s, with the window of
+    the counts as "mask" (little-endian uint16) and "params" = fp32 (zoom, fill): what the target is divided by (a
+    DepthResizeScale's factor, else 1) and what a Pad's fill pixels become (its ``msk_val``, else 0)."""
+    _check_image(image)
+    if not isinstance(counts, np.ndarray) or counts.dtype != np.uint16 or counts.ndim != 2:
+        raise ValueError("device pipeline: depth targets must be 2-D uint16 counts (got {} of {})".format(
+            getattr(counts, "shape", None), getattr(counts, "dtype", type(counts).__name__)))
+    if counts.shape != image.shape[:2]:
+        raise ValueError("device pipeline: the depth target must be HxW of its image (got {} for {})".format(
+            counts.shape, image.shape))
+    p = plan(pipeline, image.shape[0], image.shape[1])
+    (r0, r1), (c0, c1), taps = tables(p)
+    return {"image": np.ascontiguousarray(image[r0:r1, c0:c1]),
+            "mask": np.ascontiguousarray(counts[r0:r1, c0:c1], dtype="<u2"), "taps": taps,
+            "fill": (int(p.img_fill[0]) | int(p.img_fill[1]) << 8 | int(p.img_fill[2]) << 16, 0),
+            "params": np.array([p.zoom, p.depth_fill], np.float32), "lut": p.lut, "size": p.shape}
+
+
 def collate(samples):
     """a list of device samples -> {"src": uint8 [bytes], "desc": int64 [B][8], "taps": int32 [B][9 (Ho + Wo)],
     "lut": float64 [3][256], "size": int64 [2]} (tensors the DataLoader can pin)"""
@@ -281,12 +337,21 @@ def collate(samples):
     for i, s in enumerate(samples):
         img, msk = s["image"], s["mask"]
         h, w = msk.shape
-        desc[i] = (off, off + img.nbytes, h, w, 3 * w, w, s["fill"][0], s["fill"][1])
-        chunks += [img.reshape(-1), msk.reshape(-1)]
+        # (row strides in bytes: uint8 label maps, or the little-endian uint16 counts of a depth sample)
+        desc[i] = (off, off + img.nbytes, h, w, 3 * w, msk.itemsize * w, s["fill"][0], s["fill"][1])
+        chunks += [img.reshape(-1), msk.reshape(-1).view(np.uint8)]
         off += img.nbytes + msk.nbytes
     return {"src": torch.from_numpy(np.concatenate(chunks)), "desc": torch.from_numpy(desc),
             "taps": torch.from_numpy(np.stack([s["taps"] for s in samples])), "lut": torch.from_numpy(lut),
             "size": torch.tensor(size, dtype=torch.int64)}
+
+
+def collate_depth(samples):
+    """a list of depth samples -> ``collate``'s batch, the count windows packed as bytes wherever they fall (no
+    padding: the kernel reads a count as two bytes), plus "params": float32 [B][2]"""
+    batch = collate(samples)
+    batch["params"] = torch.from_numpy(np.stack([s["params"] for s in samples]).astype(np.float32))
+    return batch
 
 
 def run_batch(batch, device, dtype):
@@ -299,6 +364,19 @@ def run_batch(batch, device, dtype):
     up = {k: batch[k].to(device, non_blocking=True) for k in ("src", "desc", "taps")}
     image, mask = F.augment(up["src"], up["desc"], up["taps"], lut.to(device, non_blocking=True), Ho, Wo)
     return {"image": image, "mask": mask}
+
+
+def run_depth_batch(batch, device, dtype, depth_scale):
+    """one packed depth batch -> {"image": B x 3 x Ho x Wo channels_last ``dtype``, "mask": B x Ho x Wo float32
+    metres} on ``device`` (uploads on the current stream, one augment_depth launch)"""
+    from .. import functional as F
+
+    Ho, Wo = (int(v) for v in batch["size"])
+    lut = batch["lut"].to(dtype)
+    up = {k: batch[k].to(device, non_blocking=True) for k in ("src", "desc", "taps", "params")}
+    image, target = F.augment_depth(up["src"], up["desc"], up["taps"], lut.to(device, non_blocking=True),
+                                    up["params"], depth_scale, Ho, Wo)
+    return {"image": image, "mask": target}
 
 
 class DeviceLoader(object):
@@ -323,12 +401,30 @@ class DeviceLoader(object):
     def __iter__(self):
         device = self.device or torch.device("cuda", torch.cuda.current_device())
         for batch in self.loader:
-            yield run_batch(batch, device, self.dtype)
+            yield self.run(batch, device)
+
+    def run(self, batch, device):
+        return run_batch(batch, device, self.dtype)
+
+
+class DeviceDepthLoader(DeviceLoader):
+    """DeviceLoader for the packed batches of a DeviceDepthDataset"""
+
+    def __init__(self, loader, device=None, dtype=torch.float32, depth_scale=1e-3):
+        super(DeviceDepthLoader, self).__init__(loader, device, dtype)
+        self.depth_scale = depth_scale
+
+    def run(self, batch, device):
+        return run_depth_batch(batch, device, self.dtype, self.depth_scale)
+
+
+def _data_loader(dataset, batch_size, shuffle, args, collate_fn):
+    return DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, num_workers=args.num_workers,
+                      pin_memory=True, drop_last=True, collate_fn=collate_fn)
 
 
 def _loader(dataset, batch_size, shuffle, args, device, dtype):
-    return DeviceLoader(DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, num_workers=args.num_workers,
-                                   pin_memory=True, drop_last=True, collate_fn=collate), device, dtype)
+    return DeviceLoader(_data_loader(dataset, batch_size, shuffle, args, collate), device, dtype)
 
 
 def create_device_loaders(args, device=None, dtype=torch.float32):
@@ -348,6 +444,30 @@ def create_device_loaders(args, device=None, dtype=torch.float32):
                len(val_part), "search split" if do_search else "separate lists")
     return (_loader(train_part, args.batch_size[0], True, args, device, dtype),
             _loader(val_part, args.val_batch_size, False, args, device, dtype), do_search)
+
+
+def create_device_depth_loaders(args, device=None, dtype=torch.float32, depth_scale=1e-3, zoom_depth=True):
+    """create_depth_loaders(args, depth_scale, zoom_depth) (loaders.py) with the augmentation on the GPU: the same
+    ``args`` fields, search-mode split, shuffling and drop_last, the same batches (``image`` as ``dtype`` on
+    ``device``, channels_last; ``mask`` float32 metres on ``device``) -> (train_loader, val_loader, do_search)."""
+    val_ops = L._pipeline(L._VAL_OPS, args)
+    full = DeviceDepthDataset(args.train_list, args.train_dir, L._depth_train_pipeline(args, zoom_depth), val_ops,
+                              depth_scale)
+    do_search = args.train_list == args.val_list
+    if do_search:
+        n_train = int(len(full) * args.meta_train_prct / 100.0)
+        train_part, val_part = random_split(full, [n_train, len(full) - n_train])
+    else:
+        train_part = full
+        val_part = DeviceDepthDataset(args.val_list, args.val_dir, None, val_ops, depth_scale)
+    L.log.info("depth data (device augmentation): %d training / %d validation samples (%s)", len(train_part),
+               len(val_part), "search split" if do_search else "separate lists")
+
+    def loader(part, batch_size, shuffle):
+        return DeviceDepthLoader(_data_loader(part, batch_size, shuffle, args, collate_depth), device, dtype,
+                                 depth_scale)
+
+    return loader(train_part, args.batch_size[0], True), loader(val_part, args.val_batch_size, False), do_search
 
 
 def create_loaders(args):

@@ -56,3 +56,36 @@ def create_loaders(args):
              "search split" if do_search else "separate lists")
     return (_loader(train_part, args.batch_size[0], True, args),
             _loader(val_part, args.val_batch_size, False, args), do_search)
+
+
+
+def _depth_train_pipeline(args, zoom_depth):
+    """the training pipeline with a DepthResizeScale at position 0 (``zoom_depth``), else as it is"""
+    pipeline = _pipeline(_TRAIN_OPS, args)
+    if zoom_depth:
+        op = pipeline.transforms[0]
+        pipeline.transforms[0] = D.DepthResizeScale(op.resize_side, op.low_scale, op.high_scale, op.longer)
+    return pipeline
+
+
+def create_depth_loaders(args, depth_scale=1e-3, zoom_depth=True):
+    """``create_loaders`` for depth: the list files name ``image<TAB>depth`` pairs, depth files hold 16-bit counts
+    (metres = count * ``depth_scale``, 0 = hole) -> (train_loader, val_loader, do_search) whose batches are
+    {"image": float B x 3 x H x W, "mask": float32 B x H x W metres} - what ``train_segmenter`` with an
+    nn.BerHuLoss and ``validate_depth`` take.  The same ``args`` fields, search-mode split (one ``random_split``
+    draw), shuffling and drop_last.  ``zoom_depth``: the training pipeline's random zoom divides the target by its
+    factor (DepthResizeScale); the validation pipeline never does - its scores are in true metres."""
+    val_ops = _pipeline(_VAL_OPS, args)
+    full = D.DepthDataset(args.train_list, args.train_dir, _depth_train_pipeline(args, zoom_depth), val_ops,
+                          depth_scale)
+    do_search = args.train_list == args.val_list
+    if do_search:
+        n_train = int(len(full) * args.meta_train_prct / 100.0)
+        train_part, val_part = random_split(full, [n_train, len(full) - n_train])
+    else:
+        train_part = full
+        val_part = D.DepthDataset(args.val_list, args.val_dir, None, val_ops, depth_scale)
+    log.info("depth data: %d training / %d validation samples (%s)", len(train_part), len(val_part),
+             "search split" if do_search else "separate lists")
+    return (_loader(train_part, args.batch_size[0], True, args),
+            _loader(val_part, args.val_batch_size, False, args), do_search)

@@ -3218,6 +3218,27 @@ def augment(src, desc, taps, lut, Ho, Wo):
     return image, mask
 
 
+def augment_depth(src, desc, taps, lut, params, depth_scale, Ho, Wo):
+    """``augment`` for a metric depth target: the "mask" windows of ``src`` hold little-endian 16-bit counts (row
+    stride in bytes), fp32 ``params`` [B][2] = {zoom, fill} per sample, ``depth_scale`` metres per count -> (image
+    B x 3 x Ho x Wo channels_last of the table's dtype - ``augment``'s, bit for bit -, target fp32 B x Ho x Wo =
+    count * depth_scale / zoom in correctly rounded fp32, or the fill undivided); one nasseg_augment_depth launch
+    (include/nasseg.h)."""
+    require_device(src, desc, taps, lut, params)
+    B = desc.shape[0] if desc.dim() == 2 else 0
+    if (src.dtype != torch.uint8 or desc.dtype != torch.int64 or taps.dtype != torch.int32
+            or lut.dtype not in (torch.float32, torch.bfloat16) or src.dim() != 1 or B == 0
+            or tuple(desc.shape) != (B, 8) or tuple(taps.shape) != (B, 9 * (Ho + Wo)) or tuple(lut.shape) != (3, 256)
+            or params.dtype != torch.float32 or tuple(params.shape) != (B, 2)
+            or not all(t.is_contiguous() for t in (src, desc, taps, lut, params))):
+        raise NassegError("augment_depth: bad packed batch")
+    image = torch.empty((B, 3, Ho, Wo), device=src.device, dtype=lut.dtype, memory_format=torch.channels_last)
+    target = torch.empty((B, Ho, Wo), device=src.device, dtype=torch.float32)
+    lib.call(_k("nasseg_augment_depth", lut), ptr(src), src.numel(), ptr(desc), ptr(taps), ptr(lut), ptr(params),
+             float(depth_scale), ptr(image), ptr(target), B, Ho, Wo, current_stream())
+    return image, target
+
+
 def argmax_confusion(logits, gt, n_classes, cm=None, out_size=None, return_preds=False):
     """Fused bilinear up-sampling -> argmax -> uint8 -> confusion-matrix update.
 

@@ -8,8 +8,13 @@
            create_device_loaders, WACV training pipeline, batch 32, 16 workers, on synthetic 2048 x 1024 PNGs written
            to a temporary directory.  The first batch (worker start-up) is not counted.
 
-usage (GPU box): python tools/kbench_augment.py [kernel|loader|all]   (KBENCH_BATCHES: loader batches, default 24)
-One JSON line per measurement on stdout."""
+  --depth  the depth twins: us per batch of nasseg_augment_depth at 32 x 320 x 320 (DepthResizeScale(320, 0.7, 1.4)
+           -> RandomMirror -> RandomCrop(320) on 640 x 480 sources; fp32 and bf16 image), and images/s of
+           create_depth_loaders against create_device_depth_loaders on synthetic 640 x 480 RGB + 16-bit depth PNG
+           pairs written to a temporary directory (batch 32, 16 workers, first batch not counted).
+
+usage (GPU box): python tools/kbench_augment.py [kernel|loader|all] [--depth]   (KBENCH_BATCHES: loader batches,
+default 24).  One JSON line per measurement on stdout."""
 import json
 import os
 import sys
@@ -126,9 +131,106 @@ def time_loaders(n_batches):
         print(json.dumps({"loader": "device_over_host", "ratio": round(results["device"] / results["host"], 2)}))
 
 
+def synthetic_depth(rng, h=480, w=640):
+    """an indoor-like pair: the image of ``synthetic`` and 16-bit counts (millimetres) of a tilted plane with noise
+    and holes (0) along an edge and in specks"""
+    img, _ = synthetic(rng, h, w)
+    yy, xx = np.mgrid[0:h, 0:w]
+    counts = 1500 + 4 * xx + 3 * yy + rng.randint(-20, 21, (h, w))
+    counts[:, :12] = 0
+    counts[rng.rand(h, w) < 0.03] = 0
+    return img, counts.astype(np.uint16)
+
+
+def depth_args(tmp, lst, B, workers):
+    return types.SimpleNamespace(
+        train_dir=tmp, val_dir=tmp, train_list=lst, val_list=lst + ".val", meta_train_prct=80, resize_side=[320],
+        low_scale=0.7, high_scale=1.4, resize_longer_side=False, crop_size=[320], val_resize_side=480,
+        val_crop_size=480, normalise_params=list(NORM), batch_size=[B], val_batch_size=B, num_workers=workers)
+
+
+def time_depth_kernel(n=50):
+    rng = np.random.RandomState(0)
+    sources = [synthetic_depth(rng) for _ in range(4)]
+    pipe = D.Compose([D.DepthResizeScale(320, 0.7, 1.4), D.RandomMirror(), D.RandomCrop(320), D.Normalise(*NORM),
+                      D.ToTensor()])
+    B = 32
+    np.random.seed(0)
+    batch = dev.collate_depth([dev.plan_depth_sample(pipe, *sources[i % 4]) for i in range(B)])
+    Ho, Wo = (int(v) for v in batch["size"])
+    up = {k: batch[k].to(DEV) for k in ("src", "desc", "taps", "params")}
+    for dtype in (torch.float32, torch.bfloat16):
+        lut = batch["lut"].to(dtype).to(DEV)
+        args = (up["src"], up["desc"], up["taps"], lut, up["params"], 1e-3, Ho, Wo)
+        for _ in range(3):
+            F.augment_depth(*args)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            F.augment_depth(*args)
+        e1.record()
+        torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) / n * 1e3
+        out_bytes = B * Ho * Wo * (3 * (4 if dtype == torch.float32 else 2) + 4)
+        print(json.dumps({"kernel": "depth_train_b32", "dtype": str(dtype)[6:], "B": B, "Ho": Ho, "Wo": Wo,
+                          "us": round(us, 1), "src_MB": round(up["src"].numel() / 1e6, 2),
+                          "out_GBps": round(out_bytes / us / 1e3, 1)}), flush=True)
+
+
+def time_depth_loaders(n_batches):
+    from nas_segm_amd.data import create_depth_loaders
+    from nas_segm_amd.engine.trainer import _depth_target, _to_device_image
+
+    rng = np.random.RandomState(1)
+    with tempfile.TemporaryDirectory() as tmp:
+        from PIL import Image
+
+        n_files = 32
+        for i in range(n_files):
+            img, counts = synthetic_depth(rng)
+            Image.fromarray(img).save(os.path.join(tmp, "i{}.png".format(i)), compress_level=1)
+            Image.fromarray(counts).save(os.path.join(tmp, "d{}.png".format(i)), compress_level=1)
+        B = 32
+        lst = os.path.join(tmp, "train.lst")
+        with open(lst, "w") as fh:
+            fh.write("".join("i{0}.png\td{0}.png\n".format(i % n_files) for i in range((n_batches + 1) * B)))
+        args = depth_args(tmp, lst, B, 16)
+        with open(args.val_list, "w") as fh:
+            fh.write("i0.png\td0.png\n")
+        results = {}
+        for name in ("host", "device"):
+            loader = (create_depth_loaders(args) if name == "host"
+                      else dev.create_device_depth_loaders(args, device=DEV))[0]
+            # (workers started with spawn: none of them inherits this process's open device)
+            (loader.loader if name == "device" else loader).multiprocessing_context = "spawn"
+            np.random.seed(0)
+            t0, seen = None, 0
+            for sample in loader:
+                if name == "host":
+                    image = _to_device_image(sample["image"], torch.device(DEV))
+                    target = _depth_target(sample["mask"], torch.device(DEV))
+                else:
+                    image, target = sample["image"], sample["mask"]
+                torch.cuda.synchronize()
+                if t0 is None:
+                    t0 = time.perf_counter()
+                else:
+                    seen += image.shape[0]
+            dt = time.perf_counter() - t0
+            results[name] = seen / dt
+            print(json.dumps({"depth_loader": name, "workers": 16, "batch": B, "images": seen, "s": round(dt, 2),
+                              "images_per_s": round(seen / dt, 1), "image": list(image.shape),
+                              "dtype": str(image.dtype)[6:], "target": str(target.dtype)[6:]}), flush=True)
+        print(json.dumps({"depth_loader": "device_over_host",
+                          "ratio": round(results["device"] / results["host"], 2)}))
+
+
 if __name__ == "__main__":
-    what = sys.argv[1] if len(sys.argv) > 1 else "all"
+    argv = [a for a in sys.argv[1:] if a != "--depth"]
+    depth = "--depth" in sys.argv[1:]
+    what = argv[0] if argv else "all"
     if what in ("kernel", "all"):
-        time_kernel()
+        (time_depth_kernel if depth else time_kernel)()
     if what in ("loader", "all"):
-        time_loaders(int(os.environ.get("KBENCH_BATCHES", "24")))
+        (time_depth_loaders if depth else time_loaders)(int(os.environ.get("KBENCH_BATCHES", "24")))
