@@ -10,18 +10,9 @@
 // gradient, so backward is a single scale.
 #include <math.h>
 
-#include "common.h"
+#include "loss_common.h"
 
 namespace {
-
-// Is a per-pixel loss that takes part (l >= 0; -1 marks the others) kept at threshold tau?  l >= tau on the fp32
-// values, compared through their bit patterns (for non-negative floats the order of the patterns is the order of
-// the values) so that the answer is the same integer comparison the radix selection below made, denormals included.
-// (csrc/loss_up.hip holds a copy, up_kept, and copies of ce_sel_sum_kernel / ce_sel_finalize_kernel: change them together.)
-__device__ __forceinline__ bool sel_kept(float l, float tau) {
-  if (l < 0.f) return false;
-  return !(tau > 0.f) || __float_as_uint(l) >= __float_as_uint(tau);
-}
 
 // The selection's histograms (3 x 2048 words, see sel_hist_kernel) back to zero, by whatever grid runs this: the
 // forward kernels of nasseg_ce_sel_fwd do it on their way, the selection's launches follow them.
@@ -56,7 +47,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const act_t* __restrict__ l
         const float d = lda1(lp + c) - teacher[p * C + c];
         sq += d * d;
       }
-    if (t == ignore || t < 0 || t >= C) {  // out-of-range labels are skipped, never read
+    if (NASSEG_LABEL_SKIPPED(t, C, ignore)) {
       if (SEL) pixel_loss[p] = -1.f;
       continue;
     }
@@ -217,7 +208,7 @@ __global__ __launch_bounds__(256) void ce_tile_kernel(const act_t* __restrict__ 
     if (tid < np) {
       float* row = tile + tid * CS;
       const int64_t tg = (int64_t)target[p0 + tid];
-      bool skip = tg == ignore || tg < 0 || tg >= C;
+      bool skip = NASSEG_LABEL_SKIPPED(tg, C, ignore);
       float gp = g;
       if (BWD && SEL && !skip) {
         skip = !sel_kept(pl, tau);
@@ -300,7 +291,6 @@ __global__ __launch_bounds__(256) void ce_tile_kernel(const act_t* __restrict__ 
     }
   }
 }
-constexpr int kCeTileMaxC = 63;
 
 // dlogits[p][c] = gscale[0] * (softmax(p)[c] - [c == target]) / nvalid   (0 for ignored pixels)
 // KD (nasseg_ce_mse_bwd): + gmse[0] * 2 (x - teacher) / (P*C) on every element, ignored pixels included.
@@ -323,7 +313,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const act_t* __restrict__ l
     const act_t* lp = logits + p * C;
     act_t* dp = dlogits + p * C;
     const float* tp = KD ? teacher + p * C : nullptr;
-    bool skip = t == ignore || t < 0 || t >= C;
+    bool skip = NASSEG_LABEL_SKIPPED(t, C, ignore);
     float gp = g;
     if (SEL && !skip) {
       skip = !sel_kept(pixel_loss[p], tau);
@@ -489,86 +479,6 @@ __global__ __launch_bounds__(256) void sel_count_kernel(const float* __restrict_
     atomicAdd(reinterpret_cast<unsigned long long*>(counts + 2), (unsigned long long)red[0]);
 }
 
-// Sum pass of nasseg_ce_sel_fwd over pixel_loss + labels: partial[b] = {sum w l, sum w, count} over the kept pixels
-// of workgroup b, with the pixel -> (workgroup, thread) mapping, the accumulation order and the tree of
-// ce_fwd_kernel: with unit weights and everything kept, the very sums of nasseg_ce_fwd.  tau == nullptr: no
-// selection, every valid pixel is kept.
-template <typename TL>
-__global__ __launch_bounds__(256) void ce_sel_sum_kernel(const float* __restrict__ pixel_loss,
-                                                         const TL* __restrict__ target,
-                                                         const float* __restrict__ weight, int64_t P,
-                                                         const float* __restrict__ tau,
-                                                         float* __restrict__ partial) {
-  __shared__ float red_l[256];
-  __shared__ float red_w[256];
-  __shared__ float red_n[256];
-  const float t = tau ? tau[0] : 0.f;
-  float loss = 0.f, sw = 0.f, cnt = 0.f;
-  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
-    const float l = pixel_loss[p];
-    if (!sel_kept(l, t)) continue;
-    const float w = weight ? weight[(int64_t)target[p]] : 1.f;  // (l >= 0: the label is in [0, C))
-    loss += w * l;
-    sw += w;
-    cnt += 1.f;
-  }
-  red_l[threadIdx.x] = loss;
-  red_w[threadIdx.x] = sw;
-  red_n[threadIdx.x] = cnt;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      red_l[threadIdx.x] += red_l[threadIdx.x + s];
-      red_w[threadIdx.x] += red_w[threadIdx.x + s];
-      red_n[threadIdx.x] += red_n[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    partial[blockIdx.x * 3] = red_l[0];
-    partial[blockIdx.x * 3 + 1] = red_w[0];
-    partial[blockIdx.x * 3 + 2] = red_n[0];
-  }
-}
-
-// loss = sum w l / sum w, stats = {sum w, tau}, counts[2] = kept pixels (selected: counts[0..1] and stats[1] are
-// the selection's; else k = n = kept and tau = -inf); the order of ce_finalize_kernel.
-__global__ __launch_bounds__(256) void ce_sel_finalize_kernel(const float* __restrict__ partial, int nblk,
-                                                              int selected, float* __restrict__ loss,
-                                                              float* __restrict__ stats,
-                                                              int64_t* __restrict__ counts) {
-  __shared__ double red_l[256];
-  __shared__ double red_w[256];
-  __shared__ double red_n[256];
-  double l = 0.0, w = 0.0, n = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += 256) {
-    l += (double)partial[b * 3];
-    w += (double)partial[b * 3 + 1];
-    n += (double)partial[b * 3 + 2];
-  }
-  red_l[threadIdx.x] = l;
-  red_w[threadIdx.x] = w;
-  red_n[threadIdx.x] = n;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      red_l[threadIdx.x] += red_l[threadIdx.x + s];
-      red_w[threadIdx.x] += red_w[threadIdx.x + s];
-      red_n[threadIdx.x] += red_n[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    loss[0] = (float)(red_l[0] / red_w[0]);
-    stats[0] = (float)red_w[0];
-    counts[2] = (int64_t)red_n[0];
-    if (!selected) {
-      stats[1] = -__builtin_inff();
-      counts[0] = counts[1] = (int64_t)red_n[0];
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------
 // Region-overlap term (soft Jaccard / Dice / Tversky; nasseg_ce_region_fwd / _bwd, definition: include/nasseg.h)
 // computed in the two passes over the logits the cross-entropy makes anyway.  Over the valid pixels, with
@@ -581,7 +491,7 @@ __global__ __launch_bounds__(256) void ce_sel_finalize_kernel(const float* __res
 // arithmetic and the cross-entropy gradient expression are copied from them, so that pixel_loss and, at
 // region_weight = 0, dlogits are bit-identical to nasseg_ce_sel_fwd's / _bwd's.
 // ---------------------------------------------------------------------------
-constexpr int kRegionRows = 1024;  // (= the cap of ce_grid)
+constexpr int kRegionRows = kCeGridCap;  // (a row per workgroup of the forward)
 
 // One [np][C] tile of logits into LDS rows of stride CS: the staging loops of ce_tile_kernel.
 __device__ __forceinline__ void region_stage(const act_t* __restrict__ src, float* __restrict__ tile, int nel, int C,
@@ -637,7 +547,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       bool valid = false;
       if (tid < np) {
         tg = (int64_t)target[p0 + tid];
-        valid = !(tg == ignore || tg < 0 || tg >= C);
+        valid = !NASSEG_LABEL_SKIPPED(tg, C, ignore);
       }
       if (valid) {
         float m = row[0];
@@ -729,7 +639,7 @@ __global__ __launch_bounds__(256) void region_fwd_kernel(const act_t* __restrict
     float m = 0.f, inv = 0.f;
     if (p < P) {
       t = (int64_t)target[p];
-      valid = !(t == ignore || t < 0 || t >= C);  // out-of-range labels are skipped, never read
+      valid = !NASSEG_LABEL_SKIPPED(t, C, ignore);
       if (valid) {
         m = lda1(lp);
         for (int c = 1; c < C; ++c) m = fmaxf(m, lda1(lp + c));
@@ -923,7 +833,7 @@ __global__ __launch_bounds__(256) void region_tile_bwd_kernel(const act_t* __res
     if (tid < np) {
       float* row = tile + tid * CS;
       const int64_t tg = (int64_t)target[p0 + tid];
-      if (tg == ignore || tg < 0 || tg >= C) {
+      if (NASSEG_LABEL_SKIPPED(tg, C, ignore)) {
         for (int c = 0; c < C; ++c) row[c] = 0.f;
       } else {
         const bool kept = with_ce && sel_kept(pl, tau);
@@ -989,7 +899,7 @@ __global__ __launch_bounds__(256) void region_bwd_kernel(const act_t* __restrict
     const int64_t t = (int64_t)target[p];
     const act_t* lp = logits + p * C;
     act_t* dp = dlogits + p * C;
-    if (t == ignore || t < 0 || t >= C) {
+    if (NASSEG_LABEL_SKIPPED(t, C, ignore)) {
       for (int c = 0; c < C; ++c) sta1(dp + c, 0.f);
       continue;
     }
@@ -1092,13 +1002,6 @@ __global__ __launch_bounds__(256) void berhu_bwd_kernel(const act_t* __restrict_
   }
 }
 
-inline int ce_grid(int64_t P) {
-  int64_t b = (P + 255) / 256;
-  if (b > 1024) b = 1024;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 // the selection's launches: [zero the histograms, unless an earlier launch did,] 3 x (histogram, scan); tau[0] and
 // counts[0..2] = {k, n, 0} after
 int sel_launch(const float* v, int64_t P, float t_loss, int64_t min_kept, double keep_fraction, float* tau,
@@ -1125,15 +1028,23 @@ int sel_launch(const float* v, int64_t P, float t_loss, int64_t min_kept, double
   return NASSEG_OK;
 }
 
+// ... as ce_sel_reduce's `selection`, behind a forward kernel that cleared the histograms on its way
+auto sel_after_clear(const float* v, int64_t P, float t_loss, int64_t min_kept, double keep_fraction, void* ws,
+                     hipStream_t s) {
+  return [=](float* tau, int64_t* counts) {
+    return sel_launch(v, P, t_loss, min_kept, keep_fraction, tau, counts, ws, true, s);
+  };
+}
+
 }  // namespace
 
 extern "C" {
 
 #if NASSEG_FP32_ONLY
-int64_t nasseg_ce_workspace(void) { return 2 * 1024; }
-int64_t nasseg_ce_mse_workspace(void) { return 3 * 1024; }
+int64_t nasseg_ce_workspace(void) { return 2 * kCeGridCap; }
+int64_t nasseg_ce_mse_workspace(void) { return 3 * kCeGridCap; }
 int64_t nasseg_ohem_workspace(void) { return kSelWsWords; }
-int64_t nasseg_ce_sel_workspace(void) { return 3 * 1024 + kSelWsWords; }
+int64_t nasseg_ce_sel_workspace(void) { return 3 * kCeGridCap + kSelWsWords; }
 
 // tau = min(t_loss, k-th largest of the entries of pixel_loss that are >= 0), k = min(n, max(min_kept,
 // ceil(keep_fraction * n))) with n = the number of such entries; counts = {k, n, entries >= tau among them}.
@@ -1159,46 +1070,28 @@ int nasseg_ohem_threshold(const float* pixel_loss, int64_t P, float t_loss, int6
 int NASSEG_FN(ce_sel_fwd)(const act_t* logits, const void* target, int elem_size, const float* weight, int64_t P,
                           int C, int ignore, int select, float t_loss, int64_t min_kept, double keep_fraction,
                           float* loss, float* stats, int64_t* counts, float* pixel_loss, float* ws, void* stream) {
-  NASSEG_REQUIRE(P > 0 && P < ((int64_t)1 << 32) && C > 0, "ce_sel_fwd: bad shape");
-  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_sel_fwd: elem_size %d not supported", elem_size);
+  NASSEG_TRY(check_shape("ce_sel_fwd", P, C, true));
+  NASSEG_TRY(check_elem_size("ce_sel_fwd", elem_size));
   NASSEG_REQUIRE(logits && target && loss && stats && counts && pixel_loss && ws, "ce_sel_fwd: null pointer");
-  NASSEG_REQUIRE(!select || (min_kept >= 1 && keep_fraction >= 0.0 && keep_fraction <= 1.0),
-                 "ce_sel_fwd: selection needs min_kept >= 1 and 0 <= keep_fraction <= 1");
+  NASSEG_TRY(check_selection("ce_sel_fwd", select, min_kept, keep_fraction));
   hipStream_t s = (hipStream_t)stream;
-  const int grid = ce_grid(P);
-  const size_t lds = (size_t)256 * (C | 1) * sizeof(float);
-  const bool tiled = C <= kCeTileMaxC && ((uintptr_t)logits & 15) == 0;
-  uint32_t* hist = select ? (uint32_t*)(ws + 3 * 1024) : nullptr;  // (cleared by the forward kernel on its way)
-  if (tiled && elem_size == 8)
-    hipLaunchKernelGGL((ce_tile_kernel<int64_t, false, false, true>), dim3(grid), dim3(256), lds, s, logits,
-                       (const int64_t*)target, P, C, ignore, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, pixel_loss, hist);
-  else if (tiled)
-    hipLaunchKernelGGL((ce_tile_kernel<uint8_t, false, false, true>), dim3(grid), dim3(256), lds, s, logits,
-                       (const uint8_t*)target, P, C, ignore, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, pixel_loss, hist);
-  else if (elem_size == 8)
-    hipLaunchKernelGGL((ce_fwd_kernel<int64_t, false, true>), dim3(grid), dim3(256), 0, s, logits,
-                       (const int64_t*)target, P, C, ignore, nullptr, nullptr, nullptr, pixel_loss, hist);
-  else
-    hipLaunchKernelGGL((ce_fwd_kernel<uint8_t, false, true>), dim3(grid), dim3(256), 0, s, logits,
-                       (const uint8_t*)target, P, C, ignore, nullptr, nullptr, nullptr, pixel_loss, hist);
+  const CeGeom g = ce_geom(P, C, {logits});
+  float* sel_ws = ws + 3 * kCeGridCap;
+  uint32_t* hist = select ? (uint32_t*)sel_ws : nullptr;  // (cleared by the forward kernel on its way)
+  with_labels(target, elem_size, [&](auto labels) {
+    using TL = label_of<decltype(labels)>;
+    if (g.tiled)
+      hipLaunchKernelGGL((ce_tile_kernel<TL, false, false, true>), dim3(g.fwd), dim3(256), g.lds, s, logits, labels, P,
+                         C, ignore, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pixel_loss,
+                         hist);
+    else
+      hipLaunchKernelGGL((ce_fwd_kernel<TL, false, true>), dim3(g.fwd), dim3(256), 0, s, logits, labels, P, C, ignore,
+                         nullptr, nullptr, nullptr, pixel_loss, hist);
+  });
   NASSEG_LAUNCH_CHECK("ce_sel_fwd");
-  if (select) {
-    const int rc = sel_launch(pixel_loss, P, t_loss, min_kept, keep_fraction, stats + 1, counts, ws + 3 * 1024, true, s);
-    if (rc != NASSEG_OK) return rc;
-  }
-  const float* tau = select ? stats + 1 : nullptr;
-  if (elem_size == 8)
-    hipLaunchKernelGGL(ce_sel_sum_kernel<int64_t>, dim3(grid), dim3(256), 0, s, pixel_loss, (const int64_t*)target,
-                       weight, P, tau, ws);
-  else
-    hipLaunchKernelGGL(ce_sel_sum_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, pixel_loss, (const uint8_t*)target,
-                       weight, P, tau, ws);
-  NASSEG_LAUNCH_CHECK("ce_sel_sum");
-  hipLaunchKernelGGL(ce_sel_finalize_kernel, dim3(1), dim3(256), 0, s, ws, grid, select, loss, stats, counts);
-  NASSEG_LAUNCH_CHECK("ce_sel_finalize");
-  return NASSEG_OK;
+  return ce_sel_reduce("ce_sel_sum", "ce_sel_finalize", sel_after_clear(pixel_loss, P, t_loss, min_kept, keep_fraction,
+                                                                        sel_ws, s),
+                       pixel_loss, target, elem_size, weight, P, select, loss, stats, counts, ws, s);
 }
 
 // dlogits = gscale * weight[t] * (softmax - onehot) / stats[0] for the pixels kept at stats[1] (pixel_loss, stats:
@@ -1206,32 +1099,21 @@ int NASSEG_FN(ce_sel_fwd)(const act_t* logits, const void* target, int elem_size
 int NASSEG_FN(ce_sel_bwd)(const act_t* logits, const void* target, int elem_size, const float* weight,
                           const float* pixel_loss, const float* stats, const float* gscale, int64_t P, int C,
                           int ignore, act_t* dlogits, void* stream) {
-  NASSEG_REQUIRE(P > 0 && C > 0, "ce_sel_bwd: bad shape");
-  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_sel_bwd: elem_size %d not supported", elem_size);
+  NASSEG_TRY(check_shape("ce_sel_bwd", P, C, false));
+  NASSEG_TRY(check_elem_size("ce_sel_bwd", elem_size));
   NASSEG_REQUIRE(logits && target && pixel_loss && stats && dlogits, "ce_sel_bwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  const int grid = ce_grid(P) * 2;
-  const size_t lds = (size_t)256 * (C | 1) * sizeof(float);
-  int64_t tiles = (P + 255) / 256;
-  if (tiles > 4096) tiles = 4096;
-  const bool tiled = C <= kCeTileMaxC && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0;
-  float* pl = const_cast<float*>(pixel_loss);  // (the kernel's one parameter for both directions; backward reads)
-  if (tiled && elem_size == 8)
-    hipLaunchKernelGGL((ce_tile_kernel<int64_t, true, false, true>), dim3((unsigned)tiles), dim3(256), lds, s,
-                       logits, (const int64_t*)target, P, C, ignore, nullptr, stats, gscale, dlogits, nullptr,
-                       nullptr, nullptr, weight, pl);
-  else if (tiled)
-    hipLaunchKernelGGL((ce_tile_kernel<uint8_t, true, false, true>), dim3((unsigned)tiles), dim3(256), lds, s,
-                       logits, (const uint8_t*)target, P, C, ignore, nullptr, stats, gscale, dlogits, nullptr,
-                       nullptr, nullptr, weight, pl);
-  else if (elem_size == 8)
-    hipLaunchKernelGGL((ce_bwd_kernel<int64_t, false, true>), dim3(grid), dim3(256), 0, s, logits,
-                       (const int64_t*)target, stats, gscale, P, C, ignore, dlogits, nullptr, nullptr, weight,
-                       pixel_loss);
-  else
-    hipLaunchKernelGGL((ce_bwd_kernel<uint8_t, false, true>), dim3(grid), dim3(256), 0, s, logits,
-                       (const uint8_t*)target, stats, gscale, P, C, ignore, dlogits, nullptr, nullptr, weight,
-                       pixel_loss);
+  const CeGeom g = ce_geom(P, C, {logits, dlogits});
+  float* pl = const_cast<float*>(pixel_loss);  // (the tiled kernel's one parameter for both directions; backward reads)
+  with_labels(target, elem_size, [&](auto labels) {
+    using TL = label_of<decltype(labels)>;
+    if (g.tiled)
+      hipLaunchKernelGGL((ce_tile_kernel<TL, true, false, true>), dim3(g.tiles), dim3(256), g.lds, s, logits, labels, P,
+                         C, ignore, nullptr, stats, gscale, dlogits, nullptr, nullptr, nullptr, weight, pl);
+    else
+      hipLaunchKernelGGL((ce_bwd_kernel<TL, false, true>), dim3(g.bwd), dim3(256), 0, s, logits, labels, stats, gscale,
+                         P, C, ignore, dlogits, nullptr, nullptr, weight, pixel_loss);
+  });
   NASSEG_LAUNCH_CHECK("ce_sel_bwd");
   return NASSEG_OK;
 }
@@ -1241,7 +1123,7 @@ int NASSEG_FN(ce_sel_bwd)(const act_t* logits, const void* target, int elem_size
 #if NASSEG_FP32_ONLY
 int64_t nasseg_ce_region_workspace(int C) {
   if (C < 1) return 0;
-  return 3 * 1024 + kSelWsWords + 2 * ((int64_t)3 * C * kRegionRows + (int64_t)3 * C);
+  return 3 * kCeGridCap + kSelWsWords + 2 * ((int64_t)3 * C * kRegionRows + (int64_t)3 * C);
 }
 #endif
 
@@ -1251,58 +1133,42 @@ int NASSEG_FN(ce_region_fwd)(const act_t* logits, const void* target, int elem_s
                              double region_weight, float* loss, float* loss_ce, float* loss_region, float* stats,
                              int64_t* counts, float* pixel_loss, float* coef, float* sums, int64_t* ncls, float* ws,
                              void* stream) {
-  NASSEG_REQUIRE(P > 0 && P < ((int64_t)1 << 32) && C > 0, "ce_region_fwd: bad shape");
-  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_region_fwd: elem_size %d not supported", elem_size);
+  NASSEG_TRY(check_shape("ce_region_fwd", P, C, true));
+  NASSEG_TRY(check_elem_size("ce_region_fwd", elem_size));
   NASSEG_REQUIRE(logits && target && loss && loss_ce && loss_region && coef && sums && ncls && ws,
                  "ce_region_fwd: null pointer");
   NASSEG_REQUIRE(!with_ce || (stats && counts && pixel_loss), "ce_region_fwd: null pointer");
   NASSEG_REQUIRE(with_ce || !select, "ce_region_fwd: selection without the cross-entropy");
-  NASSEG_REQUIRE(!select || (min_kept >= 1 && keep_fraction >= 0.0 && keep_fraction <= 1.0),
-                 "ce_region_fwd: selection needs min_kept >= 1 and 0 <= keep_fraction <= 1");
+  NASSEG_TRY(check_selection("ce_region_fwd", select, min_kept, keep_fraction));
   NASSEG_REQUIRE(alpha >= 0.0 && beta >= 0.0 && alpha + beta > 0.0 && smooth >= 0.0,
                  "ce_region_fwd: alpha, beta, smooth >= 0 and alpha + beta > 0 expected");
   NASSEG_REQUIRE(!all_classes || smooth > 0.0, "ce_region_fwd: all classes need smooth > 0");
-  static_assert((3 * 1024 + kSelWsWords) % 2 == 0, "the fp64 part of the workspace is 8-byte aligned");
+  static_assert((3 * kCeGridCap + kSelWsWords) % 2 == 0, "the fp64 part of the workspace is 8-byte aligned");
   NASSEG_REQUIRE(((uintptr_t)ws & 7) == 0, "ce_region_fwd: the workspace must be 8-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  const int grid = ce_grid(P);  // (<= kRegionRows)
-  const size_t lds = (size_t)256 * (C | 1) * sizeof(float);
-  const bool tiled = C <= kCeTileMaxC && ((uintptr_t)logits & 15) == 0;
-  uint32_t* hist = select ? (uint32_t*)(ws + 3 * 1024) : nullptr;  // (cleared by the forward kernel on its way)
-  double* part = (double*)(ws + 3 * 1024 + kSelWsWords);
+  const CeGeom g = ce_geom(P, C, {logits});  // (g.fwd <= kRegionRows)
+  float* sel_ws = ws + 3 * kCeGridCap;
+  uint32_t* hist = select ? (uint32_t*)sel_ws : nullptr;  // (cleared by the forward kernel on its way)
+  double* part = (double*)(sel_ws + kSelWsWords);
   double* tot = part + (int64_t)3 * C * kRegionRows;
   float* pl = with_ce ? pixel_loss : nullptr;
-  if (tiled && elem_size == 8)
-    hipLaunchKernelGGL(region_tile_fwd_kernel<int64_t>, dim3(grid), dim3(256), lds, s, logits,
-                       (const int64_t*)target, P, C, ignore, pl, hist, part);
-  else if (tiled)
-    hipLaunchKernelGGL(region_tile_fwd_kernel<uint8_t>, dim3(grid), dim3(256), lds, s, logits,
-                       (const uint8_t*)target, P, C, ignore, pl, hist, part);
-  else if (elem_size == 8)
-    hipLaunchKernelGGL(region_fwd_kernel<int64_t>, dim3(grid), dim3(256), 0, s, logits, (const int64_t*)target, P, C,
-                       ignore, pl, hist, part);
-  else
-    hipLaunchKernelGGL(region_fwd_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)target, P, C,
-                       ignore, pl, hist, part);
-  NASSEG_LAUNCH_CHECK("ce_region_fwd");
-  if (with_ce) {
-    if (select) {
-      const int rc =
-          sel_launch(pixel_loss, P, t_loss, min_kept, keep_fraction, stats + 1, counts, ws + 3 * 1024, true, s);
-      if (rc != NASSEG_OK) return rc;
-    }
-    const float* tau = select ? stats + 1 : nullptr;
-    if (elem_size == 8)
-      hipLaunchKernelGGL(ce_sel_sum_kernel<int64_t>, dim3(grid), dim3(256), 0, s, pixel_loss, (const int64_t*)target,
-                         weight, P, tau, ws);
+  with_labels(target, elem_size, [&](auto labels) {
+    using TL = label_of<decltype(labels)>;
+    if (g.tiled)
+      hipLaunchKernelGGL(region_tile_fwd_kernel<TL>, dim3(g.fwd), dim3(256), g.lds, s, logits, labels, P, C, ignore, pl,
+                         hist, part);
     else
-      hipLaunchKernelGGL(ce_sel_sum_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, pixel_loss, (const uint8_t*)target,
-                         weight, P, tau, ws);
-    NASSEG_LAUNCH_CHECK("ce_region_sum");
-  }
-  hipLaunchKernelGGL(region_finalize_kernel, dim3(1), dim3(1024), 0, s, ws, part, grid, C, with_ce, select, alpha, beta,
-                     smooth, all_classes, region_weight, loss, loss_ce, loss_region, stats, counts, coef, sums, ncls,
-                     tot);
+      hipLaunchKernelGGL(region_fwd_kernel<TL>, dim3(g.fwd), dim3(256), 0, s, logits, labels, P, C, ignore, pl, hist,
+                         part);
+  });
+  NASSEG_LAUNCH_CHECK("ce_region_fwd");
+  if (with_ce)  // (the finalizer below reads the partials)
+    NASSEG_TRY(ce_sel_reduce("ce_region_sum", nullptr, sel_after_clear(pixel_loss, P, t_loss, min_kept, keep_fraction,
+                                                                       sel_ws, s),
+                             pixel_loss, target, elem_size, weight, P, select, nullptr, stats, counts, ws, s));
+  hipLaunchKernelGGL(region_finalize_kernel, dim3(1), dim3(1024), 0, s, ws, part, g.fwd, C, with_ce, select, alpha,
+                     beta, smooth, all_classes, region_weight, loss, loss_ce, loss_region, stats, counts, coef, sums,
+                     ncls, tot);
   NASSEG_LAUNCH_CHECK("ce_region_finalize");
   return NASSEG_OK;
 }
@@ -1311,31 +1177,22 @@ int NASSEG_FN(ce_region_bwd)(const act_t* logits, const void* target, int elem_s
                              const float* pixel_loss, const float* stats, const float* coef, const float* gscale,
                              int with_ce, double region_weight, int64_t P, int C, int ignore, act_t* dlogits,
                              void* stream) {
-  NASSEG_REQUIRE(P > 0 && C > 0, "ce_region_bwd: bad shape");
-  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_region_bwd: elem_size %d not supported", elem_size);
+  NASSEG_TRY(check_shape("ce_region_bwd", P, C, false));
+  NASSEG_TRY(check_elem_size("ce_region_bwd", elem_size));
   NASSEG_REQUIRE(logits && target && coef && dlogits, "ce_region_bwd: null pointer");
   NASSEG_REQUIRE(!with_ce || (pixel_loss && stats), "ce_region_bwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  const int grid = ce_grid(P) * 2;
-  const size_t lds = (size_t)256 * (C | 1) * sizeof(float);
-  int64_t tiles = (P + 255) / 256;
-  if (tiles > 4096) tiles = 4096;
-  const bool tiled = C <= kCeTileMaxC && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0;
+  const CeGeom g = ce_geom(P, C, {logits, dlogits});
   const float rw = (float)region_weight;
-  if (tiled && elem_size == 8)
-    hipLaunchKernelGGL(region_tile_bwd_kernel<int64_t>, dim3((unsigned)tiles), dim3(256), lds, s, logits,
-                       (const int64_t*)target, P, C, ignore, weight, pixel_loss, stats, coef, gscale, with_ce, rw,
-                       dlogits);
-  else if (tiled)
-    hipLaunchKernelGGL(region_tile_bwd_kernel<uint8_t>, dim3((unsigned)tiles), dim3(256), lds, s, logits,
-                       (const uint8_t*)target, P, C, ignore, weight, pixel_loss, stats, coef, gscale, with_ce, rw,
-                       dlogits);
-  else if (elem_size == 8)
-    hipLaunchKernelGGL(region_bwd_kernel<int64_t>, dim3(grid), dim3(256), 0, s, logits, (const int64_t*)target, P, C,
-                       ignore, weight, pixel_loss, stats, coef, gscale, with_ce, rw, dlogits);
-  else
-    hipLaunchKernelGGL(region_bwd_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)target, P, C,
-                       ignore, weight, pixel_loss, stats, coef, gscale, with_ce, rw, dlogits);
+  with_labels(target, elem_size, [&](auto labels) {
+    using TL = label_of<decltype(labels)>;
+    if (g.tiled)
+      hipLaunchKernelGGL(region_tile_bwd_kernel<TL>, dim3(g.tiles), dim3(256), g.lds, s, logits, labels, P, C, ignore,
+                         weight, pixel_loss, stats, coef, gscale, with_ce, rw, dlogits);
+    else
+      hipLaunchKernelGGL(region_bwd_kernel<TL>, dim3(g.bwd), dim3(256), 0, s, logits, labels, P, C, ignore, weight,
+                         pixel_loss, stats, coef, gscale, with_ce, rw, dlogits);
+  });
   NASSEG_LAUNCH_CHECK("ce_region_bwd");
   return NASSEG_OK;
 }
@@ -1344,26 +1201,20 @@ int NASSEG_FN(ce_region_bwd)(const act_t* logits, const void* target, int elem_s
 // out[0] = mean NLL over valid pixels, out[1] = valid count. ws: nasseg_ce_workspace() floats.
 int NASSEG_FN(ce_fwd)(const act_t* logits, const void* target, int elem_size, int64_t P, int C,
                   int ignore, float* out, float* ws, void* stream) {
-  NASSEG_REQUIRE(P > 0 && C > 0, "ce_fwd: bad shape");
+  NASSEG_TRY(check_shape("ce_fwd", P, C, false));
+  NASSEG_TRY(check_elem_size("ce_fwd", elem_size));
   hipStream_t s = (hipStream_t)stream;
-  const int grid = ce_grid(P);
-  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_fwd: elem_size %d not supported", elem_size);
-  const size_t lds = (size_t)256 * (C | 1) * sizeof(float);
-  const bool tiled = C <= kCeTileMaxC && ((uintptr_t)logits & 15) == 0;  // (vector staging loads)
-  if (tiled && elem_size == 8)
-    hipLaunchKernelGGL((ce_tile_kernel<int64_t, false>), dim3(grid), dim3(256), lds, s, logits,
-                       (const int64_t*)target, P, C, ignore, ws, nullptr, nullptr, nullptr);
-  else if (tiled)
-    hipLaunchKernelGGL((ce_tile_kernel<uint8_t, false>), dim3(grid), dim3(256), lds, s, logits,
-                       (const uint8_t*)target, P, C, ignore, ws, nullptr, nullptr, nullptr);
-  else if (elem_size == 8)
-    hipLaunchKernelGGL((ce_fwd_kernel<int64_t>), dim3(grid), dim3(256), 0, s, logits,
-                       (const int64_t*)target, P, C, ignore, ws);
-  else
-    hipLaunchKernelGGL((ce_fwd_kernel<uint8_t>), dim3(grid), dim3(256), 0, s, logits,
-                       (const uint8_t*)target, P, C, ignore, ws);
+  const CeGeom g = ce_geom(P, C, {logits});
+  with_labels(target, elem_size, [&](auto labels) {
+    using TL = label_of<decltype(labels)>;
+    if (g.tiled)
+      hipLaunchKernelGGL((ce_tile_kernel<TL, false>), dim3(g.fwd), dim3(256), g.lds, s, logits, labels, P, C, ignore,
+                         ws, nullptr, nullptr, nullptr);
+    else
+      hipLaunchKernelGGL((ce_fwd_kernel<TL>), dim3(g.fwd), dim3(256), 0, s, logits, labels, P, C, ignore, ws);
+  });
   NASSEG_LAUNCH_CHECK("ce_fwd");
-  hipLaunchKernelGGL(ce_finalize_kernel<false>, dim3(1), dim3(256), 0, s, ws, grid, out, nullptr, 0.0, nullptr,
+  hipLaunchKernelGGL(ce_finalize_kernel<false>, dim3(1), dim3(256), 0, s, ws, g.fwd, out, nullptr, 0.0, nullptr,
                      nullptr);
   NASSEG_LAUNCH_CHECK("ce_finalize");
   return NASSEG_OK;
@@ -1372,26 +1223,19 @@ int NASSEG_FN(ce_fwd)(const act_t* logits, const void* target, int elem_size, in
 // stats = out of nasseg_ce_fwd; gscale = device scalar upstream gradient (null = 1)
 int NASSEG_FN(ce_bwd)(const act_t* logits, const void* target, int elem_size, const float* stats,
                   const float* gscale, int64_t P, int C, int ignore, act_t* dlogits, void* stream) {
-  NASSEG_REQUIRE(P > 0 && C > 0, "ce_bwd: bad shape");
+  NASSEG_TRY(check_shape("ce_bwd", P, C, false));
+  NASSEG_TRY(check_elem_size("ce_bwd", elem_size));
   hipStream_t s = (hipStream_t)stream;
-  const int grid = ce_grid(P) * 2;
-  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_bwd: elem_size %d not supported", elem_size);
-  const size_t lds = (size_t)256 * (C | 1) * sizeof(float);
-  int64_t tiles = (P + 255) / 256;
-  if (tiles > 4096) tiles = 4096;
-  const bool tiled = C <= kCeTileMaxC && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0;
-  if (tiled && elem_size == 8)
-    hipLaunchKernelGGL((ce_tile_kernel<int64_t, true>), dim3((unsigned)tiles), dim3(256), lds, s, logits,
-                       (const int64_t*)target, P, C, ignore, nullptr, stats, gscale, dlogits);
-  else if (tiled)
-    hipLaunchKernelGGL((ce_tile_kernel<uint8_t, true>), dim3((unsigned)tiles), dim3(256), lds, s, logits,
-                       (const uint8_t*)target, P, C, ignore, nullptr, stats, gscale, dlogits);
-  else if (elem_size == 8)
-    hipLaunchKernelGGL((ce_bwd_kernel<int64_t>), dim3(grid), dim3(256), 0, s, logits,
-                       (const int64_t*)target, stats, gscale, P, C, ignore, dlogits);
-  else
-    hipLaunchKernelGGL((ce_bwd_kernel<uint8_t>), dim3(grid), dim3(256), 0, s, logits,
-                       (const uint8_t*)target, stats, gscale, P, C, ignore, dlogits);
+  const CeGeom g = ce_geom(P, C, {logits, dlogits});
+  with_labels(target, elem_size, [&](auto labels) {
+    using TL = label_of<decltype(labels)>;
+    if (g.tiled)
+      hipLaunchKernelGGL((ce_tile_kernel<TL, true>), dim3(g.tiles), dim3(256), g.lds, s, logits, labels, P, C, ignore,
+                         nullptr, stats, gscale, dlogits);
+    else
+      hipLaunchKernelGGL((ce_bwd_kernel<TL>), dim3(g.bwd), dim3(256), 0, s, logits, labels, stats, gscale, P, C,
+                         ignore, dlogits);
+  });
   NASSEG_LAUNCH_CHECK("ce_bwd");
   return NASSEG_OK;
 }
@@ -1402,28 +1246,23 @@ int NASSEG_FN(ce_bwd)(const act_t* logits, const void* target, int elem_size, co
 // teacher: fp32 [P][C] (the task0 cache's kd_y, whatever the logits' storage).  ws: nasseg_ce_mse_workspace() floats.
 int NASSEG_FN(ce_mse_fwd)(const act_t* logits, const void* target, int elem_size, const float* teacher, int64_t P,
                           int C, int ignore, float* ce, float* mse, float* stats, float* ws, void* stream) {
-  NASSEG_REQUIRE(P > 0 && C > 0, "ce_mse_fwd: bad shape");
-  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_mse_fwd: elem_size %d not supported", elem_size);
+  NASSEG_TRY(check_shape("ce_mse_fwd", P, C, false));
+  NASSEG_TRY(check_elem_size("ce_mse_fwd", elem_size));
   NASSEG_REQUIRE(logits && target && teacher && ce && mse && stats && ws, "ce_mse_fwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  const int grid = ce_grid(P);  // (<= 1024: ws = [1024][2] NLL partials | [1024] squared-difference partials)
-  float* sqpart = ws + 2 * 1024;
-  const size_t lds = (size_t)256 * (C | 1) * sizeof(float);
-  const bool tiled = C <= kCeTileMaxC && (((uintptr_t)logits | (uintptr_t)teacher) & 15) == 0;
-  if (tiled && elem_size == 8)
-    hipLaunchKernelGGL((ce_tile_kernel<int64_t, false, true>), dim3(grid), dim3(256), lds, s, logits,
-                       (const int64_t*)target, P, C, ignore, ws, nullptr, nullptr, nullptr, teacher, nullptr, sqpart);
-  else if (tiled)
-    hipLaunchKernelGGL((ce_tile_kernel<uint8_t, false, true>), dim3(grid), dim3(256), lds, s, logits,
-                       (const uint8_t*)target, P, C, ignore, ws, nullptr, nullptr, nullptr, teacher, nullptr, sqpart);
-  else if (elem_size == 8)
-    hipLaunchKernelGGL((ce_fwd_kernel<int64_t, true>), dim3(grid), dim3(256), 0, s, logits,
-                       (const int64_t*)target, P, C, ignore, ws, teacher, sqpart);
-  else
-    hipLaunchKernelGGL((ce_fwd_kernel<uint8_t, true>), dim3(grid), dim3(256), 0, s, logits,
-                       (const uint8_t*)target, P, C, ignore, ws, teacher, sqpart);
+  const CeGeom g = ce_geom(P, C, {logits, teacher});
+  float* sqpart = ws + 2 * kCeGridCap;  // (ws = [1024][2] NLL partials | [1024] squared-difference partials)
+  with_labels(target, elem_size, [&](auto labels) {
+    using TL = label_of<decltype(labels)>;
+    if (g.tiled)
+      hipLaunchKernelGGL((ce_tile_kernel<TL, false, true>), dim3(g.fwd), dim3(256), g.lds, s, logits, labels, P, C,
+                         ignore, ws, nullptr, nullptr, nullptr, teacher, nullptr, sqpart);
+    else
+      hipLaunchKernelGGL((ce_fwd_kernel<TL, true>), dim3(g.fwd), dim3(256), 0, s, logits, labels, P, C, ignore, ws,
+                         teacher, sqpart);
+  });
   NASSEG_LAUNCH_CHECK("ce_mse_fwd");
-  hipLaunchKernelGGL(ce_finalize_kernel<true>, dim3(1), dim3(256), 0, s, ws, grid, stats, sqpart,
+  hipLaunchKernelGGL(ce_finalize_kernel<true>, dim3(1), dim3(256), 0, s, ws, g.fwd, stats, sqpart,
                      (double)P * (double)C, ce, mse);
   NASSEG_LAUNCH_CHECK("ce_mse_finalize");
   return NASSEG_OK;
@@ -1434,27 +1273,20 @@ int NASSEG_FN(ce_mse_fwd)(const act_t* logits, const void* target, int elem_size
 int NASSEG_FN(ce_mse_bwd)(const act_t* logits, const void* target, int elem_size, const float* teacher,
                           const float* stats, const float* g_ce, const float* g_mse, int64_t P, int C, int ignore,
                           act_t* dlogits, void* stream) {
-  NASSEG_REQUIRE(P > 0 && C > 0, "ce_mse_bwd: bad shape");
-  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_mse_bwd: elem_size %d not supported", elem_size);
+  NASSEG_TRY(check_shape("ce_mse_bwd", P, C, false));
+  NASSEG_TRY(check_elem_size("ce_mse_bwd", elem_size));
   NASSEG_REQUIRE(logits && target && teacher && stats && dlogits, "ce_mse_bwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  const int grid = ce_grid(P) * 2;
-  const size_t lds = (size_t)256 * (C | 1) * sizeof(float);
-  int64_t tiles = (P + 255) / 256;
-  if (tiles > 4096) tiles = 4096;
-  const bool tiled = C <= kCeTileMaxC && (((uintptr_t)logits | (uintptr_t)dlogits | (uintptr_t)teacher) & 15) == 0;
-  if (tiled && elem_size == 8)
-    hipLaunchKernelGGL((ce_tile_kernel<int64_t, true, true>), dim3((unsigned)tiles), dim3(256), lds, s, logits,
-                       (const int64_t*)target, P, C, ignore, nullptr, stats, g_ce, dlogits, teacher, g_mse, nullptr);
-  else if (tiled)
-    hipLaunchKernelGGL((ce_tile_kernel<uint8_t, true, true>), dim3((unsigned)tiles), dim3(256), lds, s, logits,
-                       (const uint8_t*)target, P, C, ignore, nullptr, stats, g_ce, dlogits, teacher, g_mse, nullptr);
-  else if (elem_size == 8)
-    hipLaunchKernelGGL((ce_bwd_kernel<int64_t, true>), dim3(grid), dim3(256), 0, s, logits,
-                       (const int64_t*)target, stats, g_ce, P, C, ignore, dlogits, teacher, g_mse);
-  else
-    hipLaunchKernelGGL((ce_bwd_kernel<uint8_t, true>), dim3(grid), dim3(256), 0, s, logits,
-                       (const uint8_t*)target, stats, g_ce, P, C, ignore, dlogits, teacher, g_mse);
+  const CeGeom g = ce_geom(P, C, {logits, dlogits, teacher});
+  with_labels(target, elem_size, [&](auto labels) {
+    using TL = label_of<decltype(labels)>;
+    if (g.tiled)
+      hipLaunchKernelGGL((ce_tile_kernel<TL, true, true>), dim3(g.tiles), dim3(256), g.lds, s, logits, labels, P, C,
+                         ignore, nullptr, stats, g_ce, dlogits, teacher, g_mse, nullptr);
+    else
+      hipLaunchKernelGGL((ce_bwd_kernel<TL, true>), dim3(g.bwd), dim3(256), 0, s, logits, labels, stats, g_ce, P, C,
+                         ignore, dlogits, teacher, g_mse);
+  });
   NASSEG_LAUNCH_CHECK("ce_mse_bwd");
   return NASSEG_OK;
 }

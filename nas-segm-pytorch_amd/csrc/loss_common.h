@@ -1,0 +1,204 @@
+// What the segmentation losses share (csrc/loss.hip, csrc/loss_up.hip, csrc/lovasz.hip): the predicates every kernel
+// must agree on, the sum pass and the finalizer over per-pixel losses, and the host side of a launch - dispatch over
+// the label type, launch geometry, argument checks.  Like the .hip files, compiled for both activation storages.
+#pragma once
+#include <initializer_list>
+#include <type_traits>
+
+#include "common.h"
+
+namespace {
+
+// Is a per-pixel loss that takes part (l >= 0; -1 marks the others) kept at threshold tau?  l >= tau on the fp32
+// values, compared through their bit patterns (for non-negative floats the order of the patterns is the order of
+// the values) so that the answer is the same integer comparison the radix selection (csrc/loss.hip) made, denormals
+// included.
+__device__ __forceinline__ bool sel_kept(float l, float tau) {
+  if (l < 0.f) return false;
+  return !(tau > 0.f) || __float_as_uint(l) >= __float_as_uint(tau);
+}
+
+// Does the pixel with label t (int64_t) stay out of the loss?  Out-of-range labels are skipped, never read.
+// A macro for the kernels that had the expression in their bodies: through a function the compiler orders the
+// operands of one scalar `and` the other way round, and these kernels' instruction streams are pinned.
+#define NASSEG_LABEL_SKIPPED(t, C, ignore) ((t) == (ignore) || (t) < 0 || (t) >= (C))
+__device__ __forceinline__ bool label_valid(int64_t t, int C, int ignore) {
+  return !NASSEG_LABEL_SKIPPED(t, C, ignore);
+}
+
+constexpr int kCeGridCap = 1024;  // workgroups of a pass over the pixels = rows of its partials
+constexpr int kCeTileMaxC = 63;   // classes up to which a tile of 256 pixels is staged through LDS
+
+#ifndef NASSEG_LOSS_NO_SUM_PASS  // (a source that sums no per-pixel losses keeps the kernels out of its code object)
+// Sum pass over pixel_loss + labels: partial[b] = {sum w l, sum w, count} over the kept pixels of workgroup b, with
+// the pixel -> (workgroup, thread) mapping, the accumulation order and the tree of ce_fwd_kernel: with unit weights
+// and everything kept, the very sums of nasseg_ce_fwd.  tau == nullptr: no selection, every valid pixel is kept.
+template <typename TL>
+__global__ __launch_bounds__(256) void ce_sel_sum_kernel(const float* __restrict__ pixel_loss,
+                                                         const TL* __restrict__ target,
+                                                         const float* __restrict__ weight, int64_t P,
+                                                         const float* __restrict__ tau,
+                                                         float* __restrict__ partial) {
+  __shared__ float red_l[256];
+  __shared__ float red_w[256];
+  __shared__ float red_n[256];
+  const float t = tau ? tau[0] : 0.f;
+  float loss = 0.f, sw = 0.f, cnt = 0.f;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
+    const float l = pixel_loss[p];
+    if (!sel_kept(l, t)) continue;
+    const float w = weight ? weight[(int64_t)target[p]] : 1.f;  // (l >= 0: the label is in [0, C))
+    loss += w * l;
+    sw += w;
+    cnt += 1.f;
+  }
+  red_l[threadIdx.x] = loss;
+  red_w[threadIdx.x] = sw;
+  red_n[threadIdx.x] = cnt;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      red_l[threadIdx.x] += red_l[threadIdx.x + s];
+      red_w[threadIdx.x] += red_w[threadIdx.x + s];
+      red_n[threadIdx.x] += red_n[threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x * 3] = red_l[0];
+    partial[blockIdx.x * 3 + 1] = red_w[0];
+    partial[blockIdx.x * 3 + 2] = red_n[0];
+  }
+}
+
+// loss = sum w l / sum w, stats = {sum w, tau}, counts[2] = kept pixels (selected: counts[0..1] and stats[1] are
+// the selection's; else k = n = kept and tau = -inf); fp64, the order of ce_finalize_kernel.
+__global__ __launch_bounds__(256) void ce_sel_finalize_kernel(const float* __restrict__ partial, int nblk,
+                                                              int selected, float* __restrict__ loss,
+                                                              float* __restrict__ stats,
+                                                              int64_t* __restrict__ counts) {
+  __shared__ double red_l[256];
+  __shared__ double red_w[256];
+  __shared__ double red_n[256];
+  double l = 0.0, w = 0.0, n = 0.0;
+  for (int b = threadIdx.x; b < nblk; b += 256) {
+    l += (double)partial[b * 3];
+    w += (double)partial[b * 3 + 1];
+    n += (double)partial[b * 3 + 2];
+  }
+  red_l[threadIdx.x] = l;
+  red_w[threadIdx.x] = w;
+  red_n[threadIdx.x] = n;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      red_l[threadIdx.x] += red_l[threadIdx.x + s];
+      red_w[threadIdx.x] += red_w[threadIdx.x + s];
+      red_n[threadIdx.x] += red_n[threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    loss[0] = (float)(red_l[0] / red_w[0]);
+    stats[0] = (float)red_w[0];
+    counts[2] = (int64_t)red_n[0];
+    if (!selected) {
+      stats[1] = -__builtin_inff();
+      counts[0] = counts[1] = (int64_t)red_n[0];
+    }
+  }
+}
+
+#endif  // NASSEG_LOSS_NO_SUM_PASS
+
+// ---------------------------------------------------------------------------
+// Host side
+// ---------------------------------------------------------------------------
+#define NASSEG_TRY(call)              \
+  do {                                \
+    const int rc_ = (call);           \
+    if (rc_ != NASSEG_OK) return rc_; \
+  } while (0)
+
+// f(labels) with the labels as const int64_t* or const uint8_t*: a generic lambda names its kernel's template
+// arguments and its arguments once, label_of<decltype(labels)> being the kernel's label type.
+template <typename F>
+inline void with_labels(const void* target, int elem_size, F&& f) {
+  if (elem_size == 8)
+    f((const int64_t*)target);
+  else
+    f((const uint8_t*)target);
+}
+template <typename Ptr>
+using label_of = std::remove_const_t<std::remove_pointer_t<Ptr>>;
+
+inline int ce_grid(int64_t P) {
+  int64_t b = (P + 255) / 256;
+  if (b > kCeGridCap) b = kCeGridCap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+// Launch geometry of the cross-entropy kernels over [P][C] logits, 256 threads each.  tiled (ce_tile_kernel and its
+// kin: C <= kCeTileMaxC and every pointer of `vec`, which they touch with 16-byte accesses, so aligned): `fwd`
+// workgroups forward, `tiles` backward, `lds` bytes of [256][C | 1] floats.  Else (one lane per pixel): `fwd`
+// workgroups forward, `bwd` backward, no LDS.
+struct CeGeom {
+  int fwd, bwd;
+  unsigned tiles;
+  size_t lds;
+  bool tiled;
+};
+inline CeGeom ce_geom(int64_t P, int C, std::initializer_list<const void*> vec) {
+  uintptr_t bits = 0;
+  for (const void* p : vec) bits |= (uintptr_t)p;
+  int64_t tiles = (P + 255) / 256;
+  if (tiles > 4096) tiles = 4096;
+  CeGeom g;
+  g.fwd = ce_grid(P);
+  g.bwd = g.fwd * 2;
+  g.tiles = (unsigned)tiles;
+  g.lds = (size_t)256 * (C | 1) * sizeof(float);
+  g.tiled = C <= kCeTileMaxC && (bits & 15) == 0;
+  return g;
+}
+
+// The argument checks the entry points share.  p32: P also indexes 32-bit counters.
+inline int check_shape(const char* who, int64_t P, int C, bool p32) {
+  if (P > 0 && (!p32 || P < ((int64_t)1 << 32)) && C > 0) return NASSEG_OK;
+  return nasseg_fail(NASSEG_ERR_ARG, "%s: bad shape", who);
+}
+inline int check_elem_size(const char* who, int elem_size) {
+  if (elem_size == 8 || elem_size == 1) return NASSEG_OK;
+  return nasseg_fail(NASSEG_ERR_ARG, "%s: elem_size %d not supported", who, elem_size);
+}
+inline int check_selection(const char* who, int select, int64_t min_kept, double keep_fraction) {
+  if (!select || (min_kept >= 1 && keep_fraction >= 0.0 && keep_fraction <= 1.0)) return NASSEG_OK;
+  return nasseg_fail(NASSEG_ERR_ARG, "%s: selection needs min_kept >= 1 and 0 <= keep_fraction <= 1", who);
+}
+
+#ifndef NASSEG_LOSS_NO_SUM_PASS
+// What follows the pass that wrote pixel_loss: the selection (`selection(tau, counts)`, when `select`), the sum pass
+// into ws = [kCeGridCap][3] partials and - unless the caller's own finalizer reads them (fin_name == nullptr) - the
+// fp64 finalize.
+template <typename Sel>
+inline int ce_sel_reduce(const char* sum_name, const char* fin_name, Sel&& selection, const float* pixel_loss,
+                         const void* target, int elem_size, const float* weight, int64_t P, int select,
+                         float* loss, float* stats, int64_t* counts, float* ws, hipStream_t s) {
+  const int grid = ce_grid(P);
+  if (select) NASSEG_TRY(selection(stats + 1, counts));
+  const float* tau = select ? stats + 1 : nullptr;
+  with_labels(target, elem_size, [&](auto labels) {
+    hipLaunchKernelGGL(ce_sel_sum_kernel<label_of<decltype(labels)>>, dim3(grid), dim3(256), 0, s, pixel_loss, labels,
+                       weight, P, tau, ws);
+  });
+  NASSEG_LAUNCH_CHECK(sum_name);
+  if (fin_name) {
+    hipLaunchKernelGGL(ce_sel_finalize_kernel, dim3(1), dim3(256), 0, s, ws, grid, select, loss, stats, counts);
+    NASSEG_LAUNCH_CHECK(fin_name);
+  }
+  return NASSEG_OK;
+}
+#endif  // NASSEG_LOSS_NO_SUM_PASS
+
+}  // namespace

@@ -8,31 +8,22 @@
 // a label pixel lives in registers only:
 //   forward   one lane per label pixel: the four neighbour rows of the logits through L1 / L2 (lanes next to each other
 //             share them), v_c = the row nasseg_argmax_cm takes its argmax of, bit for bit; pixel_loss and lse are the
-//             only per-pixel outputs.  Selection: nasseg_ohem_threshold over pixel_loss.  Then one sum pass and one
-//             fp64 finalize launch, the arithmetic of nasseg_ce_sel_fwd's.
+//             only per-pixel outputs.  Selection: nasseg_ohem_threshold over pixel_loss.  Then the sum pass and the
+//             fp64 finalize of nasseg_ce_sel_fwd (csrc/loss_common.h: the same kernels).
 //   backward  a gather (as nasseg_bilinear_bwd): a workgroup owns a tile of kUpTile x kUpTile logits pixels and a chunk
 //             of <= kUpChunk channels, stages tile + halo of the logits in LDS (row stride cn | 1 floats: odd), and every
 //             thread walks the label pixels of ITS (pixel, channel) in a fixed order: re-interpolates its channel,
 //             exp(v - lse) - onehot, times the pixel's factor and Wy Wx.  dlogits is written once; no atomics.
 #include <math.h>
 
-#include "common.h"
+#include "loss_common.h"
 #include "resize_index.h"
 
 namespace {
 
-constexpr int kUpGridCap = 1024;  // workgroups of the forward and of the sum pass (= rows of the partials)
 constexpr int kUpTile = 8;        // backward: logits pixels per tile side
 constexpr int kUpPatch = kUpTile + 2;
 constexpr int kUpChunk = 64;      // backward: channels per workgroup
-
-// A copy of csrc/loss.hip's sel_kept (and, below, of its ce_sel_sum_kernel / ce_sel_finalize_kernel: loss.hip keeps them
-// in its unnamed namespace and points here) - it must stay the compare of the radix selection, bit for bit: is a
-// per-pixel loss that takes part (l >= 0) kept at tau?  On the bit patterns, as the radix selection compares them.
-__device__ __forceinline__ bool up_kept(float l, float tau) {
-  if (l < 0.f) return false;
-  return !(tau > 0.f) || __float_as_uint(l) >= __float_as_uint(tau);
-}
 
 // v = ly.l0 * (lx.l0 * x00 + lx.l1 * x01) + ly.l1 * (lx.l0 * x10 + lx.l1 * x11), every product and sum rounded on
 // its own (csrc/miou.hip: argmax_cm_kernel)
@@ -50,7 +41,7 @@ __global__ __launch_bounds__(256) void ce_up_fwd_kernel(const act_t* __restrict_
   const int64_t P = (int64_t)B * H * W;
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
     const int64_t t = (int64_t)target[p];
-    if (t == ignore || t < 0 || t >= C) {  // out-of-range labels are skipped, never read
+    if (NASSEG_LABEL_SKIPPED(t, C, ignore)) {
       pixel_loss[p] = -1.f;
       lse_out[p] = 0.f;
       continue;
@@ -75,82 +66,6 @@ __global__ __launch_bounds__(256) void ce_up_fwd_kernel(const act_t* __restrict_
     const float lse = m + logf(s);
     pixel_loss[p] = lse - up_interp(lda1(p00 + t), lda1(p01 + t), lda1(p10 + t), lda1(p11 + t), ly, lx);
     lse_out[p] = lse;
-  }
-}
-
-// partial[b] = {sum w l, sum w, count} over the kept pixels of workgroup b: the statements of csrc/loss.hip's
-// ce_sel_sum_kernel (tau == nullptr: every valid pixel is kept)
-template <typename TL>
-__global__ __launch_bounds__(256) void ce_up_sum_kernel(const float* __restrict__ pixel_loss,
-                                                        const TL* __restrict__ target,
-                                                        const float* __restrict__ weight, int64_t P,
-                                                        const float* __restrict__ tau, float* __restrict__ partial) {
-  __shared__ float red_l[256];
-  __shared__ float red_w[256];
-  __shared__ float red_n[256];
-  const float t = tau ? tau[0] : 0.f;
-  float loss = 0.f, sw = 0.f, cnt = 0.f;
-  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
-    const float l = pixel_loss[p];
-    if (!up_kept(l, t)) continue;
-    const float wt = weight ? weight[(int64_t)target[p]] : 1.f;  // (l >= 0: the label is in [0, C))
-    loss += wt * l;
-    sw += wt;
-    cnt += 1.f;
-  }
-  red_l[threadIdx.x] = loss;
-  red_w[threadIdx.x] = sw;
-  red_n[threadIdx.x] = cnt;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      red_l[threadIdx.x] += red_l[threadIdx.x + s];
-      red_w[threadIdx.x] += red_w[threadIdx.x + s];
-      red_n[threadIdx.x] += red_n[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    partial[blockIdx.x * 3] = red_l[0];
-    partial[blockIdx.x * 3 + 1] = red_w[0];
-    partial[blockIdx.x * 3 + 2] = red_n[0];
-  }
-}
-
-// loss = sum w l / sum w, stats = {sum w, tau}, counts[2] = kept pixels (selected: counts[0..1] and stats[1] are the
-// selection's; else k = n = kept and tau = -inf): the statements of ce_sel_finalize_kernel, fp64, fixed order
-__global__ __launch_bounds__(256) void ce_up_finalize_kernel(const float* __restrict__ partial, int nblk, int selected,
-                                                             float* __restrict__ loss, float* __restrict__ stats,
-                                                             int64_t* __restrict__ counts) {
-  __shared__ double red_l[256];
-  __shared__ double red_w[256];
-  __shared__ double red_n[256];
-  double l = 0.0, w = 0.0, n = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += 256) {
-    l += (double)partial[b * 3];
-    w += (double)partial[b * 3 + 1];
-    n += (double)partial[b * 3 + 2];
-  }
-  red_l[threadIdx.x] = l;
-  red_w[threadIdx.x] = w;
-  red_n[threadIdx.x] = n;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      red_l[threadIdx.x] += red_l[threadIdx.x + s];
-      red_w[threadIdx.x] += red_w[threadIdx.x + s];
-      red_n[threadIdx.x] += red_n[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    loss[0] = (float)(red_l[0] / red_w[0]);
-    stats[0] = (float)red_w[0];
-    counts[2] = (int64_t)red_n[0];
-    if (!selected) {
-      stats[1] = -__builtin_inff();
-      counts[0] = counts[1] = (int64_t)red_n[0];
-    }
   }
 }
 
@@ -267,7 +182,7 @@ __global__ __launch_bounds__(256) void ce_up_bwd_kernel(const act_t* __restrict_
         const float wx = up_weight(lx, j);
         if (wx == 0.f) continue;
         const int64_t p = prow + X;
-        if (!up_kept(pixel_loss[p], tau)) continue;  // (-1 on pixels that are not valid)
+        if (!sel_kept(pixel_loss[p], tau)) continue;  // (-1 on pixels that are not valid)
         const int64_t t = (int64_t)target[p];
         const float gp = (g * (weight ? weight[t] : 1.f)) / sumw;
         const int a0 = (lx.i0 - ox) * CS, a1 = (lx.i1 - ox) * CS;
@@ -278,13 +193,6 @@ __global__ __launch_bounds__(256) void ce_up_bwd_kernel(const act_t* __restrict_
     }
     sta1(dlogits + (((int64_t)b * h + i) * w + j) * C + c0 + c, acc);
   }
-}
-
-inline int up_grid(int64_t P) {
-  int64_t b = (P + 255) / 256;
-  if (b > kUpGridCap) b = kUpGridCap;
-  if (b < 1) b = 1;
-  return (int)b;
 }
 
 inline bool up_shape_ok(int B, int h, int w, int C, int H, int W) {
@@ -301,57 +209,46 @@ inline bool up_shape_ok(int B, int h, int w, int C, int H, int W) {
 extern "C" {
 
 #if NASSEG_FP32_ONLY
-// floats: [kUpGridCap][3] partials | the selection's words.  A function of the grid alone.
+// floats: [kCeGridCap][3] partials | the selection's words.  A function of the grid alone.
 int64_t nasseg_ce_up_workspace(int B, int h, int w, int C, int H, int W) {
   if (!up_shape_ok(B, h, w, C, H, W)) return 0;
-  return 3 * kUpGridCap + nasseg_ohem_workspace();
+  return 3 * kCeGridCap + nasseg_ohem_workspace();
 }
 #endif
+
+#define UP_SHAPE_CHECK(who)                          \
+  NASSEG_REQUIRE(up_shape_ok(B, h, w, C, H, W), who \
+                 ": bad shape (C >= 2, B*H*W < 2^32, B*h*w*C < 2^31, fewer than 2^24 backward tiles)")
 
 int NASSEG_FN(ce_up_fwd)(const act_t* logits, const void* target, int elem_size, const float* weight, int B, int h,
                          int w, int C, int H, int W, int ignore, int select, float t_loss, int64_t min_kept,
                          double keep_fraction, float* loss, float* stats, int64_t* counts, float* pixel_loss,
                          float* lse, float* ws, void* stream) {
-  NASSEG_REQUIRE(up_shape_ok(B, h, w, C, H, W), "ce_up_fwd: bad shape (C >= 2, B*H*W < 2^32, B*h*w*C < 2^31, fewer than 2^24 backward tiles)");
-  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_up_fwd: elem_size %d not supported", elem_size);
+  UP_SHAPE_CHECK("ce_up_fwd");
+  NASSEG_TRY(check_elem_size("ce_up_fwd", elem_size));
   NASSEG_REQUIRE(logits && target && loss && stats && counts && pixel_loss && lse && ws, "ce_up_fwd: null pointer");
-  NASSEG_REQUIRE(!select || (min_kept >= 1 && keep_fraction >= 0.0 && keep_fraction <= 1.0),
-                 "ce_up_fwd: selection needs min_kept >= 1 and 0 <= keep_fraction <= 1");
+  NASSEG_TRY(check_selection("ce_up_fwd", select, min_kept, keep_fraction));
   hipStream_t s = (hipStream_t)stream;
   const int64_t P = (int64_t)B * H * W;
-  const int grid = up_grid(P);
   const float sh = (float)h / (float)H, sw = (float)w / (float)W;
-  if (elem_size == 8)
-    hipLaunchKernelGGL(ce_up_fwd_kernel<int64_t>, dim3(grid), dim3(256), 0, s, logits, (const int64_t*)target, B, h,
-                       w, C, H, W, sh, sw, ignore, pixel_loss, lse);
-  else
-    hipLaunchKernelGGL(ce_up_fwd_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)target, B, h,
-                       w, C, H, W, sh, sw, ignore, pixel_loss, lse);
+  with_labels(target, elem_size, [&](auto labels) {
+    hipLaunchKernelGGL(ce_up_fwd_kernel<label_of<decltype(labels)>>, dim3(ce_grid(P)), dim3(256), 0, s, logits, labels,
+                       B, h, w, C, H, W, sh, sw, ignore, pixel_loss, lse);
+  });
   NASSEG_LAUNCH_CHECK("ce_up_fwd");
-  if (select) {
-    const int rc = nasseg_ohem_threshold(pixel_loss, P, t_loss, min_kept, keep_fraction, stats + 1, counts,
-                                         ws + 3 * kUpGridCap, stream);
-    if (rc != NASSEG_OK) return rc;
-  }
-  const float* tau = select ? stats + 1 : nullptr;
-  if (elem_size == 8)
-    hipLaunchKernelGGL(ce_up_sum_kernel<int64_t>, dim3(grid), dim3(256), 0, s, pixel_loss, (const int64_t*)target,
-                       weight, P, tau, ws);
-  else
-    hipLaunchKernelGGL(ce_up_sum_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, pixel_loss, (const uint8_t*)target,
-                       weight, P, tau, ws);
-  NASSEG_LAUNCH_CHECK("ce_up_sum");
-  hipLaunchKernelGGL(ce_up_finalize_kernel, dim3(1), dim3(256), 0, s, ws, grid, select, loss, stats, counts);
-  NASSEG_LAUNCH_CHECK("ce_up_finalize");
-  return NASSEG_OK;
+  const auto selection = [&](float* tau, int64_t* cnt) {  // (the stand-alone one: include/nasseg.h)
+    return nasseg_ohem_threshold(pixel_loss, P, t_loss, min_kept, keep_fraction, tau, cnt, ws + 3 * kCeGridCap, stream);
+  };
+  return ce_sel_reduce("ce_up_sum", "ce_up_finalize", selection, pixel_loss, target, elem_size, weight, P, select, loss,
+                       stats, counts, ws, s);
 }
 
 int NASSEG_FN(ce_up_bwd)(const act_t* logits, const void* target, int elem_size, const float* weight,
                          const float* pixel_loss, const float* lse, const float* stats, const float* gscale, int B,
                          int h, int w, int C, int H, int W, int ignore, act_t* dlogits, void* stream) {
   (void)ignore;  // (validity is pixel_loss >= 0: the forward decided it)
-  NASSEG_REQUIRE(up_shape_ok(B, h, w, C, H, W), "ce_up_bwd: bad shape (C >= 2, B*H*W < 2^32, B*h*w*C < 2^31, fewer than 2^24 backward tiles)");
-  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, "ce_up_bwd: elem_size %d not supported", elem_size);
+  UP_SHAPE_CHECK("ce_up_bwd");
+  NASSEG_TRY(check_elem_size("ce_up_bwd", elem_size));
   NASSEG_REQUIRE(logits && target && pixel_loss && lse && stats && dlogits, "ce_up_bwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
   const int tiles_y = cdiv(h, kUpTile), tiles_x = cdiv(w, kUpTile), nchunk = cdiv(C, kUpChunk);
@@ -360,22 +257,17 @@ int NASSEG_FN(ce_up_bwd)(const act_t* logits, const void* target, int elem_size,
   const size_t lds = (size_t)kUpPatch * kUpPatch * (cmax | 1) * sizeof(float);
   const float sh = (float)h / (float)H, sw = (float)w / (float)W;
   const bool vec = nchunk == 1 && ((uintptr_t)logits & 15) == 0;
-#define NASSEG_UP_BWD(TL, VEC)                                                                                       \
-  hipLaunchKernelGGL((ce_up_bwd_kernel<TL, VEC>), dim3((unsigned)nwg), dim3(256), lds, s, logits, (const TL*)target, \
-                     weight, pixel_loss, lse, stats, gscale, B, h, w, C, H, W, sh, sw, tiles_y, tiles_x, nchunk,    \
-                     dlogits)
-  if (elem_size == 8) {
+  with_labels(target, elem_size, [&](auto labels) {
+    using TL = label_of<decltype(labels)>;
+    const auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(256), lds, s, logits, labels, weight, pixel_loss, lse, stats,
+                         gscale, B, h, w, C, H, W, sh, sw, tiles_y, tiles_x, nchunk, dlogits);
+    };
     if (vec)
-      NASSEG_UP_BWD(int64_t, true);
+      launch(ce_up_bwd_kernel<TL, true>);
     else
-      NASSEG_UP_BWD(int64_t, false);
-  } else {
-    if (vec)
-      NASSEG_UP_BWD(uint8_t, true);
-    else
-      NASSEG_UP_BWD(uint8_t, false);
-  }
-#undef NASSEG_UP_BWD
+      launch(ce_up_bwd_kernel<TL, false>);
+  });
   NASSEG_LAUNCH_CHECK("ce_up_bwd");
   return NASSEG_OK;
 }

@@ -19,7 +19,8 @@
 // Everything is launched with a geometry that depends on (P, C) alone: capturable; no allocation, no float atomics.
 #include <math.h>
 
-#include "common.h"
+#define NASSEG_LOSS_NO_SUM_PASS  // (nothing here sums per-pixel losses)
+#include "loss_common.h"
 
 namespace {
 
@@ -35,7 +36,6 @@ __device__ __forceinline__ float lov_error(uint32_t key) { return __uint_as_floa
 __device__ __forceinline__ int64_t lov_label(const void* target, int elem_size, int64_t p) {
   return elem_size == 8 ? ((const int64_t*)target)[p] : (int64_t)((const uint8_t*)target)[p];
 }
-__device__ __forceinline__ bool lov_valid(int64_t t, int C, int ignore) { return !(t == ignore || t < 0 || t >= C); }
 
 // cnt = {N_c} (C words) | n | |K|
 __global__ __launch_bounds__(256) void lov_zero_kernel(uint32_t* __restrict__ cnt, int n) {
@@ -57,7 +57,7 @@ __device__ __forceinline__ void lov_stage(const T* __restrict__ src, float* __re
 // of the region term and of nasseg_ce_fwd, the product and the difference rounded separately (no contraction): a
 // function of the pixel's own row.  `row` (stride 1) holds x and receives the errors.
 __device__ __forceinline__ void lov_err_row(float* __restrict__ row, int64_t t, int C, int ignore) {
-  if (!lov_valid(t, C, ignore)) {
+  if (!label_valid(t, C, ignore)) {
     for (int c = 0; c < C; ++c) row[c] = -1.f;
     return;
   }
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void lov_keys_kernel(const float* __restrict__
   int64_t t = -1;
   if (p < P) {
     t = lov_label(target, elem_size, p);
-    valid = lov_valid(t, C, ignore);
+    valid = label_valid(t, C, ignore);
   }
   const int nv = __popcll(__ballot(valid));
   if (in_lds) {
@@ -501,7 +501,7 @@ __global__ __launch_bounds__(256) void lov_bwd_tile_kernel(const act_t* __restri
   __syncthreads();
   if (tid < np) {
     float* row = tile + tid * CS;
-    if (lov_valid((int64_t)target[p0 + tid], C, ignore))
+    if (label_valid((int64_t)target[p0 + tid], C, ignore))
       lov_bwd_row(row, gt + tid * CS, C, gl);
     else
       for (int c = 0; c < C; ++c) row[c] = 0.f;
@@ -529,7 +529,7 @@ __global__ __launch_bounds__(256) void lov_bwd_kernel(const act_t* __restrict__ 
   const act_t* lp = logits + p * C;
   const float* gp = coef + p * C;
   act_t* dp = dlogits + p * C;
-  if (!lov_valid(t, C, ignore)) {
+  if (!label_valid(t, C, ignore)) {
     if (!accumulate)
       for (int c = 0; c < C; ++c) sta1(dp + c, 0.f);
     return;
@@ -633,14 +633,15 @@ int lov_launch(const float* errors, const void* target, int elem_size, int64_t P
   return NASSEG_OK;
 }
 
-}  // namespace
+int lov_check(const char* who, int64_t P, int C, int elem_size) {
+  NASSEG_REQUIRE(P > 0 && C >= 2 && C <= 65535, "%s: P > 0 and 2 <= C <= 65535 expected (got P = %lld, C = %d)", who,
+                 (long long)P, C);
+  NASSEG_REQUIRE(P * (int64_t)C < ((int64_t)1 << 31), "%s: P * C must stay below 2^31 (got %lld x %d)", who,
+                 (long long)P, C);
+  return check_elem_size(who, elem_size);
+}
 
-#define LOV_SHAPE_CHECK(who)                                                                                   \
-  NASSEG_REQUIRE(P > 0 && C >= 2 && C <= 65535, who ": P > 0 and 2 <= C <= 65535 expected (got P = %lld, C = %d)", \
-                 (long long)P, C);                                                                             \
-  NASSEG_REQUIRE(P * (int64_t)C < ((int64_t)1 << 31), who ": P * C must stay below 2^31 (got %lld x %d)",      \
-                 (long long)P, C);                                                                             \
-  NASSEG_REQUIRE(elem_size == 8 || elem_size == 1, who ": elem_size %d not supported", elem_size)
+}  // namespace
 
 extern "C" {
 
@@ -652,7 +653,7 @@ int64_t nasseg_lovasz_workspace(int64_t P, int C) {
 
 int nasseg_lovasz_coef(const float* errors, const void* target, int elem_size, int64_t P, int C, int ignore,
                        int all_classes, float* loss, float* coef, int* rank, int64_t* ncls, float* ws, void* stream) {
-  LOV_SHAPE_CHECK("lovasz_coef");
+  NASSEG_TRY(lov_check("lovasz_coef", P, C, elem_size));
   NASSEG_REQUIRE(errors && target && loss && coef && ncls && ws, "lovasz_coef: null pointer");
   NASSEG_REQUIRE(((uintptr_t)ws & 7) == 0, "lovasz_coef: the workspace must be 8-byte aligned");
   return lov_launch(errors, target, elem_size, P, C, ignore, all_classes != 0, 1.0, nullptr, loss, nullptr,
@@ -664,24 +665,19 @@ int NASSEG_FN(lovasz_fwd)(const act_t* logits, const void* target, int elem_size
                           int all_classes, double lovasz_weight, const float* base_loss, float* loss,
                           float* loss_lovasz, float* errors, float* coef, int* rank, int64_t* ncls, float* ws,
                           void* stream) {
-  LOV_SHAPE_CHECK("lovasz_fwd");
+  NASSEG_TRY(lov_check("lovasz_fwd", P, C, elem_size));
   NASSEG_REQUIRE(logits && target && loss && errors && coef && ncls && ws, "lovasz_fwd: null pointer");
   NASSEG_REQUIRE(((uintptr_t)ws & 7) == 0, "lovasz_fwd: the workspace must be 8-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const unsigned grid = (unsigned)cdiv64(P, 256);
   const size_t lds = (size_t)256 * (C | 1) * sizeof(float);
-  if (C <= 63 && elem_size == 8)
-    hipLaunchKernelGGL(lov_err_tile_kernel<int64_t>, dim3(grid), dim3(256), lds, s, logits, (const int64_t*)target, P,
-                       C, ignore, errors);
-  else if (C <= 63)
-    hipLaunchKernelGGL(lov_err_tile_kernel<uint8_t>, dim3(grid), dim3(256), lds, s, logits, (const uint8_t*)target, P,
-                       C, ignore, errors);
-  else if (elem_size == 8)
-    hipLaunchKernelGGL(lov_err_kernel<int64_t>, dim3(grid), dim3(256), 0, s, logits, (const int64_t*)target, P, C,
-                       ignore, errors);
-  else
-    hipLaunchKernelGGL(lov_err_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)target, P, C,
-                       ignore, errors);
+  with_labels(target, elem_size, [&](auto labels) {
+    using TL = label_of<decltype(labels)>;
+    if (C <= 63)
+      hipLaunchKernelGGL(lov_err_tile_kernel<TL>, dim3(grid), dim3(256), lds, s, logits, labels, P, C, ignore, errors);
+    else
+      hipLaunchKernelGGL(lov_err_kernel<TL>, dim3(grid), dim3(256), 0, s, logits, labels, P, C, ignore, errors);
+  });
   NASSEG_LAUNCH_CHECK("lovasz_errors");
   return lov_launch(errors, target, elem_size, P, C, ignore, all_classes != 0, lovasz_weight, base_loss,
                                loss, loss_lovasz, coef, rank, ncls, ws, s);
@@ -690,24 +686,21 @@ int NASSEG_FN(lovasz_fwd)(const act_t* logits, const void* target, int elem_size
 int NASSEG_FN(lovasz_bwd)(const act_t* logits, const void* target, int elem_size, const float* coef,
                           const float* gscale, double lovasz_weight, int accumulate, int64_t P, int C, int ignore,
                           act_t* dlogits, void* stream) {
-  LOV_SHAPE_CHECK("lovasz_bwd");
+  NASSEG_TRY(lov_check("lovasz_bwd", P, C, elem_size));
   NASSEG_REQUIRE(logits && target && coef && dlogits, "lovasz_bwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
   const unsigned grid = (unsigned)cdiv64(P, 256);
   const float lw = (float)lovasz_weight;
   const size_t lds = (size_t)2 * 256 * (C | 1) * sizeof(float);
-  if (C <= 31 && elem_size == 8)
-    hipLaunchKernelGGL(lov_bwd_tile_kernel<int64_t>, dim3(grid), dim3(256), lds, s, logits, (const int64_t*)target,
-                       coef, gscale, lw, accumulate, P, C, ignore, dlogits);
-  else if (C <= 31)
-    hipLaunchKernelGGL(lov_bwd_tile_kernel<uint8_t>, dim3(grid), dim3(256), lds, s, logits, (const uint8_t*)target,
-                       coef, gscale, lw, accumulate, P, C, ignore, dlogits);
-  else if (elem_size == 8)
-    hipLaunchKernelGGL(lov_bwd_kernel<int64_t>, dim3(grid), dim3(256), 0, s, logits, (const int64_t*)target, coef,
-                       gscale, lw, accumulate, P, C, ignore, dlogits);
-  else
-    hipLaunchKernelGGL(lov_bwd_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)target, coef,
-                       gscale, lw, accumulate, P, C, ignore, dlogits);
+  with_labels(target, elem_size, [&](auto labels) {
+    using TL = label_of<decltype(labels)>;
+    if (C <= 31)
+      hipLaunchKernelGGL(lov_bwd_tile_kernel<TL>, dim3(grid), dim3(256), lds, s, logits, labels, coef, gscale, lw,
+                         accumulate, P, C, ignore, dlogits);
+    else
+      hipLaunchKernelGGL(lov_bwd_kernel<TL>, dim3(grid), dim3(256), 0, s, logits, labels, coef, gscale, lw, accumulate,
+                         P, C, ignore, dlogits);
+  });
   NASSEG_LAUNCH_CHECK("lovasz_bwd");
   return NASSEG_OK;
 }

@@ -2453,24 +2453,59 @@ def broadcast_to(v, size, dtype=None):
 # ---------------------------------------------------------------------------
 # loss and reward
 # ---------------------------------------------------------------------------
-def _label_tensor(target):
+def _label_tensor(target, who=None):
     require_device(target)
     if target.dtype == torch.int64:
         return target.contiguous(), 8
     if target.dtype == torch.uint8:
         return target.contiguous(), 1
-    raise NassegError("labels must be int64 or uint8 (got {})".format(target.dtype))
+    raise NassegError("{}labels must be int64 or uint8 (got {})".format("" if who is None else who + ": ",
+                                                                        target.dtype))
+
+
+def _segm_inputs(who, logits, target, weight, same_size=True):
+    """(logits, target, esz, weight) as the segmentation losses' kernels read them: NHWC logits (B, C, h, w),
+    contiguous labels of ``esz`` bytes and the logits' size (``same_size=False``: (B, H, W) of any size), fp32 class
+    weights (C,) or None.  ``who``: the public function the user called, named by every NassegError."""
+    logits = _cl(logits)
+    B, C, H, W = logits.shape
+    target, esz = _label_tensor(target, who)
+    if same_size:
+        if tuple(target.shape) != (B, H, W):
+            raise NassegError("{}: target {} does not match logits {}".format(who, tuple(target.shape),
+                                                                             tuple(logits.shape)))
+    elif target.dim() != 3 or target.shape[0] != B or target.numel() == 0:
+        raise NassegError("{}: the target must be uint8 or int64 of shape ({}, H, W) (got {})".format(
+            who, B, tuple(target.shape)))
+    if weight is not None:
+        require_device(weight)
+        if weight.dtype != torch.float32 or tuple(weight.shape) != (C,):
+            raise NassegError("{}: the class weights must be fp32 of shape ({},) (got {} {})".format(
+                who, C, weight.dtype, tuple(weight.shape)))
+        weight = weight.contiguous()
+    return logits, target, esz, weight
+
+
+def _scalar(like):
+    return torch.empty((), device=like.device, dtype=torch.float32)
+
+
+def _ce_outputs(like, B, H, W):
+    """what a cross-entropy forward writes besides its loss: stats = {sum of the kept weights, tau}, counts =
+    {k, n_valid, n_kept} (int64) and pixel_loss (B, H, W)"""
+    return (_vec(like, 2), torch.empty((3,), device=like.device, dtype=torch.int64),
+            torch.empty((B, H, W), device=like.device, dtype=torch.float32))
+
+
+def _upstream(g):
+    return g.to(torch.float32).contiguous().view(1)
 
 
 class _LogSoftmaxNLL(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, ignore_index):
-        logits = _cl(logits)
+        logits, target, esz, _ = _segm_inputs("log_softmax_nll", logits, target, None)
         B, C, H, W = logits.shape
-        target, esz = _label_tensor(target)
-        if tuple(target.shape) != (B, H, W):
-            raise NassegError("loss: target {} does not match logits {}".format(
-                tuple(target.shape), tuple(logits.shape)))
         out = _vec(logits, 2)
         ws = _ws(logits, lib.query("nasseg_ce_workspace"))
         lib.call(_k("nasseg_ce_fwd", logits), ptr(logits), ptr(target), esz, B * H * W, C, int(ignore_index),
@@ -2484,7 +2519,7 @@ class _LogSoftmaxNLL(torch.autograd.Function):
         logits, target, out = ctx.saved_tensors
         esz, ignore = ctx.cfg
         B, C, H, W = logits.shape
-        g = g.to(torch.float32).contiguous().view(1)
+        g = _upstream(g)
         d = torch.empty_like(logits)
         lib.call(_k("nasseg_ce_bwd", logits), ptr(logits), ptr(target), esz, ptr(out), ptr(g), B * H * W, C,
                  ignore, ptr(d), current_stream())
@@ -2503,19 +2538,14 @@ class _LogSoftmaxNLLMSE(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, target, teacher, ignore_index):
-        logits = _cl(logits)
+        logits, target, esz, _ = _segm_inputs("log_softmax_nll_mse", logits, target, None)
         B, C, H, W = logits.shape
-        target, esz = _label_tensor(target)
-        if tuple(target.shape) != (B, H, W):
-            raise NassegError("loss: target {} does not match logits {}".format(
-                tuple(target.shape), tuple(logits.shape)))
         require_device(teacher)
         if tuple(teacher.shape) != (B, C, H, W) or teacher.dtype != torch.float32:
             raise NassegError("log_softmax_nll_mse: the teacher must be fp32 of the logits' shape {} (got {} {})"
                               .format(tuple(logits.shape), teacher.dtype, tuple(teacher.shape)))
         teacher = teacher.contiguous(memory_format=torch.channels_last)
-        nll = torch.empty((), device=logits.device, dtype=torch.float32)
-        mse = torch.empty((), device=logits.device, dtype=torch.float32)
+        nll, mse = _scalar(logits), _scalar(logits)
         stats = _vec(logits, 2)
         ws = _ws(logits, lib.query("nasseg_ce_mse_workspace"))
         lib.call(_k("nasseg_ce_mse_fwd", logits), ptr(logits), ptr(target), esz, ptr(teacher), B * H * W, C,
@@ -2529,8 +2559,7 @@ class _LogSoftmaxNLLMSE(torch.autograd.Function):
         logits, target, teacher, stats = ctx.saved_tensors
         esz, ignore = ctx.cfg
         B, C, H, W = logits.shape
-        g_nll = g_nll.to(torch.float32).contiguous().view(1)
-        g_mse = g_mse.to(torch.float32).contiguous().view(1)
+        g_nll, g_mse = _upstream(g_nll), _upstream(g_mse)
         d = torch.empty_like(logits)
         lib.call(_k("nasseg_ce_mse_bwd", logits), ptr(logits), ptr(target), esz, ptr(teacher), ptr(stats),
                  ptr(g_nll), ptr(g_mse), B * H * W, C, ignore, ptr(d), current_stream())
@@ -2568,50 +2597,6 @@ def _select_config(who, thresh, min_kept, keep_fraction):
     return int(select), t_loss, min_kept, keep_fraction
 
 
-class _CrossEntropySelect(torch.autograd.Function):
-    """nasseg_ce_sel_fwd / _bwd.  Outputs: the loss (a scalar of its own: ``loss += aux`` is fine), and - not
-    differentiable - pixel_loss (B, H, W), tau (0-dim) and counts = {k, n_valid, n_kept} (int64)."""
-
-    @staticmethod
-    def forward(ctx, logits, target, weight, ignore_index, cfg):
-        logits = _cl(logits)
-        B, C, H, W = logits.shape
-        target, esz = _label_tensor(target)
-        if tuple(target.shape) != (B, H, W):
-            raise NassegError("cross_entropy_select: target {} does not match logits {}".format(
-                tuple(target.shape), tuple(logits.shape)))
-        if weight is not None:
-            require_device(weight)
-            if weight.dtype != torch.float32 or tuple(weight.shape) != (C,):
-                raise NassegError("cross_entropy_select: the class weights must be fp32 of shape ({},) (got {} {})"
-                                  .format(C, weight.dtype, tuple(weight.shape)))
-            weight = weight.contiguous()
-        loss = torch.empty((), device=logits.device, dtype=torch.float32)
-        stats = _vec(logits, 2)
-        counts = torch.empty((3,), device=logits.device, dtype=torch.int64)
-        pixel_loss = torch.empty((B, H, W), device=logits.device, dtype=torch.float32)
-        ws = _ws(logits, lib.query("nasseg_ce_sel_workspace"))
-        lib.call(_k("nasseg_ce_sel_fwd", logits), ptr(logits), ptr(target), esz, ptr(weight), B * H * W, C,
-                 int(ignore_index), *cfg, ptr(loss), ptr(stats), ptr(counts), ptr(pixel_loss), ptr(ws),
-                 current_stream())
-        ctx.save_for_backward(logits, target, weight, pixel_loss, stats)
-        ctx.cfg = (esz, int(ignore_index))
-        tau = _own_scalar(stats, 1)
-        ctx.mark_non_differentiable(pixel_loss, tau, counts)
-        return loss, pixel_loss, tau, counts
-
-    @staticmethod
-    def backward(ctx, g, *unused):
-        logits, target, weight, pixel_loss, stats = ctx.saved_tensors
-        esz, ignore = ctx.cfg
-        B, C, H, W = logits.shape
-        g = g.to(torch.float32).contiguous().view(1)
-        d = torch.empty_like(logits)
-        lib.call(_k("nasseg_ce_sel_bwd", logits), ptr(logits), ptr(target), esz, ptr(weight), ptr(pixel_loss),
-                 ptr(stats), ptr(g), B * H * W, C, ignore, ptr(d), current_stream())
-        return d, None, None, None, None
-
-
 def _region_config(who, region, smooth=1.0, classes="present", region_weight=1.0):
     """(alpha, beta, smooth, all_classes, region_weight) of a region-overlap term; ValueError where the definition
     ("Losses") has no meaning.  ``region``: "jaccard" | "dice" | ("tversky", alpha, beta)"""
@@ -2639,63 +2624,6 @@ def _region_config(who, region, smooth=1.0, classes="present", region_weight=1.0
     return alpha, beta, smooth, int(classes == "all"), region_weight
 
 
-class _CrossEntropyRegion(torch.autograd.Function):
-    """nasseg_ce_region_fwd / _bwd.  ``cfg``: the selection of _CrossEntropySelect, or None - the region term alone
-    (no weights, no pixel_loss).  Outputs: the loss (a scalar of its own), and - not differentiable - loss_ce,
-    loss_region, pixel_loss, tau, counts, sums = I | S (2C,), ncls = N | |K| (C + 1,) int64."""
-
-    @staticmethod
-    def forward(ctx, logits, target, weight, ignore_index, cfg, rcfg):
-        logits = _cl(logits)
-        B, C, H, W = logits.shape
-        target, esz = _label_tensor(target)
-        if tuple(target.shape) != (B, H, W):
-            raise NassegError("cross_entropy_select: target {} does not match logits {}".format(
-                tuple(target.shape), tuple(logits.shape)))
-        with_ce = cfg is not None
-        if weight is not None:
-            require_device(weight)
-            if weight.dtype != torch.float32 or tuple(weight.shape) != (C,):
-                raise NassegError("cross_entropy_select: the class weights must be fp32 of shape ({},) (got {} {})"
-                                  .format(C, weight.dtype, tuple(weight.shape)))
-            weight = weight.contiguous()
-        alpha, beta, smooth, all_classes, region_weight = rcfg
-        dev = logits.device
-        loss = torch.empty((), device=dev, dtype=torch.float32)
-        loss_ce = torch.empty((), device=dev, dtype=torch.float32)
-        loss_region = torch.empty((), device=dev, dtype=torch.float32)
-        coef, sums = _vec(logits, 2 * C), _vec(logits, 2 * C)
-        ncls = torch.empty((C + 1,), device=dev, dtype=torch.int64)
-        stats = counts = pixel_loss = tau = None
-        if with_ce:
-            stats = _vec(logits, 2)
-            counts = torch.empty((3,), device=dev, dtype=torch.int64)
-            pixel_loss = torch.empty((B, H, W), device=dev, dtype=torch.float32)
-            tau = _own_scalar(stats, 1)
-        ws = _ws(logits, lib.query("nasseg_ce_region_workspace", C))
-        lib.call(_k("nasseg_ce_region_fwd", logits), ptr(logits), ptr(target), esz, ptr(weight), B * H * W, C,
-                 int(ignore_index), int(with_ce), *(cfg if with_ce else (0, float("inf"), 0, 0.0)), alpha, beta,
-                 smooth, all_classes, region_weight, ptr(loss), ptr(loss_ce), ptr(loss_region), ptr(stats),
-                 ptr(counts), ptr(pixel_loss), ptr(coef), ptr(sums), ptr(ncls), ptr(ws), current_stream())
-        ctx.save_for_backward(logits, target, weight, pixel_loss, stats, coef)
-        ctx.cfg = (esz, int(ignore_index), int(with_ce), region_weight)
-        outs = (loss, loss_ce, loss_region, pixel_loss, tau, counts, sums, ncls)
-        ctx.mark_non_differentiable(*[o for o in outs[1:] if o is not None])
-        return outs
-
-    @staticmethod
-    def backward(ctx, g, *unused):
-        logits, target, weight, pixel_loss, stats, coef = ctx.saved_tensors
-        esz, ignore, with_ce, region_weight = ctx.cfg
-        B, C, H, W = logits.shape
-        g = g.to(torch.float32).contiguous().view(1)
-        d = torch.empty_like(logits)
-        lib.call(_k("nasseg_ce_region_bwd", logits), ptr(logits), ptr(target), esz, ptr(weight), ptr(pixel_loss),
-                 ptr(stats), ptr(coef), ptr(g), with_ce, region_weight, B * H * W, C, ignore, ptr(d),
-                 current_stream())
-        return d, None, None, None, None, None
-
-
 def _lovasz_config(who, lovasz_weight=1.0, classes="present"):
     """(lovasz_weight, all_classes) of a Lovasz-Softmax term; ValueError where the definition (INTEGRATION.md,
     "Losses") has no meaning"""
@@ -2708,6 +2636,19 @@ def _lovasz_config(who, lovasz_weight=1.0, classes="present"):
     if classes not in ("present", "all"):
         raise ValueError("{}: lovasz_classes must be \"present\" or \"all\" (got {!r})".format(who, classes))
     return lovasz_weight, int(classes == "all")
+
+
+def _segm_config(who, thresh=None, min_kept=0, keep_fraction=0.0, region=None, region_weight=1.0, region_smooth=1.0,
+                 region_classes="present", lovasz_weight=None, lovasz_classes="present"):
+    """``cross_entropy_select``'s keyword arguments -> (cfg, rcfg, lcfg): the selection, and the region and Lovasz
+    terms or None where there is no such term; ValueError as the three functions above raise it"""
+    cfg = _select_config(who, thresh, min_kept, keep_fraction)
+    rcfg = lcfg = None
+    if region is not None:
+        rcfg = _region_config(who, region, region_smooth, region_classes, region_weight)
+    if lovasz_weight is not None:
+        lcfg = _lovasz_config(who, lovasz_weight, lovasz_classes)
+    return cfg, rcfg, lcfg
 
 
 def _lovasz_forward(logits, target, esz, ignore_index, lcfg, base, want_parts):
@@ -2736,35 +2677,87 @@ def _lovasz_backward(logits, target, esz, ignore, coef, g, lovasz_weight, accumu
     return d
 
 
-class _LovaszSoftmax(torch.autograd.Function):
-    """nasseg_lovasz_fwd / _bwd alone.  Outputs: the loss (a scalar of its own), and - not differentiable, None
-    unless ``want_parts`` - errors (B, H, W, C), rank (B, H, W, C) int32, ncls = N | |K| (C + 1,) int64.  Kept for
-    backward beyond the logits and labels: G, one fp32 [P][C] tensor."""
+# What _SegmCriterion returns; a part its terms do not produce is None.  sums = I | S (2C,) and region_ncls = N | |K|
+# (C + 1,) int64 are the region term's; errors, rank (B, H, W, C) and lovasz_ncls the Lovasz term's when it runs alone
+# and its parts are wanted.
+_SegmParts = collections.namedtuple("_SegmParts", "loss pixel_loss tau counts loss_ce loss_region loss_lovasz sums "
+                                                  "region_ncls errors rank lovasz_ncls")
+
+
+class _SegmCriterion(torch.autograd.Function):
+    """The composed criterion over logits at the labels' size, one node and one dlogits: the cross-entropy with class
+    weights and selection ``cfg`` (nasseg_ce_sel_fwd / _bwd), with the region term ``rcfg`` computed by the same two
+    passes (nasseg_ce_region_fwd / _bwd, which also run the region term alone), plus the Lovasz term ``lcfg``:
+    nasseg_lovasz_fwd adds it onto the base loss on the device, nasseg_lovasz_bwd adds its gradient onto what the
+    base's backward launch has just written (or writes it, alone).  Any of the three may be None, not all.
+    Outputs: the fields of _SegmParts - the loss (a scalar of its own: ``loss += aux`` is fine), the others not
+    differentiable.  Kept for backward beyond the logits and labels: what the terms present need - pixel_loss and
+    stats (cross-entropy), 2C coefficients (region), G, one fp32 [P][C] tensor (Lovasz)."""
 
     @staticmethod
-    def forward(ctx, logits, target, ignore_index, lcfg, want_parts):
-        logits = _cl(logits)
+    def forward(ctx, logits, target, weight, ignore_index, cfg, rcfg, lcfg, want_parts):
+        with_ce = cfg is not None
+        who = "cross_entropy_select" if with_ce else "region_overlap_loss" if rcfg else "lovasz_softmax_loss"
+        logits, target, esz, weight = _segm_inputs(who, logits, target, weight)
         B, C, H, W = logits.shape
-        target, esz = _label_tensor(target)
-        if tuple(target.shape) != (B, H, W):
-            raise NassegError("lovasz_softmax_loss: target {} does not match logits {}".format(
-                tuple(target.shape), tuple(logits.shape)))
-        loss, _, errors, coef, rank, ncls = _lovasz_forward(logits, target, esz, ignore_index, (1.0, lcfg[1]), None,
-                                                            want_parts)
-        ctx.save_for_backward(logits, target, coef)
-        ctx.cfg = (esz, int(ignore_index))
-        if not want_parts:
-            return loss, None, None, None
-        ctx.mark_non_differentiable(errors, rank, ncls)
-        return loss, errors, rank, ncls
+        ignore = int(ignore_index)
+        loss = stats = counts = pixel_loss = tau = loss_ce = loss_region = rcoef = sums = rncls = None
+        if with_ce:
+            stats, counts, pixel_loss = _ce_outputs(logits, B, H, W)
+            tau = _own_scalar(stats, 1)
+        if rcfg is not None:
+            alpha, beta, smooth, all_classes, region_weight = rcfg
+            loss, loss_ce, loss_region = _scalar(logits), _scalar(logits), _scalar(logits)
+            rcoef, sums = _vec(logits, 2 * C), _vec(logits, 2 * C)
+            rncls = torch.empty((C + 1,), device=logits.device, dtype=torch.int64)
+            ws = _ws(logits, lib.query("nasseg_ce_region_workspace", C))
+            lib.call(_k("nasseg_ce_region_fwd", logits), ptr(logits), ptr(target), esz, ptr(weight), B * H * W, C,
+                     ignore, int(with_ce), *(cfg if with_ce else (0, float("inf"), 0, 0.0)), alpha, beta, smooth,
+                     all_classes, region_weight, ptr(loss), ptr(loss_ce), ptr(loss_region), ptr(stats), ptr(counts),
+                     ptr(pixel_loss), ptr(rcoef), ptr(sums), ptr(rncls), ptr(ws), current_stream())
+        elif with_ce:
+            loss = _scalar(logits)
+            ws = _ws(logits, lib.query("nasseg_ce_sel_workspace"))
+            lib.call(_k("nasseg_ce_sel_fwd", logits), ptr(logits), ptr(target), esz, ptr(weight), B * H * W, C, ignore,
+                     *cfg, ptr(loss), ptr(stats), ptr(counts), ptr(pixel_loss), ptr(ws), current_stream())
+        llov = lcoef = errors = rank = lncls = None
+        if lcfg is not None:
+            alone = loss is None  # (no base to add onto: the term's own parts are what there is to return)
+            if rcfg is None:
+                loss_ce = loss
+            loss, llov, errors, lcoef, rank, lncls = _lovasz_forward(logits, target, esz, ignore, lcfg, loss,
+                                                                     want_parts and alone)
+            if alone:
+                llov = None
+            if errors is None:
+                lncls = None
+        ctx.save_for_backward(logits, target, weight, pixel_loss, stats, rcoef, lcoef)
+        ctx.cfg = (esz, ignore, with_ce, None if rcfg is None else rcfg[4], None if lcfg is None else lcfg[0])
+        outs = _SegmParts(loss, pixel_loss, tau, counts, loss_ce, loss_region, llov, sums, rncls, errors, rank, lncls)
+        ctx.mark_non_differentiable(*[o for o in outs[1:] if o is not None])
+        return tuple(outs)
 
     @staticmethod
     def backward(ctx, g, *unused):
-        logits, target, coef = ctx.saved_tensors
-        esz, ignore = ctx.cfg
-        g = g.to(torch.float32).contiguous().view(1)
-        d = _lovasz_backward(logits, target, esz, ignore, coef, g, 1.0, False, torch.empty_like(logits))
-        return d, None, None, None, None
+        logits, target, weight, pixel_loss, stats, rcoef, lcoef = ctx.saved_tensors
+        esz, ignore, with_ce, region_weight, lovasz_weight = ctx.cfg
+        B, C, H, W = logits.shape
+        g = _upstream(g)
+        d = torch.empty_like(logits)
+        if rcoef is not None:
+            lib.call(_k("nasseg_ce_region_bwd", logits), ptr(logits), ptr(target), esz, ptr(weight), ptr(pixel_loss),
+                     ptr(stats), ptr(rcoef), ptr(g), int(with_ce), region_weight, B * H * W, C, ignore, ptr(d),
+                     current_stream())
+        elif with_ce:
+            lib.call(_k("nasseg_ce_sel_bwd", logits), ptr(logits), ptr(target), esz, ptr(weight), ptr(pixel_loss),
+                     ptr(stats), ptr(g), B * H * W, C, ignore, ptr(d), current_stream())
+        if lcoef is not None:
+            _lovasz_backward(logits, target, esz, ignore, lcoef, g, lovasz_weight, with_ce or rcoef is not None, d)
+        return (d,) + (None,) * 7
+
+
+def _segm_criterion(logits, target, weight, ignore_index, cfg, rcfg, lcfg, want_parts=False):
+    return _SegmParts(*_SegmCriterion.apply(logits, target, weight, ignore_index, cfg, rcfg, lcfg, bool(want_parts)))
 
 
 def lovasz_softmax_loss(logits, target, classes="present", ignore_index=255, return_parts=False):
@@ -2782,11 +2775,11 @@ def lovasz_softmax_loss(logits, target, classes="present", ignore_index=255, ret
     N (C,) int64, |K| 0-dim int64).
     The sort runs on the device (a stable radix sort): deterministic, no host synchronisation: capturable."""
     lcfg = _lovasz_config("lovasz_softmax_loss", 1.0, classes)
-    loss, errors, rank, ncls = _LovaszSoftmax.apply(logits, target, ignore_index, lcfg, bool(return_parts))
+    out = _segm_criterion(logits, target, None, ignore_index, None, None, lcfg, return_parts)
     if not return_parts:
-        return loss
-    C = ncls.numel() - 1
-    return loss, errors, rank, ncls[:C], ncls[C]
+        return out.loss
+    C = out.lovasz_ncls.numel() - 1
+    return out.loss, out.errors, out.rank, out.lovasz_ncls[:C], out.lovasz_ncls[C]
 
 
 def lovasz_from_errors(errors, target, classes="present", ignore_index=255):
@@ -2813,76 +2806,6 @@ def lovasz_from_errors(errors, target, classes="present", ignore_index=255):
     return loss, coef, rank, ncls[:C], ncls[C]
 
 
-class _CrossEntropyLovasz(torch.autograd.Function):
-    """The cross-entropy of _CrossEntropySelect (``rcfg`` None) or _CrossEntropyRegion, by the very launches of those
-    nodes, plus ``lovasz_weight`` times the Lovasz-Softmax term: one node, one dlogits.  nasseg_lovasz_fwd adds its
-    term onto the base loss on the device; nasseg_lovasz_bwd adds its gradient onto what the base's backward launch
-    has just written.  Outputs: the loss (a scalar of its own), and - not differentiable - pixel_loss, tau, counts,
-    loss_ce, loss_region (None without a region term), loss_lovasz."""
-
-    @staticmethod
-    def forward(ctx, logits, target, weight, ignore_index, cfg, rcfg, lcfg):
-        logits = _cl(logits)
-        B, C, H, W = logits.shape
-        target, esz = _label_tensor(target)
-        if tuple(target.shape) != (B, H, W):
-            raise NassegError("cross_entropy_select: target {} does not match logits {}".format(
-                tuple(target.shape), tuple(logits.shape)))
-        if weight is not None:
-            require_device(weight)
-            if weight.dtype != torch.float32 or tuple(weight.shape) != (C,):
-                raise NassegError("cross_entropy_select: the class weights must be fp32 of shape ({},) (got {} {})"
-                                  .format(C, weight.dtype, tuple(weight.shape)))
-            weight = weight.contiguous()
-        dev = logits.device
-        base = torch.empty((), device=dev, dtype=torch.float32)
-        stats = _vec(logits, 2)
-        counts = torch.empty((3,), device=dev, dtype=torch.int64)
-        pixel_loss = torch.empty((B, H, W), device=dev, dtype=torch.float32)
-        rcoef = loss_region = None
-        if rcfg is None:
-            ws = _ws(logits, lib.query("nasseg_ce_sel_workspace"))
-            lib.call(_k("nasseg_ce_sel_fwd", logits), ptr(logits), ptr(target), esz, ptr(weight), B * H * W, C,
-                     int(ignore_index), *cfg, ptr(base), ptr(stats), ptr(counts), ptr(pixel_loss), ptr(ws),
-                     current_stream())
-            loss_ce = base
-        else:
-            alpha, beta, smooth, all_classes, region_weight = rcfg
-            loss_ce = torch.empty((), device=dev, dtype=torch.float32)
-            loss_region = torch.empty((), device=dev, dtype=torch.float32)
-            rcoef, sums = _vec(logits, 2 * C), _vec(logits, 2 * C)
-            ncls = torch.empty((C + 1,), device=dev, dtype=torch.int64)
-            ws = _ws(logits, lib.query("nasseg_ce_region_workspace", C))
-            lib.call(_k("nasseg_ce_region_fwd", logits), ptr(logits), ptr(target), esz, ptr(weight), B * H * W, C,
-                     int(ignore_index), 1, *cfg, alpha, beta, smooth, all_classes, region_weight, ptr(base),
-                     ptr(loss_ce), ptr(loss_region), ptr(stats), ptr(counts), ptr(pixel_loss), ptr(rcoef), ptr(sums),
-                     ptr(ncls), ptr(ws), current_stream())
-        loss, llov, _, coef, _, _ = _lovasz_forward(logits, target, esz, ignore_index, lcfg, base, False)
-        ctx.save_for_backward(logits, target, weight, pixel_loss, stats, rcoef, coef)
-        ctx.cfg = (esz, int(ignore_index), None if rcfg is None else rcfg[4], lcfg[0])
-        tau = _own_scalar(stats, 1)
-        outs = (loss, pixel_loss, tau, counts, loss_ce, loss_region, llov)
-        ctx.mark_non_differentiable(*[o for o in outs[1:] if o is not None])
-        return outs
-
-    @staticmethod
-    def backward(ctx, g, *unused):
-        logits, target, weight, pixel_loss, stats, rcoef, coef = ctx.saved_tensors
-        esz, ignore, region_weight, lovasz_weight = ctx.cfg
-        B, C, H, W = logits.shape
-        g = g.to(torch.float32).contiguous().view(1)
-        d = torch.empty_like(logits)
-        if rcoef is None:
-            lib.call(_k("nasseg_ce_sel_bwd", logits), ptr(logits), ptr(target), esz, ptr(weight), ptr(pixel_loss),
-                     ptr(stats), ptr(g), B * H * W, C, ignore, ptr(d), current_stream())
-        else:
-            lib.call(_k("nasseg_ce_region_bwd", logits), ptr(logits), ptr(target), esz, ptr(weight), ptr(pixel_loss),
-                     ptr(stats), ptr(rcoef), ptr(g), 1, region_weight, B * H * W, C, ignore, ptr(d),
-                     current_stream())
-        _lovasz_backward(logits, target, esz, ignore, coef, g, lovasz_weight, True, d)
-        return d, None, None, None, None, None, None
-
-
 def region_overlap_loss(logits, target, region="jaccard", smooth=1.0, classes="present", ignore_index=255,
                         return_parts=False):
     """Soft Jaccard / Dice / Tversky loss of (B, C, H, W) logits -> 0-dim loss of its own storage (INTEGRATION.md,
@@ -2896,12 +2819,11 @@ def region_overlap_loss(logits, target, region="jaccard", smooth=1.0, classes="p
     ``return_parts``: (loss, I (C,) fp32, S (C,) fp32, N (C,) int64, |K| 0-dim int64).
     Deterministic, no host synchronisation: capturable."""
     rcfg = _region_config("region_overlap_loss", region, smooth, classes)
-    out = _CrossEntropyRegion.apply(logits, target, None, ignore_index, None, rcfg)
+    out = _segm_criterion(logits, target, None, ignore_index, None, rcfg, None)
     if not return_parts:
-        return out[0]
-    sums, ncls = out[6], out[7]
-    C = sums.numel() // 2
-    return out[0], sums[:C], sums[C:], ncls[:C], ncls[C]
+        return out.loss
+    C = out.sums.numel() // 2
+    return out.loss, out.sums[:C], out.sums[C:], out.region_ncls[:C], out.region_ncls[C]
 
 
 def cross_entropy_select(logits, target, weight=None, ignore_index=255, thresh=None, min_kept=0, keep_fraction=0.0,
@@ -2928,41 +2850,32 @@ def cross_entropy_select(logits, target, weight=None, ignore_index=255, thresh=N
     the class weights, in the same autograd node; ``return_parts`` then ends with loss_ce (where it was absent) and
     loss_lovasz: (loss, pixel_loss, tau, counts, loss_ce[, loss_region], loss_lovasz).
     No host synchronisation: capturable."""
-    cfg = _select_config("cross_entropy_select", thresh, min_kept, keep_fraction)
-    rcfg = None
-    if region is not None:
-        rcfg = _region_config("cross_entropy_select", region, region_smooth, region_classes, region_weight)
-    if lovasz_weight is not None:
-        lcfg = _lovasz_config("cross_entropy_select", lovasz_weight, lovasz_classes)
-        out = _CrossEntropyLovasz.apply(logits, target, weight, ignore_index, cfg, rcfg, lcfg)
-        return tuple(o for i, o in enumerate(out) if i != 5 or rcfg is not None) if return_parts else out[0]
-    if rcfg is None:
-        out = _CrossEntropySelect.apply(logits, target, weight, ignore_index, cfg)
-        return out if return_parts else out[0]
-    out = _CrossEntropyRegion.apply(logits, target, weight, ignore_index, cfg, rcfg)
-    return (out[0], out[3], out[4], out[5], out[1], out[2]) if return_parts else out[0]
+    cfg, rcfg, lcfg = _segm_config("cross_entropy_select", thresh, min_kept, keep_fraction, region, region_weight,
+                                   region_smooth, region_classes, lovasz_weight, lovasz_classes)
+    out = _segm_criterion(logits, target, weight, ignore_index, cfg, rcfg, lcfg)
+    if not return_parts:
+        return out.loss
+    parts = (out.loss, out.pixel_loss, out.tau, out.counts)
+    if rcfg is not None or lcfg is not None:
+        parts += (out.loss_ce,)
+    if rcfg is not None:
+        parts += (out.loss_region,)
+    if lcfg is not None:
+        parts += (out.loss_lovasz,)
+    return parts
 
 
 class _CrossEntropyUpsampled(torch.autograd.Function):
-    """nasseg_ce_up_fwd / _bwd.  Outputs as _CrossEntropySelect's, pixel_loss at the labels' size (B, H, W)."""
+    """nasseg_ce_up_fwd / _bwd.  Outputs: the loss (a scalar of its own), and - not differentiable - pixel_loss at the
+    labels' size (B, H, W), tau (0-dim) and counts = {k, n_valid, n_kept} (int64)."""
 
     @staticmethod
     def forward(ctx, logits, target, weight, ignore_index, cfg):
-        logits = _cl(logits)
+        logits, target, esz, weight = _segm_inputs("cross_entropy_upsampled", logits, target, weight, same_size=False)
         B, C, h, w = logits.shape
-        target, esz = _label_tensor(target)
-        if target.dim() != 3 or target.shape[0] != B or target.numel() == 0:
-            raise NassegError("cross_entropy_upsampled: the target must be uint8 or int64 of shape ({}, H, W) (got {})"
-                              .format(B, tuple(target.shape)))
         if C < 2:
             raise NassegError("cross_entropy_upsampled: at least two classes are expected (got logits {})".format(
                 tuple(logits.shape)))
-        if weight is not None:
-            require_device(weight)
-            if weight.dtype != torch.float32 or tuple(weight.shape) != (C,):
-                raise NassegError("cross_entropy_upsampled: the class weights must be fp32 of shape ({},) (got {} {})"
-                                  .format(C, weight.dtype, tuple(weight.shape)))
-            weight = weight.contiguous()
         H, W = int(target.shape[1]), int(target.shape[2])
         dims = (B, h, w, C, H, W)
         n_ws = lib.query("nasseg_ce_up_workspace", *dims)
@@ -2970,12 +2883,9 @@ class _CrossEntropyUpsampled(torch.autograd.Function):
             raise NassegError("cross_entropy_upsampled: logits {} against labels {} exceed B*H*W < 2^32, "
                               "B*h*w*C < 2^31 or 2^24 tiles of 8 x 8 logits and 64 channels".format(
                                   tuple(logits.shape), tuple(target.shape)))
-        dev = logits.device
-        loss = torch.empty((), device=dev, dtype=torch.float32)
-        stats = _vec(logits, 2)
-        counts = torch.empty((3,), device=dev, dtype=torch.int64)
-        pixel_loss = torch.empty((B, H, W), device=dev, dtype=torch.float32)
-        lse = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+        loss = _scalar(logits)
+        stats, counts, pixel_loss = _ce_outputs(logits, B, H, W)
+        lse = torch.empty((B, H, W), device=logits.device, dtype=torch.float32)
         ws = _ws(logits, n_ws)
         lib.call(_k("nasseg_ce_up_fwd", logits), ptr(logits), ptr(target), esz, ptr(weight), *dims,
                  int(ignore_index), *cfg, ptr(loss), ptr(stats), ptr(counts), ptr(pixel_loss), ptr(lse), ptr(ws),
@@ -2990,7 +2900,7 @@ class _CrossEntropyUpsampled(torch.autograd.Function):
     def backward(ctx, g, *unused):
         logits, target, weight, pixel_loss, lse, stats = ctx.saved_tensors
         esz, ignore, dims = ctx.cfg
-        g = g.to(torch.float32).contiguous().view(1)
+        g = _upstream(g)
         d = torch.empty_like(logits)
         lib.call(_k("nasseg_ce_up_bwd", logits), ptr(logits), ptr(target), esz, ptr(weight), ptr(pixel_loss),
                  ptr(lse), ptr(stats), ptr(g), *dims, ignore, ptr(d), current_stream())

@@ -58,30 +58,34 @@ class SegmCrossEntropy(nn.Module):
             if weight.dim() != 1 or weight.numel() == 0:
                 raise ValueError("SegmCrossEntropy: weight must be 1-D, one entry per class (got shape {})".format(
                     tuple(weight.shape)))
-        F._select_config("SegmCrossEntropy", thresh, min_kept, keep_fraction)
         self.register_buffer("weight", weight)
         self.ignore_index = int(ignore_index)
         self.thresh = thresh
         self.min_kept = min_kept
         self.keep_fraction = keep_fraction
-        if region is not None:
-            F._region_config("SegmCrossEntropy", region, region_smooth, region_classes, region_weight)
-            region = tuple(region) if isinstance(region, list) else region
-        self.region = region
+        self.region = tuple(region) if isinstance(region, list) else region
         self.region_weight = region_weight
         self.region_smooth = region_smooth
         self.region_classes = region_classes
-        if lovasz_weight is not None:
-            F._lovasz_config("SegmCrossEntropy", lovasz_weight, lovasz_classes)
-        elif lovasz_classes not in ("present", "all"):
-            raise ValueError("SegmCrossEntropy: lovasz_classes must be \"present\" or \"all\" (got {!r})".format(
-                lovasz_classes))
         self.lovasz_weight = lovasz_weight
         self.lovasz_classes = lovasz_classes
+        F._segm_config("SegmCrossEntropy", thresh, min_kept, keep_fraction, **self._terms())
+        if lovasz_weight is None and lovasz_classes not in ("present", "all"):
+            raise ValueError("SegmCrossEntropy: lovasz_classes must be \"present\" or \"all\" (got {!r})".format(
+                lovasz_classes))
         if full_size and (region is not None or lovasz_weight is not None):
             raise ValueError("SegmCrossEntropy: full_size=True has no region or Lovasz term (those terms are defined "
                              "at the logits' size only)")
         self.full_size = bool(full_size)
+
+    def _terms(self):
+        """the keyword arguments of ``F.cross_entropy_select`` for the terms this criterion has"""
+        names = ()
+        if self.region is not None:
+            names += ("region", "region_weight", "region_smooth", "region_classes")
+        if self.lovasz_weight is not None:
+            names += ("lovasz_weight", "lovasz_classes")
+        return {name: getattr(self, name) for name in names}
 
     @property
     def selects(self):
@@ -109,17 +113,9 @@ class SegmCrossEntropy(nn.Module):
 
     def forward(self, logits, target):
         self.prepare(logits.device)
-        if self.full_size:
-            return F.cross_entropy_upsampled(logits, target, self.weight, self.ignore_index, self.thresh,
-                                             self.min_kept, self.keep_fraction)
-        terms = {}
-        if self.region is not None:
-            terms.update(region=self.region, region_weight=self.region_weight, region_smooth=self.region_smooth,
-                         region_classes=self.region_classes)
-        if self.lovasz_weight is not None:
-            terms.update(lovasz_weight=self.lovasz_weight, lovasz_classes=self.lovasz_classes)
-        return F.cross_entropy_select(logits, target, self.weight, self.ignore_index, self.thresh, self.min_kept,
-                                      self.keep_fraction, **terms)
+        loss = F.cross_entropy_upsampled if self.full_size else F.cross_entropy_select
+        return loss(logits, target, self.weight, self.ignore_index, self.thresh, self.min_kept, self.keep_fraction,
+                    **self._terms())
 
     def extra_repr(self):
         s = "classes={}, ignore_index={}, thresh={}, min_kept={}, keep_fraction={}".format(
