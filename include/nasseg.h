@@ -604,6 +604,38 @@ int nasseg_berhu_masked_bwd(const float* pred, const float* target, const float*
                             int B, int h, int w, int H, int W, float valid_min, float valid_max, float* dpred,
                             void* stream);
 
+/* Full-size berHu: the criterion of nasseg_berhu_masked_fwd taken at the TARGET's size, the bilinear up-sampling of the
+ * prediction fused in (absent from the reference, "parity unpinned").  It replaces, for a caller who asks for it, the
+ * nearest sampling of the target by nasseg_berhu_masked_fwd - and the composition nasseg_bilinear_fwd +
+ * nasseg_berhu_masked_fwd at equal sizes (with nasseg_bilinear_bwd behind it), which writes and re-reads a [B][H][W]
+ * map in each direction: the loss is then taken where validate_depth (nasseg_depth_metrics) scores, on the prediction
+ * resized to the ground truth.
+ * pred [B][h][w] (one channel, fp32 or bf16 storage), target fp32 [B][H][W] at ANY size, larger than, equal to or
+ * smaller than (h, w), per axis.  For target pixel P = (b, Y, X): P is valid iff target[P] is finite and
+ * valid_min < target[P] <= valid_max; ly = lin_coeff(Y, h/H, h, H), lx = lin_coeff(X, w/W, w, W) (bilinear,
+ * align_corners = False, torch's source index in fp32) and
+ *   top = l0x x00 + l1x x01,  bot = l0x x10 + l1x x11,  v(P) = l0y top + l1y bot
+ * with every product and every sum rounded to fp32 on its own - bit for bit the value nasseg_depth_metrics scores
+ * (before its clamp); equal sizes are the identity.  d(P) = |v(P) - target[P]|, c = 0.2 * max d over the valid pixels,
+ * loss = sum B(d) / n_valid, B(d) = d if d <= c else (d*d + c*c) / (2c); out = {loss, c, n_valid}; no valid pixel:
+ * loss 0, gradient 0.  Sums over pixels: per-workgroup partials added in fp64 in a fixed order by one finalize launch.
+ * Backward (c constant): with r(P) = sign(v - t) if d <= c else (v - t) / c on valid pixels,
+ *   dpred[b][y][x] = gscale / n_valid * sum_P r(P) Wy(P, y) Wx(P, x),   Wy(P, y) = l0y [i0(Y) == y] + l1y [i1(Y) == y]
+ * (Wx alike), a gather in fp32 over the target range that can reach (y, x): a group of `group` lanes shares the range of
+ * one prediction pixel in a fixed interleaving and adds its partial sums in a fixed tree.  group = 0: chosen from
+ * (h, w, H, W) alone - the smallest of 1, 4, 16, 64, 256 that leaves a lane at most 16 of the (2H/h) x (2W/w) targets;
+ * 1, 4, 16, 64 or 256: that group (every value is correct at every shape; they differ in speed and in the order of the
+ * sum).  A prediction pixel whose range holds no valid target gets an exact zero; dpred is stored in the prediction's
+ * type, written once.  No float atomics, no host synchronisation, no allocation, a launch geometry that depends on
+ * the shapes alone: capturable and bit-reproducible.
+ * B*H*W < 2^32, B*h*w < 2^31.  ws: nasseg_berhu_up_workspace floats (0: bad shape) - a function of the grid alone,
+ * not of the pixel count. */
+int64_t nasseg_berhu_up_workspace(int B, int h, int w, int H, int W);
+int nasseg_berhu_up_fwd(const float* pred, const float* target, int B, int h, int w, int H, int W, float valid_min,
+                        float valid_max, float* out, float* ws, void* stream);
+int nasseg_berhu_up_bwd(const float* pred, const float* target, const float* stats, const float* gscale, int B, int h,
+                        int w, int H, int W, float valid_min, float valid_max, int group, float* dpred, void* stream);
+
 /* ---- mean-IoU reward: helpers/miou_utils.pyx fast_cm :7-30, compute_iu :32-57,
  * compute_ius_accs :59-90; argmax + up-sampling of engine/inference.py:58-66 ------ */
 int nasseg_fast_cm(const uint8_t* preds, const uint8_t* gt, int64_t P, int n, int64_t* cm,
@@ -905,6 +937,11 @@ int nasseg_bf16_berhu_masked_fwd(const nasseg_bf16_t* pred, const float* target,
 int nasseg_bf16_berhu_masked_bwd(const nasseg_bf16_t* pred, const float* target, const float* stats,
                                  const float* gscale, int B, int h, int w, int H, int W, float valid_min,
                                  float valid_max, nasseg_bf16_t* dpred, void* stream);
+int nasseg_bf16_berhu_up_fwd(const nasseg_bf16_t* pred, const float* target, int B, int h, int w, int H, int W,
+                             float valid_min, float valid_max, float* out, float* ws, void* stream);
+int nasseg_bf16_berhu_up_bwd(const nasseg_bf16_t* pred, const float* target, const float* stats, const float* gscale,
+                             int B, int h, int w, int H, int W, float valid_min, float valid_max, int group,
+                             nasseg_bf16_t* dpred, void* stream);
 int nasseg_bf16_depth_metrics(const nasseg_bf16_t* pred, int64_t ldp, int B, int h, int w, const float* gt, int H,
                               int W, float min_depth, float max_depth, double* acc, double* ws, void* stream);
 int nasseg_bf16_colred(int mode, const nasseg_bf16_t* a, int64_t lda, const nasseg_bf16_t* b, int64_t ldb,

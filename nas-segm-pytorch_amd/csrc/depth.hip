@@ -11,6 +11,8 @@
 //   * no valid pixel: loss 0, gradient 0.  n_valid never leaves the device.
 // Three passes over the prediction (workgroup maxima + counts -> c -> workgroup sums -> one fixed-order sum in
 // double) and one for the gradient; no float atomics, so the same inputs give the same bits.
+// Second half of the file: the criterion at the target's size, the bilinear up-sampling of the prediction fused in
+// (nasseg_berhu_up_fwd / _bwd).
 #include <math.h>
 
 #include "common.h"
@@ -167,6 +169,202 @@ inline bool masked_geom(int B, int h, int w, int H, int W, float valid_min, floa
   return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The same criterion taken at the TARGET's size (definition: include/nasseg.h, "full-size berHu"; INTEGRATION.md,
+// "Depth"): the prediction is up-sampled bilinearly to every target pixel inside the kernels - the value
+// depth_metrics_kernel (depth_eval.hip) scores, bit for bit - and never stored at that size.
+//   forward   the passes above, run over the B*H*W target pixels, one lane per pixel (the target read coalesced):
+//             validity first, so a hole costs one load; a valid pixel re-interpolates its value in each pass from
+//             the four neighbours of the small, cache-resident prediction.  Then berhu_masked_finalize_kernel.
+//   backward  a gather (as ce_up_bwd_kernel and nasseg_bilinear_bwd): a workgroup owns a T x T tile of prediction
+//             pixels, stages tile + one pixel of halo in LDS, and a group of G lanes shares every pixel: the lanes
+//             form a gx x gy grid that walks the pixel's target range (up_dst_range) with strides (gx, gy) - gx
+//             lanes next to each other read gx consecutive targets of a row - and their partial sums are added by a
+//             fixed tree through LDS.  G T T = 256; G in {1, 4, 16, 64, 256} is chosen from the shapes alone
+//             (up_bwd_group): about 16 target pixels per lane, so that the x16 / x32 auxiliary heads, whose maps
+//             have a few hundred pixels with footprints of thousands, still fill the device.  dpred is written once.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kUpThreads = 256;
+constexpr int kUpMaxTile = 16;               // T at G = 1
+constexpr int kUpPatchW = kUpMaxTile + 2;    // LDS patch: tile + halo, row stride
+
+struct UpGeom {
+  int h, w, H, W;
+  float sh, sw;  // h / H, w / W: lin_coeff's scale
+  float vmin, vmax;
+};
+
+// prediction up-sampled to target pixel p of the dense [B][H][W] map (p < 2^32: up_geom)
+__device__ __forceinline__ float up_value(const act_t* __restrict__ pred, int64_t p, const UpGeom& g) {
+  const uint32_t pu = (uint32_t)p;
+  const uint32_t q = pu / (uint32_t)g.W;
+  const int X = (int)(pu - q * (uint32_t)g.W);
+  const uint32_t b = q / (uint32_t)g.H;
+  const int Y = (int)(q - b * (uint32_t)g.H);
+  const Lin ly = lin_coeff(Y, g.sh, g.h, g.H);
+  const Lin lx = lin_coeff(X, g.sw, g.w, g.W);
+  const act_t* pb = pred + (int64_t)b * g.h * g.w;
+  const act_t* r0 = pb + (int64_t)ly.i0 * g.w;
+  const act_t* r1 = pb + (int64_t)ly.i1 * g.w;
+  return up_interp(lda1(r0 + lx.i0), lda1(r0 + lx.i1), lda1(r1 + lx.i0), lda1(r1 + lx.i1), ly, lx);
+}
+
+__global__ __launch_bounds__(256) void berhu_up_max_kernel(const act_t* __restrict__ pred,
+                                                           const float* __restrict__ target, int64_t n, UpGeom g,
+                                                           float* __restrict__ maxpart, float* __restrict__ cntpart) {
+  __shared__ float red_m[256];
+  __shared__ float red_n[256];
+  float m = 0.f, cnt = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float t = target[i];
+    if (!depth_valid(t, g.vmin, g.vmax)) continue;
+    m = fmaxf(m, fabsf(up_value(pred, i, g) - t));
+    cnt += 1.f;  // (at most n / gridDim.x + 256 < 2^24 per workgroup: exact in fp32)
+  }
+  red_m[threadIdx.x] = m;
+  red_n[threadIdx.x] = cnt;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      red_m[threadIdx.x] = fmaxf(red_m[threadIdx.x], red_m[threadIdx.x + s]);
+      red_n[threadIdx.x] += red_n[threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    maxpart[blockIdx.x] = red_m[0];
+    cntpart[blockIdx.x] = red_n[0];
+  }
+}
+
+__global__ __launch_bounds__(256) void berhu_up_sum_kernel(const act_t* __restrict__ pred,
+                                                           const float* __restrict__ target, int64_t n, UpGeom g,
+                                                           const float* __restrict__ maxpart, int nblk,
+                                                           float* __restrict__ sumpart, float* __restrict__ out) {
+  __shared__ float red[256];
+  float m = 0.f;
+  for (int b = threadIdx.x; b < nblk; b += 256) m = fmaxf(m, maxpart[b]);  // (a maximum: any order, same bits)
+  red[threadIdx.x] = m;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
+    __syncthreads();
+  }
+  const float c = 0.2f * red[0];
+  __syncthreads();
+  if (blockIdx.x == 0 && threadIdx.x == 0) out[1] = c;
+  float acc = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float t = target[i];
+    if (!depth_valid(t, g.vmin, g.vmax)) continue;
+    const float d = fabsf(up_value(pred, i, g) - t);
+    acc += (d <= c) ? d : (d * d + c * c) / (2.f * c);
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) sumpart[blockIdx.x] = red[0];
+}
+
+// grid: (tile x, tile y, image), flattened, x fastest.  Thread tid: pixel tid / G of the T x T tile (row-major), lane
+// tid % G of its group = (lane / gx, lane % gx) of the gx x (G / gx) grid over the pixel's target range.
+// dpred = gscale / n_valid * sum r Wy Wx over the valid targets of the range, r = sign(v - t) if |v - t| <= c else
+// (v - t) / c; a pixel without a valid target in its range gets an exact zero.
+__global__ __launch_bounds__(256) void berhu_up_bwd_kernel(const act_t* __restrict__ pred,
+                                                           const float* __restrict__ target,
+                                                           const float* __restrict__ stats,
+                                                           const float* __restrict__ gscale, UpGeom g, int T, int G,
+                                                           int gx, int tiles_y, int tiles_x,
+                                                           act_t* __restrict__ dpred) {
+  __shared__ float patch[kUpPatchW * kUpPatchW];
+  __shared__ float part[kUpThreads];
+  const int tid = threadIdx.x;
+  int wi = blockIdx.x;
+  const int tx = wi % tiles_x;
+  wi /= tiles_x;
+  const int ty = wi % tiles_y;
+  const int b = wi / tiles_y;
+  const int y0 = ty * T, x0 = tx * T;
+  const int ny = g.h - y0 < T ? g.h - y0 : T;  // the tile's own pixels
+  const int nx = g.w - x0 < T ? g.w - x0 : T;
+  const int oy = y0 > 0 ? y0 - 1 : 0, ox = x0 > 0 ? x0 - 1 : 0;  // origin of the patch: one pixel of halo, inside the map
+  const int py = (y0 + ny < g.h ? y0 + ny : g.h - 1) - oy + 1;     // its rows (<= T + 2)
+  const int px = (x0 + nx < g.w ? x0 + nx : g.w - 1) - ox + 1;     // its pixels per row (<= T + 2)
+  for (int k = tid; k < py * px; k += kUpThreads) {
+    const int r = k / px, q = k - r * px;
+    patch[r * kUpPatchW + q] = lda1(pred + ((int64_t)b * g.h + oy + r) * g.w + ox + q);
+  }
+  __syncthreads();
+  const float c = stats[1];
+  const float nv = stats[2];
+  const float gn = nv > 0.f ? (gscale ? gscale[0] : 1.f) / nv : 0.f;
+  const int pix = tid / G, lane = tid - pix * G;
+  const int iy = pix / T, jx = pix - iy * T;
+  const bool own = iy < ny && jx < nx;
+  const int i = y0 + iy, j = x0 + jx;
+  float acc = 0.f;
+  if (own) {
+    const int gy = G / gx;
+    const int ly0 = lane / gx, lx0 = lane - ly0 * gx;
+    int ylo, yhi, xlo, xhi;
+    up_dst_range(i, g.sh, g.h, g.H, ylo, yhi);
+    up_dst_range(j, g.sw, g.w, g.W, xlo, xhi);
+    for (int Y = ylo + ly0; Y <= yhi; Y += gy) {
+      const Lin ly = lin_coeff(Y, g.sh, g.h, g.H);
+      const float wy = up_weight(ly, i);
+      if (wy == 0.f) continue;  // (so ly.i0, ly.i1 lie in [i - 1, i + 1]: inside the patch)
+      const float* r0 = patch + (ly.i0 - oy) * kUpPatchW;
+      const float* r1 = patch + (ly.i1 - oy) * kUpPatchW;
+      const float* trow = target + ((int64_t)b * g.H + Y) * g.W;
+      for (int X = xlo + lx0; X <= xhi; X += gx) {
+        const float t = trow[X];
+        if (!depth_valid(t, g.vmin, g.vmax)) continue;
+        const Lin lx = lin_coeff(X, g.sw, g.w, g.W);
+        const float wx = up_weight(lx, j);
+        if (wx == 0.f) continue;  // (so lx.i0, lx.i1 lie in [j - 1, j + 1])
+        const int a0 = lx.i0 - ox, a1 = lx.i1 - ox;
+        const float d = up_interp(r0[a0], r0[a1], r1[a0], r1[a1], ly, lx) - t;
+        const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+        acc = fmaf(wy * wx, (fabsf(d) <= c) ? sgn : d / c, acc);
+      }
+    }
+  }
+  if (G > 1) {  // (G is the launch's: every thread of the workgroup takes the same branch)
+    part[tid] = acc;
+    __syncthreads();
+    for (int s = G >> 1; s > 0; s >>= 1) {
+      if (lane < s) part[tid] += part[tid + s];
+      __syncthreads();
+    }
+    acc = part[tid];
+  }
+  if (own && lane == 0) sta1(dpred + ((int64_t)b * g.h + i) * g.w + j, gn * acc);
+}
+
+inline bool up_geom(int B, int h, int w, int H, int W, float valid_min, float valid_max, UpGeom* g) {
+  if (!(B > 0 && h > 0 && w > 0 && H > 0 && W > 0)) return false;
+  if ((int64_t)B * H * W >= ((int64_t)1 << 32)) return false;  // (up_value's 32-bit divisions; fp32 counts per workgroup)
+  if ((int64_t)B * h * w >= ((int64_t)1 << 31)) return false;  // (the backward's grid: at most one workgroup per pixel)
+  g->h = h, g->w = w, g->H = H, g->W = W;
+  g->sh = (float)h / (float)H, g->sw = (float)w / (float)W;
+  g->vmin = valid_min, g->vmax = valid_max;
+  return true;
+}
+
+// lanes per prediction pixel in the backward: the smallest of 1, 4, 16, 64, 256 that leaves a lane at most 16 of the
+// (2 H/h) x (2 W/w) target pixels a prediction pixel's weights reach (one per axis at equal size, two when
+// down-sampling).  From the shapes alone.
+inline int up_bwd_group(int h, int w, int H, int W) {
+  const int64_t fy = H > h ? cdiv64(2 * (int64_t)H, h) : (H == h ? 1 : 2);
+  const int64_t fx = W > w ? cdiv64(2 * (int64_t)W, w) : (W == w ? 1 : 2);
+  int G = 1;
+  while (G < kUpThreads && fy * fx > 16 * (int64_t)G) G *= 4;
+  return G;
+}
+
 }  // namespace
 
 extern "C" {
@@ -210,6 +408,64 @@ int NASSEG_FN(berhu_masked_bwd)(const act_t* pred, const float* target, const fl
   hipLaunchKernelGGL(berhu_masked_bwd_kernel, dim3(red_grid(n) * 2), dim3(256), 0, (hipStream_t)stream, pred,
                      target, stats, gscale, n, g, dpred);
   NASSEG_LAUNCH_CHECK("berhu_masked_bwd");
+  return NASSEG_OK;
+}
+
+#if NASSEG_FP32_ONLY
+// floats: [1024] maxima | [1024] counts | [1024] sums, whatever the sizes - a function of the grid alone
+int64_t nasseg_berhu_up_workspace(int B, int h, int w, int H, int W) {
+  UpGeom g;
+  return up_geom(B, h, w, H, W, 0.f, 0.f, &g) ? 3 * kMaxGrid : 0;
+}
+#endif
+
+#define UP_GEOM_CHECK(who) \
+  NASSEG_REQUIRE(up_geom(B, h, w, H, W, valid_min, valid_max, &g), who ": bad shape (B*H*W < 2^32, B*h*w < 2^31)")
+
+// pred: dense [B][h][w] (one channel), target: fp32 [B][H][W].  out[0] = loss, out[1] = c, out[2] = n_valid.
+// ws: nasseg_berhu_up_workspace floats.
+int NASSEG_FN(berhu_up_fwd)(const act_t* pred, const float* target, int B, int h, int w, int H, int W,
+                            float valid_min, float valid_max, float* out, float* ws, void* stream) {
+  UpGeom g;
+  UP_GEOM_CHECK("berhu_up_fwd");
+  NASSEG_REQUIRE(pred && target && out && ws, "berhu_up_fwd: null pointer");
+  NASSEG_REQUIRE(valid_min == valid_min && valid_max == valid_max, "berhu_up_fwd: NaN bound");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = (int64_t)B * H * W;
+  const int grid = red_grid(n);
+  float* maxpart = ws;
+  float* cntpart = ws + kMaxGrid;
+  float* sumpart = ws + 2 * kMaxGrid;
+  hipLaunchKernelGGL(berhu_up_max_kernel, dim3(grid), dim3(256), 0, s, pred, target, n, g, maxpart, cntpart);
+  NASSEG_LAUNCH_CHECK("berhu_up_max");
+  hipLaunchKernelGGL(berhu_up_sum_kernel, dim3(grid), dim3(256), 0, s, pred, target, n, g, maxpart, grid, sumpart,
+                     out);
+  NASSEG_LAUNCH_CHECK("berhu_up_sum");
+  hipLaunchKernelGGL(berhu_masked_finalize_kernel, dim3(1), dim3(256), 0, s, sumpart, cntpart, grid, out);
+  NASSEG_LAUNCH_CHECK("berhu_up_finalize");
+  return NASSEG_OK;
+}
+
+// stats = out of nasseg_berhu_up_fwd; gscale = device scalar upstream gradient (null = 1); group: lanes per
+// prediction pixel - 0: chosen from the shapes (up_bwd_group), else 1, 4, 16, 64 or 256 (measurements and tests)
+int NASSEG_FN(berhu_up_bwd)(const act_t* pred, const float* target, const float* stats, const float* gscale, int B,
+                            int h, int w, int H, int W, float valid_min, float valid_max, int group, act_t* dpred,
+                            void* stream) {
+  UpGeom g;
+  UP_GEOM_CHECK("berhu_up_bwd");
+  NASSEG_REQUIRE(pred && target && stats && dpred, "berhu_up_bwd: null pointer");
+  NASSEG_REQUIRE(valid_min == valid_min && valid_max == valid_max, "berhu_up_bwd: NaN bound");
+  NASSEG_REQUIRE(group == 0 || group == 1 || group == 4 || group == 16 || group == 64 || group == 256,
+                 "berhu_up_bwd: group must be 0, 1, 4, 16, 64 or 256 (got %d)", group);
+  const int G = group ? group : up_bwd_group(h, w, H, W);
+  int T = kUpMaxTile;  // G T T = 256
+  for (int k = G; k > 1; k /= 4) T /= 2;
+  const int gx = G >= 256 ? 32 : (G >= 16 ? 16 : G);
+  const int tiles_y = cdiv(h, T), tiles_x = cdiv(w, T);
+  const int64_t nwg = (int64_t)B * tiles_y * tiles_x;  // (<= B*h*w < 2^31: up_geom)
+  hipLaunchKernelGGL(berhu_up_bwd_kernel, dim3((unsigned)nwg), dim3(kUpThreads), 0, (hipStream_t)stream, pred, target,
+                     stats, gscale, g, T, G, gx, tiles_y, tiles_x, dpred);
+  NASSEG_LAUNCH_CHECK("berhu_up_bwd");
   return NASSEG_OK;
 }
 

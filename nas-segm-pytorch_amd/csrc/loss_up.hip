@@ -25,14 +25,6 @@ constexpr int kUpTile = 8;        // backward: logits pixels per tile side
 constexpr int kUpPatch = kUpTile + 2;
 constexpr int kUpChunk = 64;      // backward: channels per workgroup
 
-// v = ly.l0 * (lx.l0 * x00 + lx.l1 * x01) + ly.l1 * (lx.l0 * x10 + lx.l1 * x11), every product and sum rounded on
-// its own (csrc/miou.hip: argmax_cm_kernel)
-__device__ __forceinline__ float up_interp(float x00, float x01, float x10, float x11, const Lin& ly, const Lin& lx) {
-  const float top = __fadd_rn(__fmul_rn(lx.l0, x00), __fmul_rn(lx.l1, x01));
-  const float bot = __fadd_rn(__fmul_rn(lx.l0, x10), __fmul_rn(lx.l1, x11));
-  return __fadd_rn(__fmul_rn(ly.l0, top), __fmul_rn(ly.l1, bot));
-}
-
 template <typename TL>
 __global__ __launch_bounds__(256) void ce_up_fwd_kernel(const act_t* __restrict__ logits, const TL* __restrict__ target,
                                                         int B, int h, int w, int C, int H, int W, float sh, float sw,
@@ -69,27 +61,7 @@ __global__ __launch_bounds__(256) void ce_up_fwd_kernel(const act_t* __restrict_
   }
 }
 
-// conservative range [lo, hi] of label coordinates whose footprint can touch logits index i (csrc/resize.hip's
-// dst_range: a coordinate inside it that does not touch i has weight exactly 0)
-__device__ __forceinline__ void up_dst_range(int i, float scale, int in_size, int out_size, int& lo, int& hi) {
-  if (in_size == out_size) {
-    lo = hi = i;
-    return;
-  }
-  // src(o) in [i-1, i+1)  <=>  o in [(i-0.5)/scale - 0.5, (i+1.5)/scale - 0.5)
-  const float inv = 1.0f / scale;
-  lo = (int)floorf(((float)i - 0.5f) * inv - 0.5f) - 1;
-  hi = (int)ceilf(((float)i + 1.5f) * inv - 0.5f) + 1;
-  if (lo < 0) lo = 0;
-  if (hi > out_size - 1) hi = out_size - 1;
-}
-__device__ __forceinline__ float up_weight(const Lin& l, int i) {
-  float wt = 0.f;
-  if (l.i0 == i) wt += l.l0;
-  if (l.i1 == i) wt += l.l1;
-  return wt;
-}
-
+// (up_interp, up_dst_range, up_weight: csrc/resize_index.h)
 // grid: (channel chunk, tile x, tile y, image), flattened, chunk fastest.  VEC: the patch is staged with 16-byte
 // (bf16: 8-byte) loads - one chunk (C <= kUpChunk) and 16-byte aligned logits; else element by element.
 // LDS: patch[kUpPatch][kUpPatch][cn | 1] floats.

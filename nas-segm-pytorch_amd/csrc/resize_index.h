@@ -31,6 +31,36 @@ __device__ __forceinline__ Lin lin_coeff(int dst, float scale, int in_size, int 
   return r;
 }
 
+// The fused up-sampling criteria (loss_up.hip, depth.hip): the value, and the two halves of its transpose.
+// v = ly.l0 * (lx.l0 * x00 + lx.l1 * x01) + ly.l1 * (lx.l0 * x10 + lx.l1 * x11), every product and sum rounded on
+// its own (csrc/miou.hip: argmax_cm_kernel; csrc/depth_eval.hip: depth_metrics_kernel)
+__device__ __forceinline__ float up_interp(float x00, float x01, float x10, float x11, const Lin& ly, const Lin& lx) {
+  const float top = __fadd_rn(__fmul_rn(lx.l0, x00), __fmul_rn(lx.l1, x01));
+  const float bot = __fadd_rn(__fmul_rn(lx.l0, x10), __fmul_rn(lx.l1, x11));
+  return __fadd_rn(__fmul_rn(ly.l0, top), __fmul_rn(ly.l1, bot));
+}
+// conservative range [lo, hi] of destination coordinates whose footprint can touch source index i (csrc/resize.hip's
+// dst_range: a coordinate inside it that does not touch i has weight exactly 0); scale = in/out
+__device__ __forceinline__ void up_dst_range(int i, float scale, int in_size, int out_size, int& lo, int& hi) {
+  if (in_size == out_size) {
+    lo = hi = i;
+    return;
+  }
+  // src(o) in [i-1, i+1)  <=>  o in [(i-0.5)/scale - 0.5, (i+1.5)/scale - 0.5)
+  const float inv = 1.0f / scale;
+  lo = (int)floorf(((float)i - 0.5f) * inv - 0.5f) - 1;
+  hi = (int)ceilf(((float)i + 1.5f) * inv - 0.5f) + 1;
+  if (lo < 0) lo = 0;
+  if (hi > out_size - 1) hi = out_size - 1;
+}
+// weight of source index i in the destination coordinate l belongs to
+__device__ __forceinline__ float up_weight(const Lin& l, int i) {
+  float wt = 0.f;
+  if (l.i0 == i) wt += l.l0;
+  if (l.i1 == i) wt += l.l1;
+  return wt;
+}
+
 // torch 'nearest': src = min(floor(dst * scale), in-1), scale = in/out (fp32)
 __device__ __forceinline__ int nearest_src(int dst, float scale, int in_size) {
   int i = (int)floorf((float)dst * scale);

@@ -47,17 +47,24 @@ def build_candidate(config, ctrl_version="wacv", num_classes=19, agg_size=48, au
 def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", num_classes=19,
                        agg_size=48, aux_cell=True, repeats=1, epochs=1, aux_weight=0.15,
                        omit_classes=(0,), device="cuda", stats=None, graphed=False, task="segm",
-                       min_depth=1e-3, max_depth=10.0, segm_crit=None):
+                       min_depth=1e-3, max_depth=10.0, segm_crit=None, depth_crit=None):
     """Train the candidate on ``train_batches`` (lists of {"image", "mask"}) for ``epochs``
     passes and return its validation reward; failures score 0 like in the reference.
     task="depth": the masks are fp32 depth maps at the image's size (holes: 0 / NaN / inf), the decoder has one
-    output channel, the loss is BerHuLoss(valid_min=0) and the reward comes from ``validate_depth``
-    (``min_depth`` / ``max_depth``: its valid range).
+    output channel, the loss is ``depth_crit`` - an nn.BerHuLoss, e.g. ``BerHuLoss(0.0, full_size=True)`` for the
+    loss at the target's size; None: BerHuLoss(valid_min=0) - and the reward comes from ``validate_depth``
+    (``min_depth`` / ``max_depth``: its valid range).  Any other ``depth_crit``, or one given with task="segm", is a
+    ValueError.
     ``segm_crit`` (task="segm"): the training criterion, e.g. an nn.SegmCrossEntropy with class weights,
     hard-example mining or a region-overlap (soft Jaccard / Dice) term; None: LogSoftmax + NLL with ignore index 255."""
+    if depth_crit is not None and not isinstance(depth_crit, BerHuLoss):
+        raise ValueError("evaluate_candidate: depth_crit must be an nn.BerHuLoss (got {!r})".format(depth_crit))
     if _task(task) == "depth":
         return _evaluate_depth_candidate(config, train_batches, val_batches, ctrl_version, agg_size, aux_cell,
-                                         repeats, epochs, aux_weight, device, stats, graphed, min_depth, max_depth)
+                                         repeats, epochs, aux_weight, device, stats, graphed, min_depth, max_depth,
+                                         depth_crit)
+    if depth_crit is not None:
+        raise ValueError("evaluate_candidate: depth_crit belongs to task=\"depth\" (got task={!r})".format(task))
     try:
         segmenter = build_candidate(config, ctrl_version, num_classes, agg_size, aux_cell, repeats,
                                     device)
@@ -98,9 +105,9 @@ def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", 
 
 
 def _evaluate_depth_candidate(config, train_batches, val_batches, ctrl_version, agg_size, aux_cell, repeats, epochs,
-                              aux_weight, device, stats, graphed, min_depth, max_depth):
+                              aux_weight, device, stats, graphed, min_depth, max_depth, depth_crit=None):
     """``evaluate_candidate`` for task="depth": the same optimisers, clip norms and eager / replayed paths, with the
-    depth step and the depth reward"""
+    depth step (``depth_crit``; None: BerHuLoss(valid_min=0)) and the depth reward"""
     try:
         segmenter = build_candidate(config, ctrl_version, 1, agg_size, aux_cell, repeats, device, task="depth")
     except RuntimeError:
@@ -109,7 +116,7 @@ def _evaluate_depth_candidate(config, train_batches, val_batches, ctrl_version, 
     optim_enc = torch.optim.SGD(model.encoder.parameters(), lr=1e-3, momentum=0.9, weight_decay=1e-5)
     optim_dec = torch.optim.Adam(model.decoder.parameters(), lr=3e-3, weight_decay=1e-5)
     aux = aux_weight if ctrl_version == "cvpr" else -1
-    crit = BerHuLoss(valid_min=0.0)
+    crit = BerHuLoss(valid_min=0.0) if depth_crit is None else depth_crit
 
     def on_device(sample):
         return (sample["image"].to(device=device, dtype=torch.float32).contiguous(memory_format=torch.channels_last),

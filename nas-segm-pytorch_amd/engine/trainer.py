@@ -76,8 +76,9 @@ def _labels(mask, device):
 
 
 def _depth_crit(segm_crit):
-    """the criterion itself when it selects the depth step (an nn.BerHuLoss: fp32 full-size targets, masked berHu),
-    else None: softmax/NLL on class labels, as ever"""
+    """the criterion itself when it selects the depth step (an nn.BerHuLoss: fp32 full-size targets, masked berHu
+    at the prediction's size or, with ``full_size=True``, at the target's), else None: softmax/NLL on class labels,
+    as ever"""
     return segm_crit if isinstance(segm_crit, BerHuLoss) else None
 
 
@@ -313,7 +314,7 @@ def _segmenter_stepper(segmenter, image, target, optim_enc, optim_dec, ignore, e
             _bn_modes(model), _trainable_signature(list(model.parameters()), (optim_enc, optim_dec)))
     extra = {}
     if depth_crit is not None:  # (the loss kind, and what the recorded launches carry by value)
-        base = base + (("berhu", id(depth_crit), depth_crit.valid_min, depth_crit.valid_max),)
+        base = base + ((id(depth_crit),) + depth_crit.config(),)
         extra["depth_crit"] = depth_crit
     if segm_crit is not None:
         base = base + (segm_crit.config(),)

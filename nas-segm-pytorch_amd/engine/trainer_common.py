@@ -77,7 +77,8 @@ def task1_loss(segmenter, image, target, ignore_index, aux_weight, segm_crit=Non
 def depth_loss(output, aux_outs, target, crit, aux_weight):
     """``crit`` (nn.BerHuLoss: the masked berHu) of the main head + aux_weight * that of every auxiliary head when
     aux_weight > 0.  Every head is compared with the SAME full-size target: the kernel samples it at the head's own
-    size, so nothing is resized (src/engine/trainer.py:245-250 resizes each head to the target instead)."""
+    size - or, for ``BerHuLoss(full_size=True)``, up-samples the head to it - so nothing is resized here
+    (src/engine/trainer.py:245-250 resizes each head to the target instead)."""
     loss = crit(output, target)
     if aux_weight > 0:
         for aux_out in aux_outs:

@@ -3028,6 +3028,64 @@ def berhu_loss_masked(pred, target, valid_min=0.0, valid_max=float("inf")):
     return _BerHuMasked.apply(pred, target, valid_min, valid_max)
 
 
+class _BerHuUpsampled(torch.autograd.Function):
+    """nasseg_berhu_up_fwd / _bwd.  Outputs: the loss (a scalar of its own), and - not differentiable - c and n_valid
+    (0-dim, fp32).  ``group``: the backward's lanes per prediction pixel (0: from the shapes)"""
+
+    @staticmethod
+    def forward(ctx, pred, target, valid_min, valid_max, group):
+        require_device(pred, target)
+        if pred.dtype not in (torch.float32, torch.bfloat16) or pred.dim() != 4 or pred.shape[1] != 1:
+            raise NassegError("berhu_loss_upsampled: the prediction must be fp32 or bf16 of shape (B, 1, h, w) "
+                              "(got {} {})".format(pred.dtype, tuple(pred.shape)))
+        if target.dtype != torch.float32 or target.dim() != 3 or target.shape[0] != pred.shape[0]:
+            raise NassegError("berhu_loss_upsampled: the target must be fp32 of shape (B, H, W) (got {} {})".format(
+                target.dtype, tuple(target.shape)))
+        p, t = pred.contiguous(), target.contiguous()  # (one channel: NCHW and NHWC are the same memory)
+        B, _, h, w = p.shape
+        H, W = int(t.shape[1]), int(t.shape[2])
+        n_ws = lib.query("nasseg_berhu_up_workspace", B, h, w, H, W)
+        if n_ws <= 0:
+            raise NassegError("berhu_loss_upsampled: prediction {} against target {} is empty or exceeds "
+                              "B*H*W < 2^32, B*h*w < 2^31".format(tuple(pred.shape), tuple(target.shape)))
+        cfg = (B, h, w, H, W, float(valid_min), float(valid_max))
+        out = _vec(p, 3)
+        ws = _ws(p, n_ws)
+        lib.call(_k("nasseg_berhu_up_fwd", p), ptr(p), ptr(t), *cfg, ptr(out), ptr(ws), current_stream())
+        ctx.save_for_backward(p, t, out)
+        ctx.cfg = cfg + (int(group),)
+        # (the loss under a tensor of its own, as _BerHuMasked.forward returns it: it may be updated in place;
+        #  backward reads out[1], out[2] only)
+        c, n_valid = _own_scalar(out, 1), _own_scalar(out, 2)
+        ctx.mark_non_differentiable(c, n_valid)
+        return _own_scalar(out, 0), c, n_valid
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        p, t, out = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous().view(1)
+        d = torch.empty_like(p)
+        lib.call(_k("nasseg_berhu_up_bwd", p), ptr(p), ptr(t), ptr(out), ptr(g), *ctx.cfg, ptr(d), current_stream())
+        return d, None, None, None, None
+
+
+def berhu_loss_upsampled(pred, target, valid_min=0.0, valid_max=float("inf"), return_parts=False):
+    """``berhu_loss_masked`` taken at the TARGET's size: the reverse-Huber loss of a depth head whose prediction is
+    up-sampled bilinearly (align_corners=False) to the (B, H, W) target inside the kernels ("Depth").
+
+    pred (B, 1, h, w) fp32 or bf16, target (B, H, W) fp32 at ANY size, larger than, equal to or smaller than the
+    prediction, per axis.  A TARGET pixel counts iff it is finite and ``valid_min < t <= valid_max``; v = the
+    up-sampled prediction there - the value ``depth_metrics`` scores, bit for bit; d = |v - t|, c = 0.2 * max d (a
+    constant in backward), loss = mean over the valid target pixels of (d if d <= c else (d^2 + c^2) / (2c)); no
+    valid pixel: loss 0, gradient 0.  Nothing of the target's size is allocated in either direction: the gradient is
+    gathered straight into the prediction's shape (exact zeros where no valid target pixel reaches a prediction
+    pixel), without atomics - the same inputs give the same bits.
+    Returns a 0-dim tensor that may be updated in place; ``return_parts``: (loss, c, n_valid), all 0-dim fp32.
+    No host synchronisation: capturable."""
+    out = _BerHuUpsampled.apply(pred, target, valid_min, valid_max, 0)
+    return out if return_parts else out[0]
+
+
 def depth_metrics(pred, gt, min_depth=1e-3, max_depth=10.0, acc=None):
     """Fused bilinear up-sampling -> validity mask -> clamp -> sums of the depth scores: the depth counterpart of
     ``argmax_confusion``.

@@ -10,18 +10,32 @@ class BerHuLoss(nn.Module):
     """Reverse-Huber criterion of a depth head: ``F.berhu_loss_masked`` (absent from the reference; Laina et al.
     2016, eq. 2).  forward(pred (B, 1, h, w), target (B, H, W) fp32 at any size, holes where the target is not
     finite or outside ``(valid_min, valid_max]``) -> 0-dim loss.  Handed to ``engine.trainer.train_segmenter`` as
-    ``segm_crit`` it selects the depth step."""
+    ``segm_crit`` it selects the depth step.
+    ``full_size=True``: ``F.berhu_loss_upsampled`` instead - the prediction is up-sampled bilinearly to the target
+    inside the kernels and the loss is taken over the TARGET's valid pixels, every one of them: the resolution
+    ``validate_depth`` scores at (without it, each prediction pixel sees the one target pixel nearest sampling
+    picks).  The training steps hand every head the same full-size target either way."""
 
-    def __init__(self, valid_min=0.0, valid_max=float("inf")):
+    def __init__(self, valid_min=0.0, valid_max=float("inf"), full_size=False):
         super(BerHuLoss, self).__init__()
         self.valid_min = float(valid_min)
         self.valid_max = float(valid_max)
+        self.full_size = bool(full_size)
+
+    def config(self):
+        """what a recorded step carries by value (the stepper cache's key, engine/trainer.py): the loss kind and
+        the two bounds, which are kernel arguments"""
+        return ("berhu_up" if self.full_size else "berhu", self.valid_min, self.valid_max)
 
     def forward(self, pred, target):
-        return F.berhu_loss_masked(pred, target, self.valid_min, self.valid_max)
+        loss = F.berhu_loss_upsampled if self.full_size else F.berhu_loss_masked
+        return loss(pred, target, self.valid_min, self.valid_max)
 
     def extra_repr(self):
-        return "valid_min={}, valid_max={}".format(self.valid_min, self.valid_max)
+        s = "valid_min={}, valid_max={}".format(self.valid_min, self.valid_max)
+        if self.full_size:
+            s += ", full_size=True"
+        return s
 
 
 class SegmCrossEntropy(nn.Module):
