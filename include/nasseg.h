@@ -636,6 +636,29 @@ int nasseg_berhu_up_fwd(const float* pred, const float* target, int B, int h, in
 int nasseg_berhu_up_bwd(const float* pred, const float* target, const float* stats, const float* gscale, int B, int h,
                         int w, int H, int W, float valid_min, float valid_max, int group, float* dpred, void* stream);
 
+/* Row-indexed twins of the four entry points above, for targets that live in a cache (the task0 depth cache,
+ * engine/trainer.py: populate_task0(task="depth")): target is the WHOLE cache, fp32 [n_rows][H][W], and rows a DEVICE
+ * array of B cache rows - the index nasseg_gather_rows takes; image b of the prediction is compared with
+ * target[clamp(rows[b], 0, n_rows - 1)] (the clamp is a memory-safety net only: the host checks the range).  Repeated
+ * and unordered rows are legal.  Everything else - validity, c, out = {loss, c, n_valid}, the backward with c constant,
+ * group, the workspaces nasseg_berhu_masked_workspace() / nasseg_berhu_up_workspace(B, h, w, H, W) - is as above, and
+ * so is every bit: the result is that of the un-indexed entry point on a gathered copy target[rows] (the same kernels,
+ * launch geometry, order of sums and finalize; only the address of an image's target differs), which is never
+ * written.  B*H*W < 2^32 and B*h*w < 2^31 bound the BATCH; the cache may be larger (rows[b]*H*W is 64-bit).  Neither
+ * the cache nor the table is written. */
+int nasseg_berhu_masked_rows_fwd(const float* pred, const float* target, const int64_t* rows, int64_t n_rows, int B,
+                                 int h, int w, int H, int W, float valid_min, float valid_max, float* out, float* ws,
+                                 void* stream);
+int nasseg_berhu_masked_rows_bwd(const float* pred, const float* target, const int64_t* rows, int64_t n_rows,
+                                 const float* stats, const float* gscale, int B, int h, int w, int H, int W,
+                                 float valid_min, float valid_max, float* dpred, void* stream);
+int nasseg_berhu_up_rows_fwd(const float* pred, const float* target, const int64_t* rows, int64_t n_rows, int B, int h,
+                             int w, int H, int W, float valid_min, float valid_max, float* out, float* ws,
+                             void* stream);
+int nasseg_berhu_up_rows_bwd(const float* pred, const float* target, const int64_t* rows, int64_t n_rows,
+                             const float* stats, const float* gscale, int B, int h, int w, int H, int W,
+                             float valid_min, float valid_max, int group, float* dpred, void* stream);
+
 /* ---- mean-IoU reward: helpers/miou_utils.pyx fast_cm :7-30, compute_iu :32-57,
  * compute_ius_accs :59-90; argmax + up-sampling of engine/inference.py:58-66 ------ */
 int nasseg_fast_cm(const uint8_t* preds, const uint8_t* gt, int64_t P, int n, int64_t* cm,
@@ -942,6 +965,19 @@ int nasseg_bf16_berhu_up_fwd(const nasseg_bf16_t* pred, const float* target, int
 int nasseg_bf16_berhu_up_bwd(const nasseg_bf16_t* pred, const float* target, const float* stats, const float* gscale,
                              int B, int h, int w, int H, int W, float valid_min, float valid_max, int group,
                              nasseg_bf16_t* dpred, void* stream);
+int nasseg_bf16_berhu_masked_rows_fwd(const nasseg_bf16_t* pred, const float* target, const int64_t* rows,
+                                      int64_t n_rows, int B, int h, int w, int H, int W, float valid_min,
+                                      float valid_max, float* out, float* ws, void* stream);
+int nasseg_bf16_berhu_masked_rows_bwd(const nasseg_bf16_t* pred, const float* target, const int64_t* rows,
+                                      int64_t n_rows, const float* stats, const float* gscale, int B, int h, int w,
+                                      int H, int W, float valid_min, float valid_max, nasseg_bf16_t* dpred,
+                                      void* stream);
+int nasseg_bf16_berhu_up_rows_fwd(const nasseg_bf16_t* pred, const float* target, const int64_t* rows, int64_t n_rows,
+                                  int B, int h, int w, int H, int W, float valid_min, float valid_max, float* out,
+                                  float* ws, void* stream);
+int nasseg_bf16_berhu_up_rows_bwd(const nasseg_bf16_t* pred, const float* target, const int64_t* rows, int64_t n_rows,
+                                  const float* stats, const float* gscale, int B, int h, int w, int H, int W,
+                                  float valid_min, float valid_max, int group, nasseg_bf16_t* dpred, void* stream);
 int nasseg_bf16_depth_metrics(const nasseg_bf16_t* pred, int64_t ldp, int B, int h, int w, const float* gt, int H,
                               int W, float min_depth, float max_depth, double* acc, double* ws, void* stream);
 int nasseg_bf16_colred(int mode, const nasseg_bf16_t* a, int64_t lda, const nasseg_bf16_t* b, int64_t ldb,

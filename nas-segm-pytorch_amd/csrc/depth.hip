@@ -13,6 +13,10 @@
 // double) and one for the gradient; no float atomics, so the same inputs give the same bits.
 // Second half of the file: the criterion at the target's size, the bilinear up-sampling of the prediction fused in
 // (nasseg_berhu_up_fwd / _bwd).
+// Every pass exists once, as a template on whether a ROW TABLE is present (nasseg_berhu_*_rows_*): image b of the
+// prediction is then compared with image rows[b] of a larger target - the task0 depth cache - instead of image b;
+// only the address of an image's target differs, so both forms give the same bits and the batch's targets are
+// never gathered into a copy.
 #include <math.h>
 
 #include "common.h"
@@ -27,31 +31,56 @@ struct MaskedGeom {
   float sh, sw, vmin, vmax;
 };
 
+// kRows false: image b of the target is image b, the table is empty - the kernels the un-indexed entry points launch
+// carry nothing for it.  kRows true: the target is a cache [n_rows][H][W] and image b is its row rows[b], clamped to
+// the cache as nasseg_gather_rows clamps it (a memory-safety net: the host checks).
+template <bool kRows>
+struct RowTable {
+  const int64_t* rows;
+  int64_t n_rows;
+};
+template <>
+struct RowTable<false> {};
+
+__device__ __forceinline__ const float* target_image(const float* __restrict__ target, const RowTable<true>& rt,
+                                                     int64_t b, int64_t HW) {
+  int64_t r = rt.rows[b];
+  r = r < 0 ? 0 : (r >= rt.n_rows ? rt.n_rows - 1 : r);
+  return target + r * HW;  // (64-bit: the cache may hold more than 2^32 elements)
+}
+
 __device__ __forceinline__ bool depth_valid(float t, float vmin, float vmax) {
   const bool finite = (__float_as_uint(t) & 0x7f800000u) != 0x7f800000u;
   return finite && t > vmin && t <= vmax;
 }
 
 // target of prediction element i of the dense [B][h][w] map
-__device__ __forceinline__ float masked_target(const float* __restrict__ target, int64_t i, const MaskedGeom& g) {
+template <bool kRows>
+__device__ __forceinline__ float masked_target(const float* __restrict__ target, const RowTable<kRows>& rt, int64_t i,
+                                               const MaskedGeom& g) {
   const int x = (int)(i % g.w);
   const int64_t r = i / g.w;
   const int y = (int)(r % g.h);
   const int64_t b = r / g.h;
   const int sy = nearest_src(y, g.sh, g.H);
   const int sx = nearest_src(x, g.sw, g.W);
-  return target[(b * g.H + sy) * g.W + sx];
+  if constexpr (!kRows) {
+    return target[(b * g.H + sy) * g.W + sx];
+  } else {
+    return target_image(target, rt, b, (int64_t)g.H * g.W)[(int64_t)sy * g.W + sx];
+  }
 }
 
+template <bool kRows>
 __global__ __launch_bounds__(256) void berhu_masked_max_kernel(const act_t* __restrict__ pred,
-                                                               const float* __restrict__ target, int64_t n,
-                                                               MaskedGeom g, float* __restrict__ maxpart,
+                                                               const float* __restrict__ target, RowTable<kRows> rt,
+                                                               int64_t n, MaskedGeom g, float* __restrict__ maxpart,
                                                                float* __restrict__ cntpart) {
   __shared__ float red_m[256];
   __shared__ float red_n[256];
   float m = 0.f, cnt = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float t = masked_target(target, i, g);
+    const float t = masked_target<kRows>(target, rt, i, g);
     if (!depth_valid(t, g.vmin, g.vmax)) continue;
     m = fmaxf(m, fabsf(lda1(pred + i) - t));
     cnt += 1.f;  // (at most n / gridDim.x + 256 < 2^24 per workgroup: exact in fp32)
@@ -72,9 +101,11 @@ __global__ __launch_bounds__(256) void berhu_masked_max_kernel(const act_t* __re
   }
 }
 
+template <bool kRows>
 __global__ __launch_bounds__(256) void berhu_masked_sum_kernel(const act_t* __restrict__ pred,
-                                                               const float* __restrict__ target, int64_t n,
-                                                               MaskedGeom g, const float* __restrict__ maxpart,
+                                                               const float* __restrict__ target, RowTable<kRows> rt,
+                                                               int64_t n, MaskedGeom g,
+                                                               const float* __restrict__ maxpart,
                                                                int nblk, float* __restrict__ sumpart,
                                                                float* __restrict__ out) {
   __shared__ float red[256];
@@ -91,7 +122,7 @@ __global__ __launch_bounds__(256) void berhu_masked_sum_kernel(const act_t* __re
   if (blockIdx.x == 0 && threadIdx.x == 0) out[1] = c;
   float acc = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float t = masked_target(target, i, g);
+    const float t = masked_target<kRows>(target, rt, i, g);
     if (!depth_valid(t, g.vmin, g.vmax)) continue;
     const float d = fabsf(lda1(pred + i) - t);
     acc += (d <= c) ? d : (d * d + c * c) / (2.f * c);
@@ -134,8 +165,9 @@ __global__ __launch_bounds__(256) void berhu_masked_finalize_kernel(const float*
 }
 
 // dpred = g / n_valid * (sign(diff) if |diff| <= c else diff / c) on valid pixels, exactly 0 elsewhere
+template <bool kRows>
 __global__ __launch_bounds__(256) void berhu_masked_bwd_kernel(const act_t* __restrict__ pred,
-                                                               const float* __restrict__ target,
+                                                               const float* __restrict__ target, RowTable<kRows> rt,
                                                                const float* __restrict__ stats,
                                                                const float* __restrict__ gscale, int64_t n,
                                                                MaskedGeom g, act_t* __restrict__ dpred) {
@@ -143,7 +175,7 @@ __global__ __launch_bounds__(256) void berhu_masked_bwd_kernel(const act_t* __re
   const float nv = stats[2];
   const float gn = nv > 0.f ? (gscale ? gscale[0] : 1.f) / nv : 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float t = masked_target(target, i, g);
+    const float t = masked_target<kRows>(target, rt, i, g);
     float r = 0.f;
     if (depth_valid(t, g.vmin, g.vmax)) {
       const float d = lda1(pred + i) - t;
@@ -194,13 +226,17 @@ struct UpGeom {
   float vmin, vmax;
 };
 
-// prediction up-sampled to target pixel p of the dense [B][H][W] map (p < 2^32: up_geom)
-__device__ __forceinline__ float up_value(const act_t* __restrict__ pred, int64_t p, const UpGeom& g) {
+// target pixel p of the dense [B][H][W] map of the BATCH (p < 2^32: up_geom) -> (b, Y, X)
+__device__ __forceinline__ void up_decode(int64_t p, const UpGeom& g, uint32_t& b, int& Y, int& X) {
   const uint32_t pu = (uint32_t)p;
   const uint32_t q = pu / (uint32_t)g.W;
-  const int X = (int)(pu - q * (uint32_t)g.W);
-  const uint32_t b = q / (uint32_t)g.H;
-  const int Y = (int)(q - b * (uint32_t)g.H);
+  X = (int)(pu - q * (uint32_t)g.W);
+  b = q / (uint32_t)g.H;
+  Y = (int)(q - b * (uint32_t)g.H);
+}
+
+// prediction up-sampled to target pixel (b, Y, X)
+__device__ __forceinline__ float up_value(const act_t* __restrict__ pred, uint32_t b, int Y, int X, const UpGeom& g) {
   const Lin ly = lin_coeff(Y, g.sh, g.h, g.H);
   const Lin lx = lin_coeff(X, g.sw, g.w, g.W);
   const act_t* pb = pred + (int64_t)b * g.h * g.w;
@@ -209,16 +245,35 @@ __device__ __forceinline__ float up_value(const act_t* __restrict__ pred, int64_
   return up_interp(lda1(r0 + lx.i0), lda1(r0 + lx.i1), lda1(r1 + lx.i0), lda1(r1 + lx.i1), ly, lx);
 }
 
+// target pixel p of the batch: the batch's own map, or - with a row table - the pixel of the cache image its image
+// selects: the 32-bit index is decoded within the batch first (into b, Y, X), the cache offset is 64-bit.  Without a
+// table the caller decodes after the validity test.
+template <bool kRows>
+__device__ __forceinline__ float up_target(const float* __restrict__ target, const RowTable<kRows>& rt, int64_t p,
+                                           const UpGeom& g, uint32_t& b, int& Y, int& X) {
+  if constexpr (!kRows) {
+    return target[p];
+  } else {
+    up_decode(p, g, b, Y, X);
+    return target_image(target, rt, (int64_t)b, (int64_t)g.H * g.W)[(int64_t)Y * g.W + X];
+  }
+}
+
+template <bool kRows>
 __global__ __launch_bounds__(256) void berhu_up_max_kernel(const act_t* __restrict__ pred,
-                                                           const float* __restrict__ target, int64_t n, UpGeom g,
-                                                           float* __restrict__ maxpart, float* __restrict__ cntpart) {
+                                                           const float* __restrict__ target, RowTable<kRows> rt,
+                                                           int64_t n, UpGeom g, float* __restrict__ maxpart,
+                                                           float* __restrict__ cntpart) {
   __shared__ float red_m[256];
   __shared__ float red_n[256];
   float m = 0.f, cnt = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float t = target[i];
+    uint32_t b;
+    int Y, X;
+    const float t = up_target<kRows>(target, rt, i, g, b, Y, X);
     if (!depth_valid(t, g.vmin, g.vmax)) continue;
-    m = fmaxf(m, fabsf(up_value(pred, i, g) - t));
+    if (!kRows) up_decode(i, g, b, Y, X);  // (validity first: a hole costs one load)
+    m = fmaxf(m, fabsf(up_value(pred, b, Y, X, g) - t));
     cnt += 1.f;  // (at most n / gridDim.x + 256 < 2^24 per workgroup: exact in fp32)
   }
   red_m[threadIdx.x] = m;
@@ -237,9 +292,11 @@ __global__ __launch_bounds__(256) void berhu_up_max_kernel(const act_t* __restri
   }
 }
 
+template <bool kRows>
 __global__ __launch_bounds__(256) void berhu_up_sum_kernel(const act_t* __restrict__ pred,
-                                                           const float* __restrict__ target, int64_t n, UpGeom g,
-                                                           const float* __restrict__ maxpart, int nblk,
+                                                           const float* __restrict__ target, RowTable<kRows> rt,
+                                                           int64_t n, UpGeom g, const float* __restrict__ maxpart,
+                                                           int nblk,
                                                            float* __restrict__ sumpart, float* __restrict__ out) {
   __shared__ float red[256];
   float m = 0.f;
@@ -255,9 +312,12 @@ __global__ __launch_bounds__(256) void berhu_up_sum_kernel(const act_t* __restri
   if (blockIdx.x == 0 && threadIdx.x == 0) out[1] = c;
   float acc = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float t = target[i];
+    uint32_t b;
+    int Y, X;
+    const float t = up_target<kRows>(target, rt, i, g, b, Y, X);
     if (!depth_valid(t, g.vmin, g.vmax)) continue;
-    const float d = fabsf(up_value(pred, i, g) - t);
+    if (!kRows) up_decode(i, g, b, Y, X);  // (validity first: a hole costs one load)
+    const float d = fabsf(up_value(pred, b, Y, X, g) - t);
     acc += (d <= c) ? d : (d * d + c * c) / (2.f * c);
   }
   red[threadIdx.x] = acc;
@@ -273,8 +333,9 @@ __global__ __launch_bounds__(256) void berhu_up_sum_kernel(const act_t* __restri
 // tid % G of its group = (lane / gx, lane % gx) of the gx x (G / gx) grid over the pixel's target range.
 // dpred = gscale / n_valid * sum r Wy Wx over the valid targets of the range, r = sign(v - t) if |v - t| <= c else
 // (v - t) / c; a pixel without a valid target in its range gets an exact zero.
+template <bool kRows>
 __global__ __launch_bounds__(256) void berhu_up_bwd_kernel(const act_t* __restrict__ pred,
-                                                           const float* __restrict__ target,
+                                                           const float* __restrict__ target, RowTable<kRows> rt,
                                                            const float* __restrict__ stats,
                                                            const float* __restrict__ gscale, UpGeom g, int T, int G,
                                                            int gx, int tiles_y, int tiles_x,
@@ -307,6 +368,8 @@ __global__ __launch_bounds__(256) void berhu_up_bwd_kernel(const act_t* __restri
   const int i = y0 + iy, j = x0 + jx;
   float acc = 0.f;
   if (own) {
+    const float* timg = target;  // (the image of the workgroup's b: one scalar load of the table)
+    if constexpr (kRows) timg = target_image(target, rt, (int64_t)b, (int64_t)g.H * g.W);
     const int gy = G / gx;
     const int ly0 = lane / gx, lx0 = lane - ly0 * gx;
     int ylo, yhi, xlo, xhi;
@@ -318,7 +381,7 @@ __global__ __launch_bounds__(256) void berhu_up_bwd_kernel(const act_t* __restri
       if (wy == 0.f) continue;  // (so ly.i0, ly.i1 lie in [i - 1, i + 1]: inside the patch)
       const float* r0 = patch + (ly.i0 - oy) * kUpPatchW;
       const float* r1 = patch + (ly.i1 - oy) * kUpPatchW;
-      const float* trow = target + ((int64_t)b * g.H + Y) * g.W;
+      const float* trow = kRows ? timg + (int64_t)Y * g.W : target + ((int64_t)b * g.H + Y) * g.W;
       for (int X = xlo + lx0; X <= xhi; X += gx) {
         const float t = trow[X];
         if (!depth_valid(t, g.vmin, g.vmax)) continue;
@@ -365,6 +428,107 @@ inline int up_bwd_group(int h, int w, int H, int W) {
   return G;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Launches: one body per entry-point pair.  kRows false: target is the batch's own [B][H][W] map (rt unused);
+// true: the cache [n_rows][H][W] and the device table of B rows.  Same geometry, same order of sums, same finalize.
+// ---------------------------------------------------------------------------------------------------------------
+inline bool rows_ok(const RowTable<false>&) { return true; }
+inline bool rows_ok(const RowTable<true>& rt) { return rt.rows && rt.n_rows > 0; }
+#define ROWS_CHECK(who) NASSEG_REQUIRE(rows_ok(rt), "%s: a row table of B entries and n_rows > 0 are expected", who)
+
+template <bool kRows>
+int masked_fwd(const char* who, const act_t* pred, const float* target, RowTable<kRows> rt, int B, int h, int w, int H,
+               int W, float valid_min, float valid_max, float* out, float* ws, void* stream) {
+  MaskedGeom g;
+  NASSEG_REQUIRE(masked_geom(B, h, w, H, W, valid_min, valid_max, &g), "%s: bad shape", who);
+  NASSEG_REQUIRE(pred && target && out && ws, "%s: null pointer", who);
+  ROWS_CHECK(who);
+  NASSEG_REQUIRE(valid_min == valid_min && valid_max == valid_max, "%s: NaN bound", who);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = (int64_t)B * h * w;
+  const int grid = red_grid(n);
+  float* maxpart = ws;
+  float* cntpart = ws + kMaxGrid;
+  float* sumpart = ws + 2 * kMaxGrid;
+  hipLaunchKernelGGL(berhu_masked_max_kernel<kRows>, dim3(grid), dim3(256), 0, s, pred, target, rt, n, g, maxpart,
+                     cntpart);
+  NASSEG_LAUNCH_CHECK("berhu_masked_max");
+  hipLaunchKernelGGL(berhu_masked_sum_kernel<kRows>, dim3(grid), dim3(256), 0, s, pred, target, rt, n, g, maxpart,
+                     grid, sumpart, out);
+  NASSEG_LAUNCH_CHECK("berhu_masked_sum");
+  hipLaunchKernelGGL(berhu_masked_finalize_kernel, dim3(1), dim3(256), 0, s, sumpart, cntpart, grid, out);
+  NASSEG_LAUNCH_CHECK("berhu_masked_finalize");
+  return NASSEG_OK;
+}
+
+template <bool kRows>
+int masked_bwd(const char* who, const act_t* pred, const float* target, RowTable<kRows> rt, const float* stats,
+               const float* gscale, int B, int h, int w, int H, int W, float valid_min, float valid_max, act_t* dpred,
+               void* stream) {
+  MaskedGeom g;
+  NASSEG_REQUIRE(masked_geom(B, h, w, H, W, valid_min, valid_max, &g), "%s: bad shape", who);
+  NASSEG_REQUIRE(pred && target && stats && dpred, "%s: null pointer", who);
+  ROWS_CHECK(who);
+  const int64_t n = (int64_t)B * h * w;
+  hipLaunchKernelGGL(berhu_masked_bwd_kernel<kRows>, dim3(red_grid(n) * 2), dim3(256), 0, (hipStream_t)stream, pred,
+                     target, rt, stats, gscale, n, g, dpred);
+  NASSEG_LAUNCH_CHECK("berhu_masked_bwd");
+  return NASSEG_OK;
+}
+
+#define UP_GEOM_CHECK(who) \
+  NASSEG_REQUIRE(up_geom(B, h, w, H, W, valid_min, valid_max, &g), "%s: bad shape (B*H*W < 2^32, B*h*w < 2^31)", who)
+
+template <bool kRows>
+int up_fwd(const char* who, const act_t* pred, const float* target, RowTable<kRows> rt, int B, int h, int w, int H,
+           int W, float valid_min, float valid_max, float* out, float* ws, void* stream) {
+  UpGeom g;
+  UP_GEOM_CHECK(who);
+  NASSEG_REQUIRE(pred && target && out && ws, "%s: null pointer", who);
+  ROWS_CHECK(who);
+  NASSEG_REQUIRE(valid_min == valid_min && valid_max == valid_max, "%s: NaN bound", who);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = (int64_t)B * H * W;
+  const int grid = red_grid(n);
+  float* maxpart = ws;
+  float* cntpart = ws + kMaxGrid;
+  float* sumpart = ws + 2 * kMaxGrid;
+  hipLaunchKernelGGL(berhu_up_max_kernel<kRows>, dim3(grid), dim3(256), 0, s, pred, target, rt, n, g, maxpart,
+                     cntpart);
+  NASSEG_LAUNCH_CHECK("berhu_up_max");
+  hipLaunchKernelGGL(berhu_up_sum_kernel<kRows>, dim3(grid), dim3(256), 0, s, pred, target, rt, n, g, maxpart, grid,
+                     sumpart, out);
+  NASSEG_LAUNCH_CHECK("berhu_up_sum");
+  hipLaunchKernelGGL(berhu_masked_finalize_kernel, dim3(1), dim3(256), 0, s, sumpart, cntpart, grid, out);
+  NASSEG_LAUNCH_CHECK("berhu_up_finalize");
+  return NASSEG_OK;
+}
+
+template <bool kRows>
+int up_bwd(const char* who, const act_t* pred, const float* target, RowTable<kRows> rt, const float* stats,
+           const float* gscale, int B, int h, int w, int H, int W, float valid_min, float valid_max, int group,
+           act_t* dpred, void* stream) {
+  UpGeom g;
+  UP_GEOM_CHECK(who);
+  NASSEG_REQUIRE(pred && target && stats && dpred, "%s: null pointer", who);
+  ROWS_CHECK(who);
+  NASSEG_REQUIRE(valid_min == valid_min && valid_max == valid_max, "%s: NaN bound", who);
+  NASSEG_REQUIRE(group == 0 || group == 1 || group == 4 || group == 16 || group == 64 || group == 256,
+                 "%s: group must be 0, 1, 4, 16, 64 or 256 (got %d)", who, group);
+  const int G = group ? group : up_bwd_group(h, w, H, W);
+  int T = kUpMaxTile;  // G T T = 256
+  for (int k = G; k > 1; k /= 4) T /= 2;
+  const int gx = G >= 256 ? 32 : (G >= 16 ? 16 : G);
+  const int tiles_y = cdiv(h, T), tiles_x = cdiv(w, T);
+  const int64_t nwg = (int64_t)B * tiles_y * tiles_x;  // (<= B*h*w < 2^31: up_geom)
+  hipLaunchKernelGGL(berhu_up_bwd_kernel<kRows>, dim3((unsigned)nwg), dim3(kUpThreads), 0, (hipStream_t)stream, pred,
+                     target, rt, stats, gscale, g, T, G, gx, tiles_y, tiles_x, dpred);
+  NASSEG_LAUNCH_CHECK("berhu_up_bwd");
+  return NASSEG_OK;
+}
+
+const RowTable<false> kNoRows = {};
+
 }  // namespace
 
 extern "C" {
@@ -377,38 +541,34 @@ int64_t nasseg_berhu_masked_workspace(void) { return 3 * kMaxGrid; }
 // ws: nasseg_berhu_masked_workspace() floats.
 int NASSEG_FN(berhu_masked_fwd)(const act_t* pred, const float* target, int B, int h, int w, int H, int W,
                                 float valid_min, float valid_max, float* out, float* ws, void* stream) {
-  MaskedGeom g;
-  NASSEG_REQUIRE(masked_geom(B, h, w, H, W, valid_min, valid_max, &g), "berhu_masked_fwd: bad shape");
-  NASSEG_REQUIRE(pred && target && out && ws, "berhu_masked_fwd: null pointer");
-  NASSEG_REQUIRE(valid_min == valid_min && valid_max == valid_max, "berhu_masked_fwd: NaN bound");
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t n = (int64_t)B * h * w;
-  const int grid = red_grid(n);
-  float* maxpart = ws;
-  float* cntpart = ws + kMaxGrid;
-  float* sumpart = ws + 2 * kMaxGrid;
-  hipLaunchKernelGGL(berhu_masked_max_kernel, dim3(grid), dim3(256), 0, s, pred, target, n, g, maxpart, cntpart);
-  NASSEG_LAUNCH_CHECK("berhu_masked_max");
-  hipLaunchKernelGGL(berhu_masked_sum_kernel, dim3(grid), dim3(256), 0, s, pred, target, n, g, maxpart, grid,
-                     sumpart, out);
-  NASSEG_LAUNCH_CHECK("berhu_masked_sum");
-  hipLaunchKernelGGL(berhu_masked_finalize_kernel, dim3(1), dim3(256), 0, s, sumpart, cntpart, grid, out);
-  NASSEG_LAUNCH_CHECK("berhu_masked_finalize");
-  return NASSEG_OK;
+  return masked_fwd<false>("berhu_masked_fwd", pred, target, kNoRows, B, h, w, H, W, valid_min, valid_max, out, ws,
+                           stream);
 }
 
 // stats = out of nasseg_berhu_masked_fwd; gscale = device scalar upstream gradient (null = 1)
 int NASSEG_FN(berhu_masked_bwd)(const act_t* pred, const float* target, const float* stats, const float* gscale,
                                 int B, int h, int w, int H, int W, float valid_min, float valid_max, act_t* dpred,
                                 void* stream) {
-  MaskedGeom g;
-  NASSEG_REQUIRE(masked_geom(B, h, w, H, W, valid_min, valid_max, &g), "berhu_masked_bwd: bad shape");
-  NASSEG_REQUIRE(pred && target && stats && dpred, "berhu_masked_bwd: null pointer");
-  const int64_t n = (int64_t)B * h * w;
-  hipLaunchKernelGGL(berhu_masked_bwd_kernel, dim3(red_grid(n) * 2), dim3(256), 0, (hipStream_t)stream, pred,
-                     target, stats, gscale, n, g, dpred);
-  NASSEG_LAUNCH_CHECK("berhu_masked_bwd");
-  return NASSEG_OK;
+  return masked_bwd<false>("berhu_masked_bwd", pred, target, kNoRows, stats, gscale, B, h, w, H, W, valid_min,
+                           valid_max, dpred, stream);
+}
+
+// The row-indexed twins: target is the whole cache [n_rows][H][W], rows a device array of B cache rows; image b of the
+// prediction meets target[clamp(rows[b], 0, n_rows - 1)].  Everything else - and every bit - as above on target[rows].
+int NASSEG_FN(berhu_masked_rows_fwd)(const act_t* pred, const float* target, const int64_t* rows, int64_t n_rows,
+                                     int B, int h, int w, int H, int W, float valid_min, float valid_max, float* out,
+                                     float* ws, void* stream) {
+  const RowTable<true> rt = {rows, n_rows};
+  return masked_fwd<true>("berhu_masked_rows_fwd", pred, target, rt, B, h, w, H, W, valid_min, valid_max, out, ws,
+                          stream);
+}
+
+int NASSEG_FN(berhu_masked_rows_bwd)(const act_t* pred, const float* target, const int64_t* rows, int64_t n_rows,
+                                     const float* stats, const float* gscale, int B, int h, int w, int H, int W,
+                                     float valid_min, float valid_max, act_t* dpred, void* stream) {
+  const RowTable<true> rt = {rows, n_rows};
+  return masked_bwd<true>("berhu_masked_rows_bwd", pred, target, rt, stats, gscale, B, h, w, H, W, valid_min,
+                          valid_max, dpred, stream);
 }
 
 #if NASSEG_FP32_ONLY
@@ -419,31 +579,11 @@ int64_t nasseg_berhu_up_workspace(int B, int h, int w, int H, int W) {
 }
 #endif
 
-#define UP_GEOM_CHECK(who) \
-  NASSEG_REQUIRE(up_geom(B, h, w, H, W, valid_min, valid_max, &g), who ": bad shape (B*H*W < 2^32, B*h*w < 2^31)")
-
 // pred: dense [B][h][w] (one channel), target: fp32 [B][H][W].  out[0] = loss, out[1] = c, out[2] = n_valid.
 // ws: nasseg_berhu_up_workspace floats.
 int NASSEG_FN(berhu_up_fwd)(const act_t* pred, const float* target, int B, int h, int w, int H, int W,
                             float valid_min, float valid_max, float* out, float* ws, void* stream) {
-  UpGeom g;
-  UP_GEOM_CHECK("berhu_up_fwd");
-  NASSEG_REQUIRE(pred && target && out && ws, "berhu_up_fwd: null pointer");
-  NASSEG_REQUIRE(valid_min == valid_min && valid_max == valid_max, "berhu_up_fwd: NaN bound");
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t n = (int64_t)B * H * W;
-  const int grid = red_grid(n);
-  float* maxpart = ws;
-  float* cntpart = ws + kMaxGrid;
-  float* sumpart = ws + 2 * kMaxGrid;
-  hipLaunchKernelGGL(berhu_up_max_kernel, dim3(grid), dim3(256), 0, s, pred, target, n, g, maxpart, cntpart);
-  NASSEG_LAUNCH_CHECK("berhu_up_max");
-  hipLaunchKernelGGL(berhu_up_sum_kernel, dim3(grid), dim3(256), 0, s, pred, target, n, g, maxpart, grid, sumpart,
-                     out);
-  NASSEG_LAUNCH_CHECK("berhu_up_sum");
-  hipLaunchKernelGGL(berhu_masked_finalize_kernel, dim3(1), dim3(256), 0, s, sumpart, cntpart, grid, out);
-  NASSEG_LAUNCH_CHECK("berhu_up_finalize");
-  return NASSEG_OK;
+  return up_fwd<false>("berhu_up_fwd", pred, target, kNoRows, B, h, w, H, W, valid_min, valid_max, out, ws, stream);
 }
 
 // stats = out of nasseg_berhu_up_fwd; gscale = device scalar upstream gradient (null = 1); group: lanes per
@@ -451,22 +591,25 @@ int NASSEG_FN(berhu_up_fwd)(const act_t* pred, const float* target, int B, int h
 int NASSEG_FN(berhu_up_bwd)(const act_t* pred, const float* target, const float* stats, const float* gscale, int B,
                             int h, int w, int H, int W, float valid_min, float valid_max, int group, act_t* dpred,
                             void* stream) {
-  UpGeom g;
-  UP_GEOM_CHECK("berhu_up_bwd");
-  NASSEG_REQUIRE(pred && target && stats && dpred, "berhu_up_bwd: null pointer");
-  NASSEG_REQUIRE(valid_min == valid_min && valid_max == valid_max, "berhu_up_bwd: NaN bound");
-  NASSEG_REQUIRE(group == 0 || group == 1 || group == 4 || group == 16 || group == 64 || group == 256,
-                 "berhu_up_bwd: group must be 0, 1, 4, 16, 64 or 256 (got %d)", group);
-  const int G = group ? group : up_bwd_group(h, w, H, W);
-  int T = kUpMaxTile;  // G T T = 256
-  for (int k = G; k > 1; k /= 4) T /= 2;
-  const int gx = G >= 256 ? 32 : (G >= 16 ? 16 : G);
-  const int tiles_y = cdiv(h, T), tiles_x = cdiv(w, T);
-  const int64_t nwg = (int64_t)B * tiles_y * tiles_x;  // (<= B*h*w < 2^31: up_geom)
-  hipLaunchKernelGGL(berhu_up_bwd_kernel, dim3((unsigned)nwg), dim3(kUpThreads), 0, (hipStream_t)stream, pred, target,
-                     stats, gscale, g, T, G, gx, tiles_y, tiles_x, dpred);
-  NASSEG_LAUNCH_CHECK("berhu_up_bwd");
-  return NASSEG_OK;
+  return up_bwd<false>("berhu_up_bwd", pred, target, kNoRows, stats, gscale, B, h, w, H, W, valid_min, valid_max,
+                       group, dpred, stream);
+}
+
+// row-indexed twins (see nasseg_berhu_masked_rows_fwd): the limits B*H*W < 2^32, B*h*w < 2^31 are the BATCH's, the
+// cache may be larger
+int NASSEG_FN(berhu_up_rows_fwd)(const act_t* pred, const float* target, const int64_t* rows, int64_t n_rows, int B,
+                                 int h, int w, int H, int W, float valid_min, float valid_max, float* out, float* ws,
+                                 void* stream) {
+  const RowTable<true> rt = {rows, n_rows};
+  return up_fwd<true>("berhu_up_rows_fwd", pred, target, rt, B, h, w, H, W, valid_min, valid_max, out, ws, stream);
+}
+
+int NASSEG_FN(berhu_up_rows_bwd)(const act_t* pred, const float* target, const int64_t* rows, int64_t n_rows,
+                                 const float* stats, const float* gscale, int B, int h, int w, int H, int W,
+                                 float valid_min, float valid_max, int group, act_t* dpred, void* stream) {
+  const RowTable<true> rt = {rows, n_rows};
+  return up_bwd<true>("berhu_up_rows_bwd", pred, target, rt, stats, gscale, B, h, w, H, W, valid_min, valid_max,
+                      group, dpred, stream);
 }
 
 }  // extern "C"

@@ -37,7 +37,8 @@ from torch import nn
 
 from .. import functional as F
 from . import graph_dag
-from .trainer_common import check_cache_rows, clip_and_step, inner, task0_loss, task1_depth_loss, task1_loss
+from .trainer_common import (check_cache_rows, clip_and_step, inner, task0_depth_loss, task0_loss, task1_depth_loss,
+                             task1_loss)
 
 logger = logging.getLogger(__name__)
 
@@ -397,10 +398,16 @@ class GraphedTask0Step(_GraphedStep):
     ``kd_coeff`` (not None): the loss has the distillation term kd_coeff * nn.MSELoss()(output, kd_y) of
     src/engine/trainer.py:147-149, the teacher rows gathered from the cache's ``kd_y`` inside the graph too and
     the term fused with the softmax/NLL (F.log_softmax_nll_mse).
+    ``depth_crit`` (an nn.BerHuLoss; the cache has a 'depth' entry, populate_task0(task="depth")): the depth step -
+    ``task0_depth_loss``: the criterion's kernels read the full-size maps of the cache in place through the step's
+    static index tensor, so the graph holds no gather of the targets; its bounds are recorded by value.
     """
 
     def __init__(self, Xy_train, segmenter, optim_dec, batch_size, ignore_index=255, dec_grad_clip=0.0,
-                 aux_weight=0, capture_optimisers=False, warmup=2, kd_coeff=None, segm_crit=None):
+                 aux_weight=0, capture_optimisers=False, warmup=2, kd_coeff=None, segm_crit=None, depth_crit=None):
+        if depth_crit is not None and (kd_coeff is not None or segm_crit is not None or "depth" not in Xy_train):
+            raise ValueError("GraphedTask0Step: depth_crit needs a depth cache (populate_task0(task=\"depth\")) and "
+                             "goes with neither distillation nor a segmentation criterion")
         if kd_coeff is not None and segm_crit is not None:
             raise ValueError("GraphedTask0Step: the fused distillation term exists for the plain softmax/NLL only")
         if getattr(segm_crit, "full_size", False):
@@ -413,13 +420,17 @@ class GraphedTask0Step(_GraphedStep):
         self.aux_weight = aux_weight
         self.kd_coeff = kd_coeff
         self.segm_crit = segm_crit  # (an nn.SegmCrossEntropy; not together with kd_coeff: no fused term for it)
+        self.depth_crit = depth_crit
         self._trained = [model.decoder]
         self.groups = [(list(model.decoder.parameters()), dec_grad_clip, optim_dec)]
         self.decoder = model.decoder
-        self.index = torch.arange(batch_size, device=Xy_train["y"].device, dtype=torch.int64)
+        self.index = torch.arange(batch_size, device=Xy_train["depth" if depth_crit is not None else "y"].device,
+                                  dtype=torch.int64)
         self._init_common(segmenter, capture_optimisers, (optim_dec,), warmup)
 
     def _forward_loss(self):
+        if self.depth_crit is not None:
+            return task0_depth_loss(self.cache, self.index, self.decoder, self.depth_crit, self.aux_weight)
         return task0_loss(self.cache, self.index, self.decoder, self.ignore_index, self.aux_weight, self.kd_coeff,
                           segm_crit=self.segm_crit)
 

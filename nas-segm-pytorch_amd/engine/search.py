@@ -17,7 +17,7 @@ from .graphed import GraphedSegmenterStep
 from ..nn.losses import BerHuLoss
 from .inference import validate, validate_depth
 from .segmenter import RankParallel, Segmenter
-from .trainer import _ignore_index, _segm_crit, train_segmenter
+from .trainer import _ignore_index, _segm_crit, populate_task0, train_segmenter, train_task0
 
 
 class _Crit(object):
@@ -47,7 +47,7 @@ def build_candidate(config, ctrl_version="wacv", num_classes=19, agg_size=48, au
 def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", num_classes=19,
                        agg_size=48, aux_cell=True, repeats=1, epochs=1, aux_weight=0.15,
                        omit_classes=(0,), device="cuda", stats=None, graphed=False, task="segm",
-                       min_depth=1e-3, max_depth=10.0, segm_crit=None, depth_crit=None):
+                       min_depth=1e-3, max_depth=10.0, segm_crit=None, depth_crit=None, task0_epochs=0):
     """Train the candidate on ``train_batches`` (lists of {"image", "mask"}) for ``epochs``
     passes and return its validation reward; failures score 0 like in the reference.
     task="depth": the masks are fp32 depth maps at the image's size (holes: 0 / NaN / inf), the decoder has one
@@ -56,13 +56,19 @@ def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", 
     (``min_depth`` / ``max_depth``: its valid range).  Any other ``depth_crit``, or one given with task="segm", is a
     ValueError.
     ``segm_crit`` (task="segm"): the training criterion, e.g. an nn.SegmCrossEntropy with class weights,
-    hard-example mining or a region-overlap (soft Jaccard / Dice) term; None: LogSoftmax + NLL with ignore index 255."""
+    hard-example mining or a region-overlap (soft Jaccard / Dice) term; None: LogSoftmax + NLL with ignore index 255.
+    ``task0_epochs`` > 0: the search protocol's first stage before the ``epochs`` end-to-end ones - the encoder's
+    features of every sample of ``train_batches`` are cached once (``populate_task0``; task="depth": with the
+    full-size depth maps) and the decoder alone is trained on the cache for that many epochs (``train_task0``, at the
+    batches' size, with the same criterion).  0: no such stage, exactly as before."""
     if depth_crit is not None and not isinstance(depth_crit, BerHuLoss):
         raise ValueError("evaluate_candidate: depth_crit must be an nn.BerHuLoss (got {!r})".format(depth_crit))
+    if not isinstance(task0_epochs, int) or isinstance(task0_epochs, bool) or task0_epochs < 0:
+        raise ValueError("evaluate_candidate: task0_epochs must be an integer >= 0 (got {!r})".format(task0_epochs))
     if _task(task) == "depth":
         return _evaluate_depth_candidate(config, train_batches, val_batches, ctrl_version, agg_size, aux_cell,
                                          repeats, epochs, aux_weight, device, stats, graphed, min_depth, max_depth,
-                                         depth_crit)
+                                         depth_crit, task0_epochs)
     if depth_crit is not None:
         raise ValueError("evaluate_candidate: depth_crit belongs to task=\"depth\" (got task={!r})".format(task))
     try:
@@ -75,6 +81,8 @@ def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", 
     optim_dec = torch.optim.Adam(model.decoder.parameters(), lr=3e-3, weight_decay=1e-5)
     aux = aux_weight if ctrl_version == "cvpr" else -1
     segm_crit = _Crit() if segm_crit is None else segm_crit
+    if task0_epochs and not _task0_stage(segmenter, train_batches, optim_dec, segm_crit, task0_epochs, aux, "segm"):
+        return 0.0
     if graphed:
         # one capture per candidate, one replay per step (engine/graphed.py): same results, no host
         # launch cost - what bounds a candidate at 321x321 ... 713x713
@@ -104,10 +112,28 @@ def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", 
     return float(reward)
 
 
+def _task0_stage(segmenter, train_batches, optim_dec, crit, task0_epochs, aux, task):
+    """the decoder-only stage of ``evaluate_candidate``: cache every sample of ``train_batches``, then ``task0_epochs``
+    epochs of ``train_task0`` at the batches' size (clip norm 3, as the end-to-end stage).  False: a RuntimeError
+    inside (``try_except``) - the candidate scores 0.  The module is left in training mode, as it was built."""
+    n_train = sum(int(b["image"].shape[0]) for b in train_batches)
+    cache = populate_task0(segmenter, train_batches, None, n_train, task=task)
+    ok = not isinstance(cache, int)  # (try_except: 0)
+    for epoch in range(task0_epochs if ok else 0):
+        if train_task0(cache, segmenter, optim_dec, epoch, crit, None, int(train_batches[0]["image"].shape[0]), False,
+                       False, 0.0, 3.0, False, aux_weight=aux) == 0:
+            ok = False
+            break
+    segmenter.train()
+    return ok
+
+
 def _evaluate_depth_candidate(config, train_batches, val_batches, ctrl_version, agg_size, aux_cell, repeats, epochs,
-                              aux_weight, device, stats, graphed, min_depth, max_depth, depth_crit=None):
+                              aux_weight, device, stats, graphed, min_depth, max_depth, depth_crit=None,
+                              task0_epochs=0):
     """``evaluate_candidate`` for task="depth": the same optimisers, clip norms and eager / replayed paths, with the
-    depth step (``depth_crit``; None: BerHuLoss(valid_min=0)) and the depth reward"""
+    depth step (``depth_crit``; None: BerHuLoss(valid_min=0)) and the depth reward; ``task0_epochs``: decoder-only
+    epochs on the depth cache first"""
     try:
         segmenter = build_candidate(config, ctrl_version, 1, agg_size, aux_cell, repeats, device, task="depth")
     except RuntimeError:
@@ -122,6 +148,8 @@ def _evaluate_depth_candidate(config, train_batches, val_batches, ctrl_version, 
         return (sample["image"].to(device=device, dtype=torch.float32).contiguous(memory_format=torch.channels_last),
                 sample["mask"].to(device=device, dtype=torch.float32))
 
+    if task0_epochs and not _task0_stage(segmenter, train_batches, optim_dec, crit, task0_epochs, aux, "depth"):
+        return 0.0
     if graphed:
         try:
             image, depth = on_device(train_batches[0])

@@ -24,7 +24,8 @@ from ..helpers.utils import AverageMeter, try_except
 from ..nn.losses import BerHuLoss, SegmCrossEntropy
 from ..nn.modules import TREE_VERSION
 from . import graphed
-from .trainer_common import cache_feature_keys, check_cache_rows, task0_loss, task1_depth_loss, task1_loss
+from .trainer_common import (cache_feature_keys, check_cache_rows, task0_depth_loss, task0_loss, task1_depth_loss,
+                             task1_loss)
 from .trainer_common import clip_and_step as _clip_and_step
 from .trainer_common import inner as _inner
 
@@ -290,9 +291,9 @@ def _cached_stepper(owner, slot, base_key, shape_key, build):
 
 
 def _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_clip, aux_weight, kd_coeff=None,
-                   segm_crit=None):
+                   segm_crit=None, depth_crit=None):
     """kd_coeff: None - no distillation term; else the coefficient of the fused nn.MSELoss term (``native_kd``);
-    segm_crit: ``_segm_crit``'s"""
+    segm_crit: ``_segm_crit``'s; depth_crit: the nn.BerHuLoss of the depth step on a depth cache"""
     model = _inner(segmenter)
     base = (TREE_VERSION[0], id(optim_dec), ignore, dec_grad_clip, aux_weight, _bn_modes(model.decoder),
             _trainable_signature(list(model.decoder.parameters()), (optim_dec,)))
@@ -302,6 +303,9 @@ def _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_
     if segm_crit is not None:  # (threshold, min_kept and keep_fraction are kernel arguments: recorded by value)
         base = base + (segm_crit.config(),)
         extra["segm_crit"] = segm_crit
+    if depth_crit is not None:  # (the loss kind; valid_min and valid_max are kernel arguments: recorded by value)
+        base = base + ((id(depth_crit),) + depth_crit.config(),)
+        extra["depth_crit"] = depth_crit
     shape = (batch_size, tuple((k, v.data_ptr(), tuple(v.shape)) for k, v in Xy_train.items() if k != "out_size"))
     return _cached_stepper(model, "_nasseg_task0_stepper", base, shape, lambda: graphed.GraphedTask0Step(
         Xy_train, segmenter, optim_dec, batch_size, ignore, dec_grad_clip, aux_weight, kd_coeff=kd_coeff, **extra))
@@ -325,7 +329,7 @@ def _segmenter_stepper(segmenter, image, target, optim_enc, optim_dec, ignore, e
 
 
 @try_except
-def populate_task0(segmenter, train_loader, kd_net, n_train, do_kd=False):
+def populate_task0(segmenter, train_loader, kd_net, n_train, do_kd=False, task="segm"):
     """Run the encoder (eval, no grad, one image at a time) over ``n_train``
     samples and keep its feature maps, the nearest-resized labels and optionally
     the teacher's logits on the device.  Returns the cache dict
@@ -335,7 +339,17 @@ def populate_task0(segmenter, train_loader, kd_net, n_train, do_kd=False):
     and is stored channels_last, pre-allocated for ``n_train`` samples on the first batch and
     filled in place by copy kernels (no list of slices, no torch.stack, no layout change), so
     that a training step gathers its batch with one nasseg_gather_rows per entry.  Data
-    parallel, every rank caches the samples of ITS loader: the cache is sharded."""
+    parallel, every rank caches the samples of ITS loader: the cache is sharded.
+
+    task="depth": the masks are depth maps; instead of 'y' the cache gets 'depth': (N, H, W) fp32, the loader's maps
+    as they arrive - full size, holes (0 / NaN / inf) included, bit for bit, nothing resized: the berHu kernels of
+    the decoder-only depth step read them in place through the batch's row index (``train_task0`` with an
+    nn.BerHuLoss).  All maps must share one (H, W) - the cache is one tensor - and there is no distillation term for
+    depth: otherwise ValueError."""
+    if task not in ("segm", "depth"):
+        raise ValueError("populate_task0: task must be 'segm' or 'depth' (got {!r})".format(task))
+    if task == "depth" and do_kd:
+        raise ValueError("populate_task0: there is no distillation term for depth (do_kd with task=\"depth\")")
     cache = {}
     segmenter.eval()
     _set_stage(train_loader, "train")
@@ -365,9 +379,18 @@ def populate_task0(segmenter, train_loader, kd_net, n_train, do_kd=False):
             for i, f in enumerate(feats):
                 store(i, f, seen)
             size = feats[0].size()[2:]
-            labels = _labels(sample["mask"], device)
-            F.nearest_label_resize(labels, size, out=slot(
-                "y", torch.empty((1,) + tuple(size), dtype=torch.int64), seen, b))
+            if task == "depth":
+                depth = _depth_target(sample["mask"], device)
+                if depth.dim() != 3 or depth.shape[0] != b or (
+                        "depth" in cache and tuple(depth.shape[1:]) != tuple(cache["depth"].shape[1:])):
+                    raise ValueError("populate_task0: depth maps of one size (b, H, W) expected - the cache is one "
+                                     "tensor (got {}{})".format(tuple(depth.shape), ", cached {}".format(
+                                         tuple(cache["depth"].shape[1:])) if "depth" in cache else ""))
+                slot("depth", depth, seen, b).copy_(depth)  # (a plain device copy: every bit, NaN payloads included)
+            else:
+                labels = _labels(sample["mask"], device)
+                F.nearest_label_resize(labels, size, out=slot(
+                    "y", torch.empty((1,) + tuple(size), dtype=torch.int64), seen, b))
             if do_kd:
                 # (the teacher runs in fp32 whatever the candidate's activation storage)
                 store("kd_y", F.bilinear_resize(kd_net(image if image.dtype == torch.float32 else image.float()),
@@ -378,6 +401,10 @@ def populate_task0(segmenter, train_loader, kd_net, n_train, do_kd=False):
                 for k in list(cache):
                     cache[k] = cache[k][:seen]
                 cache["out_size"] = size
+                if task == "depth":
+                    d = cache["depth"]
+                    logger.info(" Depth cache: {} maps of {} x {}, fp32, {:.1f} MiB".format(
+                        d.shape[0], d.shape[1], d.shape[2], d.numel() * d.element_size() / 2.0 ** 20))
                 break
         else:
             for k in list(cache):  # (loader exhausted first - as in the reference, no 'out_size' then)
@@ -386,7 +413,7 @@ def populate_task0(segmenter, train_loader, kd_net, n_train, do_kd=False):
 
 
 def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255, dec_grad_clip=0.0, aux_weight=0,
-                    freeze_bn=False, do_kd=False, kd_coeff=0.0, kd_crit=None, segm_crit=None):
+                    freeze_bn=False, do_kd=False, kd_coeff=0.0, kd_crit=None, segm_crit=None, depth_crit=None):
     """step(batch_idx) -> device loss: one decoder-only training step on the cache rows
     ``batch_idx`` (a host array of ``batch_size`` indices).  Small batches are launch-bound, so the
     step is replayed from a hipGraph where that wins (engine/graphed.py: auto_graph; the stepper
@@ -397,16 +424,25 @@ def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255
     softmax/NLL [+ kd_coeff * MSE to the cached teacher logits, one fused kernel] (+ aux heads),
     backward, [all-reduce], clip, optimiser.
     ``segm_crit`` (``_segm_crit``'s: class weights / hard-example selection / region term): the loss of every head; with
-    distillation as well the step is launched from the host and ``kd_crit`` is called as written."""
+    distillation as well the step is launched from the host and ``kd_crit`` is called as written.
+    ``depth_crit`` (an nn.BerHuLoss, on a cache with a 'depth' entry - populate_task0(task="depth")): the depth step
+    instead - gather the feature rows, decoder, the criterion of every head against the full-size maps of the cache,
+    read in place through the batch's rows (trainer_common.task0_depth_loss): nothing is resized, no target batch is
+    gathered; replayed or launched from the host by the same rule."""
     decoder = _inner(segmenter).decoder
     feat = Xy_train[cache_feature_keys(Xy_train)[0]]
     out_size = tuple(Xy_train["out_size"])
-    device = Xy_train["y"].device
+    device = Xy_train["depth" if depth_crit is not None else "y"].device
     dec_params = list(decoder.parameters())
     pack_memo = F.PackMemo()
     n_pixels = batch_size * int(feat.shape[2]) * int(feat.shape[3]) * 16
     fused_kd = do_kd and segm_crit is None and native_kd(kd_crit, Xy_train.get("kd_y"), out_size)
     extra = {} if segm_crit is None else {"segm_crit": segm_crit}
+    if depth_crit is not None:
+        if "depth" not in Xy_train or do_kd or segm_crit is not None:
+            raise ValueError("make_task0_step: depth_crit needs a depth cache (populate_task0(task=\"depth\")) and "
+                             "goes with neither distillation nor a segmentation criterion")
+        extra = {"depth_crit": depth_crit}
     if (not do_kd or fused_kd) and _replays(segmenter, device, n_pixels):
         stepper = _task0_stepper(Xy_train, segmenter, optim_dec, batch_size, ignore_index, dec_grad_clip,
                                  aux_weight, kd_coeff if fused_kd else None, **extra)
@@ -419,8 +455,11 @@ def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255
             check_cache_rows(idx, Xy_train, "train_task0")
             idx = idx.to(device, non_blocking=True)
             with F.packed_once(pack_memo):  # (one weight re-pack launch per step)
-                loss = task0_loss(Xy_train, idx, decoder, ignore_index, aux_weight, kd_coeff if do_kd else None,
-                                  kd_crit, fused_kd, **extra)
+                if depth_crit is not None:
+                    loss = task0_depth_loss(Xy_train, idx, decoder, depth_crit, aux_weight)
+                else:
+                    loss = task0_loss(Xy_train, idx, decoder, ignore_index, aux_weight, kd_coeff if do_kd else None,
+                                      kd_crit, fused_kd, **extra)
                 _zero_grads(segmenter, (optim_dec,))
                 with F.deferred_wgrad(params=dec_params, second_stream=False):  # (crops of the feature cache: launch-bound)
                     loss.backward()
@@ -438,11 +477,20 @@ def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255
 def train_task0(Xy_train, segmenter, optim_dec, epoch, segm_crit, kd_crit, batch_size, freeze_bn,
                 do_kd, kd_coeff, dec_grad_clip, do_polyak, avg_param=None, polyak_decay=0.9,
                 aux_weight=0):
-    """Decoder-only epoch over the cached encoder features (trainer.py:78-175)."""
-    if _depth_crit(segm_crit) is not None:
-        raise ValueError("train_task0: depth candidates are trained end to end only (train_segmenter) - the task0 "
-                         "cache holds class labels, not depth maps")
-    if getattr(segm_crit, "full_size", False):
+    """Decoder-only epoch over the cached encoder features (trainer.py:78-175).
+    An nn.BerHuLoss on a cache with a 'depth' entry (populate_task0(task="depth")): the decoder-only DEPTH epoch."""
+    depth_crit = _depth_crit(segm_crit)
+    depth_cache = "depth" in Xy_train
+    if depth_crit is not None and not depth_cache:
+        raise ValueError("train_task0: on this cache depth candidates are trained end to end only (train_segmenter) - "
+                         "it holds class labels, not depth maps; populate_task0(..., task=\"depth\") makes the cache "
+                         "of full-size depth maps a BerHuLoss trains the decoder on")
+    if depth_cache and depth_crit is None:
+        raise ValueError("train_task0: a depth cache (populate_task0(task=\"depth\")) needs an nn.BerHuLoss as "
+                         "segm_crit (got {!r})".format(segm_crit))
+    if depth_cache and do_kd:
+        raise ValueError("train_task0: there is no distillation term for depth (do_kd with a depth cache)")
+    if depth_crit is None and getattr(segm_crit, "full_size", False):
         raise ValueError("train_task0: a full-size criterion (SegmCrossEntropy(full_size=True)) is for the end-to-end "
                          "step only (train_segmenter) - the task0 cache holds labels at the logits' size")
     decoder = _inner(segmenter).decoder
@@ -459,7 +507,8 @@ def train_task0(Xy_train, segmenter, optim_dec, epoch, segm_crit, kd_crit, batch
     np.random.shuffle(indices)
     step = make_task0_step(Xy_train, segmenter, optim_dec, batch_size, _ignore_index(segm_crit), dec_grad_clip,
                            aux_weight, freeze_bn, do_kd, kd_coeff, kd_crit,
-                           _segm_crit(segm_crit, Xy_train["y"].device))
+                           None if depth_cache else _segm_crit(segm_crit, Xy_train["y"].device),
+                           **({"depth_crit": depth_crit} if depth_cache else {}))
     for i in range(n_passes):
         start = time.time()
         syncs = _syncs(segmenter)

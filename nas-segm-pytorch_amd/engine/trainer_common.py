@@ -94,13 +94,13 @@ def task1_depth_loss(segmenter, image, target, crit, aux_weight):
 
 def cache_feature_keys(cache):
     """the encoder-feature entries of the task0 cache (engine/trainer.py: populate_task0)"""
-    return [k for k in cache.keys() if k not in ("y", "kd_y", "out_size")]
+    return [k for k in cache.keys() if k not in ("y", "depth", "kd_y", "out_size")]
 
 
 def check_cache_rows(idx, cache, caller):
     """the reference's Xy_train[k][train_idx] raises here (src/engine/trainer.py:132-137); the gather kernel's
     clamp is a memory-safety net only"""
-    n_rows = int(cache["y"].shape[0])
+    n_rows = int(cache["y" if "y" in cache else "depth"].shape[0])
     if not idx.is_cuda and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n_rows):
         raise IndexError("{}: cache row index out of range [0, {})".format(caller, n_rows))
 
@@ -128,3 +128,19 @@ def task0_loss(cache, index, decoder, ignore_index, aux_weight, kd_coeff=None, k
             kd_y = kd_y if kd_y is not None else F.gather_rows(cache["kd_y"], index)
             loss = loss + kd_coeff * kd_crit(output, kd_y)
     return segmentation_loss(output, aux_outs, target, ignore_index, aux_weight, loss, segm_crit)
+
+
+def task0_depth_loss(cache, index, decoder, crit, aux_weight):
+    """forward + loss of the decoder-only DEPTH step on the cache rows ``index`` (an int64 device tensor): gather the
+    feature rows, decoder, ``crit`` (nn.BerHuLoss) of the main head + aux_weight * that of every auxiliary head when
+    aux_weight > 0 - ``depth_loss`` with the targets left where they are: the kernels read image b's full-size map
+    from ``cache["depth"]`` through ``index``, so no head is resized and no gathered target is written (with
+    ``full_size=True`` the heads are up-sampled inside the kernels)."""
+    feats = [F.gather_rows(cache[k], index) for k in cache_feature_keys(cache)]
+    output, aux_outs = _heads(decoder(feats))
+    depth = cache["depth"]
+    loss = crit(output, depth, rows=index)
+    if aux_weight > 0:
+        for aux_out in aux_outs:
+            loss = loss + crit(aux_out, depth, rows=index) * aux_weight
+    return loss

@@ -2981,14 +2981,39 @@ def berhu_loss(pred, target):
     return _BerHu.apply(pred, target)
 
 
+def _cache_rows(who, pred, target, rows):
+    """the checks of ``rows=``: ``target`` is a cache (N, H, W), fp32 and contiguous as it stands - it is never
+    copied -, ``rows`` an int64 device tensor of one cache row per image of ``pred``.  An index that can be read
+    without a synchronisation (a host tensor) is checked against [0, N) before it is refused for being on the host;
+    on the device the kernels clamp (a memory-safety net, as in ``gather_rows``).  Returns N."""
+    if not torch.is_tensor(rows) or rows.dtype != torch.int64 or rows.dim() != 1 or not rows.is_contiguous():
+        raise NassegError("{}: rows must be a contiguous 1-D int64 tensor".format(who))
+    if not torch.is_tensor(target) or target.dtype != torch.float32 or target.dim() != 3 or target.shape[0] < 1:
+        raise NassegError("{}: with rows, the target must be an fp32 cache of shape (N, H, W) (got {} {})".format(
+            who, getattr(target, "dtype", None), tuple(getattr(target, "shape", ()))))
+    n_rows = int(target.shape[0])
+    if rows.shape[0] != pred.shape[0]:
+        raise NassegError("{}: one cache row per image expected ({} rows for {} images)".format(
+            who, rows.shape[0], pred.shape[0]))
+    if not rows.is_cuda and rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n_rows):
+        raise IndexError("{}: cache row index out of range [0, {})".format(who, n_rows))
+    require_device(pred, target, rows)
+    if not target.is_contiguous():
+        raise NassegError("{}: with rows, the target cache must be contiguous (it is read in place)".format(who))
+    return n_rows
+
+
 class _BerHuMasked(torch.autograd.Function):
+    """nasseg_berhu_masked_fwd / _bwd; with ``rows`` their row-indexed twins on the cache ``target``"""
+
     @staticmethod
-    def forward(ctx, pred, target, valid_min, valid_max):
+    def forward(ctx, pred, target, valid_min, valid_max, rows=None):
+        n_rows = None if rows is None else _cache_rows("berhu_loss_masked", pred, target, rows)
         require_device(pred, target)
         if pred.dtype not in (torch.float32, torch.bfloat16) or pred.dim() != 4 or pred.shape[1] != 1:
             raise NassegError("berhu_loss_masked: the prediction must be fp32 or bf16 of shape (B, 1, h, w) (got {} {})"
                               .format(pred.dtype, tuple(pred.shape)))
-        if target.dtype != torch.float32 or target.dim() != 3 or target.shape[0] != pred.shape[0]:
+        if target.dtype != torch.float32 or target.dim() != 3 or (rows is None and target.shape[0] != pred.shape[0]):
             raise NassegError("berhu_loss_masked: the target must be fp32 of shape (B, H, W) (got {} {})".format(
                 target.dtype, tuple(target.shape)))
         p, t = pred.contiguous(), target.contiguous()  # (one channel: NCHW and NHWC are the same memory)
@@ -2997,8 +3022,14 @@ class _BerHuMasked(torch.autograd.Function):
         cfg = (B, h, w, H, W, float(valid_min), float(valid_max))
         out = _vec(p, 3)
         ws = _ws(p, lib.query("nasseg_berhu_masked_workspace"))
-        lib.call(_k("nasseg_berhu_masked_fwd", p), ptr(p), ptr(t), *cfg, ptr(out), ptr(ws), current_stream())
-        ctx.save_for_backward(p, t, out)
+        if rows is None:
+            lib.call(_k("nasseg_berhu_masked_fwd", p), ptr(p), ptr(t), *cfg, ptr(out), ptr(ws), current_stream())
+            ctx.save_for_backward(p, t, out)
+        else:
+            lib.call(_k("nasseg_berhu_masked_rows_fwd", p), ptr(p), ptr(t), ptr(rows), n_rows, *cfg, ptr(out), ptr(ws),
+                     current_stream())
+            ctx.save_for_backward(p, t, out, rows)
+        ctx.n_rows = n_rows
         ctx.cfg = cfg
         # The loss is out[0] under a tensor of its own, not a view of ``out``: a caller may update it in place
         # (``loss += aux_weight * aux_loss``, the reference's idiom) - autograd refuses that on a view made inside a
@@ -3009,23 +3040,32 @@ class _BerHuMasked(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        p, t, out = ctx.saved_tensors
+        p, t, out = ctx.saved_tensors[:3]
         g = g.to(torch.float32).contiguous().view(1)
         d = torch.empty_like(p)
-        lib.call(_k("nasseg_berhu_masked_bwd", p), ptr(p), ptr(t), ptr(out), ptr(g), *ctx.cfg, ptr(d),
-                 current_stream())
-        return d, None, None, None
+        if ctx.n_rows is None:
+            lib.call(_k("nasseg_berhu_masked_bwd", p), ptr(p), ptr(t), ptr(out), ptr(g), *ctx.cfg, ptr(d),
+                     current_stream())
+            return d, None, None, None
+        lib.call(_k("nasseg_berhu_masked_rows_bwd", p), ptr(p), ptr(t), ptr(ctx.saved_tensors[3]), ctx.n_rows, ptr(out),
+                 ptr(g), *ctx.cfg, ptr(d), current_stream())
+        return d, None, None, None, None
 
 
-def berhu_loss_masked(pred, target, valid_min=0.0, valid_max=float("inf")):
+def berhu_loss_masked(pred, target, valid_min=0.0, valid_max=float("inf"), rows=None):
     """Reverse-Huber loss of a depth head against a full-size target with holes (absent from the reference).
 
     pred (B, 1, h, w) fp32 or bf16, target (B, H, W) fp32 at ANY size: prediction pixel (y, x) is compared with the
     target pixel ``F.interpolate(mode="nearest")`` would put there (never written anywhere).  A pixel counts iff its
     target t is finite and ``valid_min < t <= valid_max``; d = |pred - t|, c = 0.2 * max d (a constant in backward),
     loss = mean over valid pixels of (d if d <= c else (d^2 + c^2) / (2c)); no valid pixel: loss 0, gradient 0.
-    Returns a 0-dim tensor that may be updated in place.  No host synchronisation: capturable."""
-    return _BerHuMasked.apply(pred, target, valid_min, valid_max)
+    Returns a 0-dim tensor that may be updated in place.  No host synchronisation: capturable.
+    ``rows`` (an int64 device tensor of B entries): ``target`` is a cache (N, H, W), fp32 and contiguous, and image b
+    meets ``target[rows[b]]`` - read in place by the kernels, bit for bit the call on the gathered ``target[rows]``,
+    which is never made (the task0 depth cache, engine/trainer.py).  Repeated and unordered rows are legal."""
+    if rows is None:
+        return _BerHuMasked.apply(pred, target, valid_min, valid_max)
+    return _BerHuMasked.apply(pred, target, valid_min, valid_max, rows)
 
 
 class _BerHuUpsampled(torch.autograd.Function):
@@ -3033,12 +3073,13 @@ class _BerHuUpsampled(torch.autograd.Function):
     (0-dim, fp32).  ``group``: the backward's lanes per prediction pixel (0: from the shapes)"""
 
     @staticmethod
-    def forward(ctx, pred, target, valid_min, valid_max, group):
+    def forward(ctx, pred, target, valid_min, valid_max, group, rows=None):
+        n_rows = None if rows is None else _cache_rows("berhu_loss_upsampled", pred, target, rows)
         require_device(pred, target)
         if pred.dtype not in (torch.float32, torch.bfloat16) or pred.dim() != 4 or pred.shape[1] != 1:
             raise NassegError("berhu_loss_upsampled: the prediction must be fp32 or bf16 of shape (B, 1, h, w) "
                               "(got {} {})".format(pred.dtype, tuple(pred.shape)))
-        if target.dtype != torch.float32 or target.dim() != 3 or target.shape[0] != pred.shape[0]:
+        if target.dtype != torch.float32 or target.dim() != 3 or (rows is None and target.shape[0] != pred.shape[0]):
             raise NassegError("berhu_loss_upsampled: the target must be fp32 of shape (B, H, W) (got {} {})".format(
                 target.dtype, tuple(target.shape)))
         p, t = pred.contiguous(), target.contiguous()  # (one channel: NCHW and NHWC are the same memory)
@@ -3051,8 +3092,14 @@ class _BerHuUpsampled(torch.autograd.Function):
         cfg = (B, h, w, H, W, float(valid_min), float(valid_max))
         out = _vec(p, 3)
         ws = _ws(p, n_ws)
-        lib.call(_k("nasseg_berhu_up_fwd", p), ptr(p), ptr(t), *cfg, ptr(out), ptr(ws), current_stream())
-        ctx.save_for_backward(p, t, out)
+        if rows is None:
+            lib.call(_k("nasseg_berhu_up_fwd", p), ptr(p), ptr(t), *cfg, ptr(out), ptr(ws), current_stream())
+            ctx.save_for_backward(p, t, out)
+        else:
+            lib.call(_k("nasseg_berhu_up_rows_fwd", p), ptr(p), ptr(t), ptr(rows), n_rows, *cfg, ptr(out), ptr(ws),
+                     current_stream())
+            ctx.save_for_backward(p, t, out, rows)
+        ctx.n_rows = n_rows
         ctx.cfg = cfg + (int(group),)
         # (the loss under a tensor of its own, as _BerHuMasked.forward returns it: it may be updated in place;
         #  backward reads out[1], out[2] only)
@@ -3062,14 +3109,18 @@ class _BerHuUpsampled(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, *unused):
-        p, t, out = ctx.saved_tensors
+        p, t, out = ctx.saved_tensors[:3]
         g = g.to(torch.float32).contiguous().view(1)
         d = torch.empty_like(p)
-        lib.call(_k("nasseg_berhu_up_bwd", p), ptr(p), ptr(t), ptr(out), ptr(g), *ctx.cfg, ptr(d), current_stream())
-        return d, None, None, None, None
+        if ctx.n_rows is None:
+            lib.call(_k("nasseg_berhu_up_bwd", p), ptr(p), ptr(t), ptr(out), ptr(g), *ctx.cfg, ptr(d), current_stream())
+            return d, None, None, None, None
+        lib.call(_k("nasseg_berhu_up_rows_bwd", p), ptr(p), ptr(t), ptr(ctx.saved_tensors[3]), ctx.n_rows, ptr(out),
+                 ptr(g), *ctx.cfg, ptr(d), current_stream())
+        return d, None, None, None, None, None
 
 
-def berhu_loss_upsampled(pred, target, valid_min=0.0, valid_max=float("inf"), return_parts=False):
+def berhu_loss_upsampled(pred, target, valid_min=0.0, valid_max=float("inf"), return_parts=False, rows=None):
     """``berhu_loss_masked`` taken at the TARGET's size: the reverse-Huber loss of a depth head whose prediction is
     up-sampled bilinearly (align_corners=False) to the (B, H, W) target inside the kernels ("Depth").
 
@@ -3081,8 +3132,13 @@ def berhu_loss_upsampled(pred, target, valid_min=0.0, valid_max=float("inf"), re
     gathered straight into the prediction's shape (exact zeros where no valid target pixel reaches a prediction
     pixel), without atomics - the same inputs give the same bits.
     Returns a 0-dim tensor that may be updated in place; ``return_parts``: (loss, c, n_valid), all 0-dim fp32.
-    No host synchronisation: capturable."""
-    out = _BerHuUpsampled.apply(pred, target, valid_min, valid_max, 0)
+    No host synchronisation: capturable.
+    ``rows``: as in ``berhu_loss_masked`` - ``target`` is a cache (N, H, W) read in place through the B cache rows;
+    B*H*W < 2^32 bounds the batch, the cache may be larger."""
+    if rows is None:
+        out = _BerHuUpsampled.apply(pred, target, valid_min, valid_max, 0)
+    else:
+        out = _BerHuUpsampled.apply(pred, target, valid_min, valid_max, 0, rows)
     return out if return_parts else out[0]
 
 

@@ -27,9 +27,13 @@ class BerHuLoss(nn.Module):
         the two bounds, which are kernel arguments"""
         return ("berhu_up" if self.full_size else "berhu", self.valid_min, self.valid_max)
 
-    def forward(self, pred, target):
+    def forward(self, pred, target, rows=None):
+        """``rows`` (an int64 device tensor, one entry per image): ``target`` is a cache (N, H, W) and image b meets
+        ``target[rows[b]]``, read in place (the task0 depth cache)"""
         loss = F.berhu_loss_upsampled if self.full_size else F.berhu_loss_masked
-        return loss(pred, target, self.valid_min, self.valid_max)
+        if rows is None:
+            return loss(pred, target, self.valid_min, self.valid_max)
+        return loss(pred, target, self.valid_min, self.valid_max, rows=rows)
 
     def extra_repr(self):
         s = "valid_min={}, valid_max={}".format(self.valid_min, self.valid_max)
