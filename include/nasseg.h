@@ -711,6 +711,59 @@ int nasseg_optim_step(const int64_t* tensors, int n_tensors, const int* chunks, 
 int nasseg_polyak(const int64_t* tensors, int n_tensors, const int* chunks, int n_chunks, float decay, float alpha,
                   void* stream);
 
+/* ---- the search controller: src/rl/micro_controllers.py (MicroController.forward :148-265, TemplateController.forward
+ * :442-571, evaluate_actions :267-274 / :573-580), sampling and log-probabilities of src/rl/utils.py:7-27, the PPO
+ * surrogate of src/rl/gradient_estimators.py:170-187 (REINFORCE :42-57 needs the rollout and its backward only).
+ * In both controllers the LSTM's next input is its own previous output and enc_op is never read, so every step's
+ * distribution is independent of the actions: B action rows are ONE T-step rollout plus B T gathers, n samples one
+ * rollout plus n T inverse-CDF look-ups.  fp32 only; the dependent chain runs in one workgroup; no atomics: results
+ * repeat bit for bit, host-launched or replayed from a hipGraph.
+ *   params   DEVICE int64 [1 + 4L + 2 n_heads] addresses, torch's own layouts (nothing is re-packed): g_emb (H);
+ *            per LSTM layer k weight_ih_l{k} (4H, H), weight_hh_l{k} (4H, H), bias_ih_l{k}, bias_hh_l{k} (4H), gates
+ *            i, f, g, o; per head its Linear's weight (n, H) and bias (n).
+ *   steps    DEVICE int32 [T][3] = {head (-1: a warm-up step, the enc_num_layers loop), choices n, position of the
+ *            step's action in an action row (-1: none)}; the kernels clamp n to max_choices and ignore heads >=
+ *            n_heads and positions >= A.
+ *   actions  DEVICE int32 [n_rows][A]; rows DEVICE int32 [B] picks the B rows to evaluate (null: rows 0..B-1); row
+ *            indices and actions are clamped into range.  B = 0: no log-probabilities.
+ *   u        DEVICE fp32 [n_samples][T] uniforms in [0, 1) (null with n_samples = 0): sampled int32 [n_samples][A]
+ *            receives, at every step's position, the first index i with u < p_0 + .. + p_i (the CDF accumulated in
+ *            ascending order, the last index catches the rest); positions without a step are set to 0.  sampled_lp
+ *            [n_samples]: their log-probabilities, the sums nasseg_ctrl_rollout's log_prob gives for those rows.
+ *   saved    DEVICE fp32 [nasseg_ctrl_saved_floats(T, H, L)], written for nasseg_ctrl_backward: activated gates, cell
+ *            states, layer outputs, per-step probabilities / log-probabilities / centred logits.
+ *   entropy  DEVICE fp32 [1] = sum_t -sum_i p log p (a head with one choice adds 0); log_prob [B] = sum_t
+ *            log p_t[a[b, t]], t ascending.
+ * Limits (refused with NASSEG_ERR_ARG): H <= 256, L <= 4, T <= 128, max_choices <= 64, n_heads <= 64, B <= 1024,
+ * n_samples <= 1024.
+ * nasseg_ctrl_backward: from d_log_prob [B] (null: zeros) and d_entropy [1] (null: zero),
+ *   dlogits_t = sum_b d_log_prob[b] (onehot(a[b, t]) - p_t) + d_entropy (-p_t (log p_t + H_t)), b ascending,
+ * (log p_t + H_t taken as the logits centred on their mean under p_t, which the rollout saved: no cancellation),
+ * back through the heads, the layers and time (layer 0's input at t + 1 is the top layer's output at t) in one
+ * workgroup, then the parameter gradients in a second launch, one thread per element, t ascending: grads + gtab[e][0]
+ * receives entry e's gradient, laid out like the parameter; gtab DEVICE int32 [1 + 4L + 2 n_heads][2] = {offset in
+ * floats, rows (heads: n)}.  bias_ih and bias_hh receive the same sums; g_emb layer 0's input gradient at t = 0.
+ * work: DEVICE fp32 [nasseg_ctrl_work_floats(T, H, L)].
+ * nasseg_ctrl_ppo_seed: log_prob [B] against old_log_prob / adv [n_rows] at rows[B] (null: 0..B-1).  As the reference
+ * subtracts a (B, 1) array from a (B,) tensor, ratio_ij = exp(log_prob[j] - old[i]) over B x B pairs (B = 1, the
+ * search's setting: the usual formula): action_loss = -mean_ij min(ratio_ij adv_i, clamp(ratio_ij, clip_lo, clip_hi)
+ * adv_i); acc[0] += action_loss, acc[1] += entropy[0]; d_log_prob [B] and d_entropy [1] = -entropy_coef are the
+ * gradients of action_loss - entropy_coef entropy (min and clamp pass gradients as torch's do: a tie splits, the
+ * clamp's bounds are inside). */
+int64_t nasseg_ctrl_saved_floats(int T, int H, int L);
+int64_t nasseg_ctrl_work_floats(int T, int H, int L);
+int nasseg_ctrl_rollout(const int64_t* params, const int* steps, int T, int H, int L, int n_heads, int max_choices,
+                        const int* actions, const int* rows, int n_rows, int B, int A, const float* u, int n_samples,
+                        int* sampled, float* sampled_lp, float* saved, float* entropy, float* log_prob,
+                        void* stream);
+int nasseg_ctrl_backward(const int64_t* params, const int* steps, int T, int H, int L, int n_heads, int max_choices,
+                         const int* actions, const int* rows, int n_rows, int B, int A, const float* d_log_prob,
+                         const float* d_entropy, const float* saved, float* work, const int* gtab, float* grads,
+                         void* stream);
+int nasseg_ctrl_ppo_seed(const float* log_prob, const float* entropy, const float* old_log_prob, const float* adv,
+                         const int* rows, int n_rows, int B, float clip_lo, float clip_hi, float entropy_coef,
+                         float* acc, float* d_log_prob, float* d_entropy, void* stream);
+
 /* ---- hipGraph scheduling of a captured step (reference src/nn/micro_decoders.py:54-139: the five
  * ops of a ContextualCell read one input, the two cells of a MergeCell share nothing) ---------------------------------
  * A step recorded from one stream is a line of nodes.  The host side (engine/graph_dag.py) knows from this header

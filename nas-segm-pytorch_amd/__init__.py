@@ -9,7 +9,7 @@ from . import functional  # noqa: F401
 from ._lib import NassegError, lib  # noqa: F401
 
 
-def install_dropin(kd=False, data=False, data_on_device=False):
+def install_dropin(kd=False, data=False, data_on_device=False, controller=False):
     """Register this package under the module names the reference's own scripts
     import (``nn.layer_factory``, ``nn.micro_decoders``, ``nn.encoders``,
     ``rl.genotypes``, ``helpers.miou_utils``, ``engine.trainer``,
@@ -21,6 +21,9 @@ def install_dropin(kd=False, data=False, data_on_device=False):
     its resizes are restatements whose parity with cv2 is NOT pinned.
     data_on_device=True maps them too, but ``data.loaders.create_loaders`` then resolves to
     data/device.py: the same batches, augmented on the GPU (fp32 images already on the device).
+    controller=True maps ``rl.micro_controllers``, ``rl.agent``, ``rl.gradient_estimators`` and ``helpers.storage``
+    onto the native search controller (rl/, csrc/controller.hip): the reference's ``from rl.agent import create_agent,
+    train_agent`` (src/main_search.py:37) then runs the LSTM rollout, its backward and PPO on the device.
     See INTEGRATION.md."""
     import sys
 
@@ -50,6 +53,12 @@ def install_dropin(kd=False, data=False, data_on_device=False):
         from .data import datasets, device
 
         table.update({"data": data_pkg, "data.datasets": datasets, "data.loaders": device})
+    if controller:
+        from .helpers import storage
+        from .rl import agent, gradient_estimators, micro_controllers
+
+        table.update({"rl": rl, "helpers": helpers, "rl.micro_controllers": micro_controllers, "rl.agent": agent,
+                      "rl.gradient_estimators": gradient_estimators, "helpers.storage": storage})
     for name, mod in table.items():
         sys.modules[name] = mod
     # `rl`, `helpers`, `engine` keep the reference's other submodules importable:

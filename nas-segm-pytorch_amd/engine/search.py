@@ -1,7 +1,8 @@
-"""Candidate evaluation for the NAS outer loop (BASELINE config 4): the controller stays
-on the host (rank 0) and samples genotypes; every sampled decoder is built, trained for a
-few steps and validated on ONE GPU, several candidates in parallel one per rank, and the
-rewards are gathered back to rank 0 where ``train_agent`` consumes them
+"""Candidate evaluation for the NAS outer loop (BASELINE config 4): the controller lives on
+rank 0 (rl/: on that rank's GPU; the reference's own: on the host) and samples genotypes;
+every sampled decoder is built, trained for a few steps and validated on ONE GPU, several
+candidates in parallel one per rank, and the rewards are gathered back to rank 0 where
+``train_agent`` consumes them
 (src/main_search.py:490-513,543-660; src/rl/agent.py:73-77).  No gradient exchange is
 needed in this mode - candidates are independent.
 """

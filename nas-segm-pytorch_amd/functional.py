@@ -3611,6 +3611,173 @@ def prepare_image(img, dtype=torch.float32, plan=None):
     return image
 
 
+# -- the search controller (csrc/controller.hip) ---------------------------------------------------------------------
+class ControllerPlan(object):
+    """What the controller kernels need to know about a controller, built once per module (rl/micro_controllers.py):
+    ``steps`` = [(head index or -1, choices, position in an action row or -1)] per LSTM step, ``head_rows`` = choices
+    per head.  Parameters are handed to the calls as a list in TABLE ORDER - g_emb, then weight_ih / weight_hh /
+    bias_ih / bias_hh per LSTM layer, then weight and bias per head - and reach the kernels as a device table of their
+    addresses: the table is rebuilt when an address changes, the values are never copied, so nothing goes stale after
+    an optimiser step.  A hipGraph captured around these calls has the table's and the parameters' addresses baked in:
+    it is valid as long as the parameters stay where they are (in-place updates, as optimisers make them), and has to
+    be captured again after they were re-allocated (``.to()``,
+    ``load_state_dict(assign=True)``).  Gradients come back as slices of one flat buffer laid out by ``offsets``."""
+
+    def __init__(self, steps, hidden, layers, head_rows, action_len):
+        self.steps = [tuple(int(v) for v in s) for s in steps]
+        self.T, self.H, self.L, self.A = len(self.steps), int(hidden), int(layers), int(action_len)
+        self.head_rows = [int(n) for n in head_rows]
+        self.NH = len(self.head_rows)
+        self.maxn = max(self.head_rows) if self.head_rows else 0
+        H = self.H
+        self.shapes = [(H,)] + [s for _ in range(self.L) for s in ((4 * H, H), (4 * H, H), (4 * H,), (4 * H,))]
+        self.shapes += [s for n in self.head_rows for s in ((n, H), (n,))]
+        self.numels = [int(np.prod(s)) for s in self.shapes]
+        self.offsets, off = [], 0
+        for n in self.numels:
+            self.offsets.append(off)
+            off += (n + 3) // 4 * 4  # (every slice 16-byte aligned)
+        self.total = off
+        self._static = {}  # device -> (steps, gtab)
+        self._ptab = {}    # device -> (addresses, table)
+
+    def tables(self, params):
+        """(parameter addresses, step table, gradient table) on the parameters' device"""
+        if len(params) != len(self.shapes):
+            raise NassegError("controller: {} parameters for a table of {}".format(len(params), len(self.shapes)))
+        require_device(*params)
+        for p, shape in zip(params, self.shapes):
+            if p.dtype != torch.float32 or p.numel() != int(np.prod(shape)) or not p.is_contiguous():
+                raise NassegError("controller: parameters must be contiguous fp32 of {} elements (got {} {})".format(
+                    int(np.prod(shape)), p.dtype, tuple(p.shape)))
+        dev = params[0].device
+        if any(p.device != dev for p in params):
+            raise NassegError("controller: parameters on several devices")
+        static = self._static.get(dev)
+        if static is None:
+            rows = [1] + [4 * self.H] * (4 * self.L) + [n for n in self.head_rows for _ in (0, 1)]
+            static = (torch.tensor(self.steps, dtype=torch.int32, device=dev).reshape(-1, 3).contiguous(),
+                      torch.tensor(list(zip(self.offsets, rows)), dtype=torch.int32, device=dev).contiguous())
+            self._static[dev] = static
+        key = tuple(p.data_ptr() for p in params)
+        ent = self._ptab.get(dev)
+        if ent is None or ent[0] != key:
+            ent = (key, torch.tensor(key, dtype=torch.int64, device=dev))
+            self._ptab[dev] = ent
+        return ent[1], static[0], static[1]
+
+    def dims(self):
+        return (self.T, self.H, self.L, self.NH, self.maxn)
+
+    def split(self, flat):
+        """the parameters' gradients: slices of the flat buffer, in table order"""
+        return [flat[o:o + n].view(s) for o, n, s in zip(self.offsets, self.numels, self.shapes)]
+
+
+def _ctrl_rows(plan, actions, rows):
+    """(actions, rows, n_rows, B) as the kernels take them"""
+    if actions is None:
+        return None, None, 0, 0
+    if actions.dtype != torch.int32 or actions.dim() != 2 or actions.shape[1] != plan.A or not actions.is_contiguous():
+        raise NassegError("controller: actions must be a contiguous int32 (rows, {}) tensor (got {} {})".format(
+            plan.A, actions.dtype, tuple(actions.shape)))
+    require_device(actions, rows)
+    if rows is not None and (rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_contiguous()):
+        raise NassegError("controller: rows must be a contiguous int32 vector")
+    n_rows = int(actions.shape[0])
+    return actions, rows, n_rows, (n_rows if rows is None else int(rows.shape[0]))
+
+
+def controller_forward(plan, params, actions=None, rows=None, u=None):
+    """One nasseg_ctrl_rollout launch, no autograd: -> (entropy (), log_prob (B,), saved, sampled (n, A) int32 or None,
+    sampled log_prob (n,) or None).  ``saved`` is what ``controller_backward`` reads."""
+    ptab, steps, _ = plan.tables(params)
+    actions, rows, n_rows, B = _ctrl_rows(plan, actions, rows)
+    like = params[0]
+    T, H, L, NH, maxn = plan.dims()
+    n, sampled, sampled_lp = 0, None, None
+    if u is not None:
+        require_device(u)
+        if u.dtype != torch.float32 or u.dim() != 2 or u.shape[1] != T or not u.is_contiguous():
+            raise NassegError("controller: uniforms must be a contiguous fp32 (n, {}) tensor".format(T))
+        n = int(u.shape[0])
+        sampled = torch.empty((n, plan.A), device=like.device, dtype=torch.int32)
+        sampled_lp = torch.empty((n,), device=like.device, dtype=torch.float32)
+    saved = _ws(like, lib.query("nasseg_ctrl_saved_floats", T, H, L))
+    entropy = _scalar(like)
+    log_prob = torch.empty((B,), device=like.device, dtype=torch.float32)
+    lib.call("nasseg_ctrl_rollout", ptr(ptab), ptr(steps), T, H, L, NH, maxn, ptr(actions), ptr(rows), n_rows, B,
+             plan.A, ptr(u), n, ptr(sampled), ptr(sampled_lp), ptr(saved), ptr(entropy),
+             ptr(log_prob) if B else None, current_stream())
+    return entropy, log_prob, saved, sampled, sampled_lp
+
+
+def controller_backward(plan, params, saved, actions, rows, d_log_prob, d_entropy, flat=None, work=None):
+    """The two nasseg_ctrl_backward launches (the chain in one workgroup, then the parameter gradients), no autograd:
+    writes every parameter's gradient into ``flat`` (plan.total floats, made when None) and returns it."""
+    ptab, steps, gtab = plan.tables(params)
+    actions, rows, n_rows, B = _ctrl_rows(plan, actions, rows)
+    T, H, L, NH, maxn = plan.dims()
+    if flat is None:
+        flat = _ws(params[0], plan.total)
+    if work is None:
+        work = _ws(params[0], lib.query("nasseg_ctrl_work_floats", T, H, L))
+    lib.call("nasseg_ctrl_backward", ptr(ptab), ptr(steps), T, H, L, NH, maxn, ptr(actions), ptr(rows), n_rows, B,
+             plan.A, ptr(d_log_prob) if B else None, ptr(d_entropy), ptr(saved), ptr(work), ptr(gtab), ptr(flat),
+             current_stream())
+    return flat
+
+
+class _ControllerRollout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, actions, rows, *params):
+        entropy, log_prob, saved, _, _ = controller_forward(plan, params, actions, rows)
+        ctx.plan = plan
+        ctx.save_for_backward(saved, actions, rows, *params)
+        return entropy, log_prob
+
+    @staticmethod
+    def backward(ctx, g_ent, g_lp):
+        saved, actions, rows = ctx.saved_tensors[:3]
+        params = ctx.saved_tensors[3:]
+        plan = ctx.plan
+        if g_ent is not None:
+            g_ent = g_ent.to(torch.float32).contiguous()
+        if g_lp is not None:
+            g_lp = g_lp.to(torch.float32).contiguous()
+        flat = controller_backward(plan, params, saved, actions if g_lp is not None else None,
+                                   rows if g_lp is not None else None, g_lp, g_ent)
+        grads = plan.split(flat)
+        return (None, None, None) + tuple(g.view_as(p) if need else None
+                                           for g, p, need in zip(grads, params, ctx.needs_input_grad[3:]))
+
+
+def controller_rollout(plan, params, actions=None, rows=None):
+    """The controller's T-step rollout as ONE autograd node: -> (entropy, log_probs) - the total entropy of the
+    steps' distributions (0-dim) and, for the B action rows ``actions[rows]`` (int32 (n_rows, A); rows None: all of
+    them; actions None: B = 0), log_probs (B,).  Backward: the two nasseg_ctrl_backward launches.  Both results are
+    tensors of their own (``loss += ...`` on them works)."""
+    return _ControllerRollout.apply(plan, actions, rows, *params)
+
+
+def controller_sample(plan, params, u):
+    """Sample u.shape[0] candidates from ONE rollout by inverse CDF of the uniforms u (n, T): -> (actions int32 (n, A),
+    log_probs (n,), entropy ()); no autograd."""
+    with torch.no_grad():
+        entropy, _, _, sampled, sampled_lp = controller_forward(plan, [p.detach() for p in params], u=u)
+    return sampled, sampled_lp, entropy
+
+
+def controller_ppo_seed(log_prob, entropy, old_log_prob, adv, rows, clip_param, entropy_coef, acc, d_log_prob,
+                        d_entropy):
+    """The PPO surrogate on the device (nasseg_ctrl_ppo_seed): adds action_loss and entropy to ``acc`` (2,) and
+    writes the gradients of action_loss - entropy_coef * entropy into d_log_prob (B,) and d_entropy ()."""
+    require_device(log_prob, entropy, old_log_prob, adv, rows, acc, d_log_prob, d_entropy)
+    lib.call("nasseg_ctrl_ppo_seed", ptr(log_prob), ptr(entropy), ptr(old_log_prob), ptr(adv), ptr(rows),
+             int(old_log_prob.numel()), int(log_prob.numel()), float(1.0 - clip_param), float(1.0 + clip_param),
+             float(entropy_coef), ptr(acc), ptr(d_log_prob), ptr(d_entropy), current_stream())
+
+
 def _apply_library_knobs():
     if _PW_MIN_PIXELS is not None:
         lib.query("nasseg_conv_pw_min_pixels", int(_PW_MIN_PIXELS))
