@@ -659,6 +659,61 @@ int nasseg_berhu_up_rows_bwd(const float* pred, const float* target, const int64
                              const float* stats, const float* gscale, int B, int h, int w, int H, int W,
                              float valid_min, float valid_max, int group, float* dpred, void* stream);
 
+/* Depth terms: the scale-invariant log term (Eigen et al. 2014, eq. 4, without a square root) and the multi-scale
+ * gradient-matching term (MegaDepth, Li & Snavely 2018; MiDaS, Ranftl et al. 2020) on top of the masked berHu - the
+ * surrogates of what validate_depth (nasseg_depth_metrics) scores, which are all functions of ln p - ln g (absent from
+ * the reference, "parity unpinned").  At the PREDICTION's size only.
+ * pred [B][h][w] (one channel, fp32 or bf16 storage), target fp32 [B][H][W] at any size.  Sampling and validity are
+ * exactly nasseg_berhu_masked_fwd's: prediction pixel i = (b, y, x) meets t_i = target[b][nearest_src(y)][nearest_src(x)]
+ * and is valid iff t_i is finite and valid_min < t_i <= valid_max; V = the valid pixels, n = |V|.  valid_min >= 0 and
+ * pred_min > 0 are required (every logarithm is defined).
+ *   residual   r_i = logf(max(p_i, pred_min)) - logf(t_i) on V, fp32, each logf on its own; written to resid, fp32
+ *              [B][h][w] - the only per-pixel tensor the forward writes; an invalid pixel carries a NaN.
+ *   D          = mean_V(r^2) - silog_lambda * mean_V(r)^2, 0 <= silog_lambda <= 1.  The silog score is sqrt(D) at
+ *              silog_lambda = 1; the root is left out so that the gradient stays finite at a perfect prediction.
+ *   L_gm       = sum_{k < scales} S_k / M_k, s = 2^k; G_k = the pixels with y % s == 0 and x % s == 0 within each image,
+ *              M_k = the valid pixels of G_k over the batch,
+ *              S_k = sum_{i in G_k} ( [i, i+(0,s) valid] |r_{i+(0,s)} - r_i| + [i, i+(s,0) valid] |r_{i+(s,0)} - r_i| ),
+ *              a neighbour counting only inside the same image; M_k == 0: the scale contributes 0.  0 <= scales <= 8
+ *              (0: no such term, L_gm = 0, the stencil pass is not launched).
+ *   total      = berhu_weight * berhu[0] + silog_weight * D + grad_weight * L_gm, berhu = out of nasseg_berhu_masked_fwd
+ *              on the same arguments (null: taken as 0).  n == 0: D = L_gm = 0, gradient 0.
+ * out (16 floats) = total | D | L_gm | n | m = mean_V(r) | M_0..M_7 | 3 unused.  Pass 1 writes resid and the workgroup
+ * sums of r, r^2 and the count; pass 2 is one stencil sweep over resid for all scales; one finalize launch adds the
+ * workgroup partials in fp64 in a fixed order.  ws: nasseg_depth_terms_workspace() floats.
+ * Backward (m and the M_k are functions of the mask; c of the berHu constant): resid, terms = resid, out of the forward,
+ * gscale = the device scalar upstream gradient of the total (null = 1); the three weights are arguments by value.
+ * ONE kernel writes dpred once, in the prediction's type (bf16 storage: one rounding of the sum of all three terms):
+ *   dpred_i = gscale * [ berhu_weight * (berHu's gradient, as nasseg_berhu_masked_bwd)
+ *             + [p_i > pred_min] / p_i * ( silog_weight * (2/n)(r_i - silog_lambda m)
+ *               + grad_weight * sum_k [i in G_k] / M_k * sum_{j in {i+-(0,s), i+-(s,0)}, j valid, in the image} sign(r_i - r_j) ) ]
+ * on valid pixels, exactly 0 on invalid ones; sign(0) = 0.  A pixel with p_i <= pred_min gets no gradient from the two
+ * terms - the berHu, which they sit on top of, still pulls it up.
+ * No float atomics, no host synchronisation, no allocation, a launch geometry that depends on the shapes (and scales)
+ * alone: capturable and bit-reproducible.  n and the M_k reach the backward as fp32 (out[3], out[5 + k]), as n_valid of
+ * nasseg_berhu_masked_fwd does (its out[2]): above 2^24 valid pixels a count is rounded, and 2/n and 1/M_k with it.
+ * _rows_: target is the cache [n_rows][H][W] read in place through the B cache
+ * rows, as nasseg_berhu_masked_rows_fwd - bit for bit the un-indexed call on target[rows]. */
+int64_t nasseg_depth_terms_workspace(void);
+int nasseg_depth_terms_fwd(const float* pred, const float* target, int B, int h, int w, int H, int W, float valid_min,
+                           float valid_max, float pred_min, float silog_lambda, int scales, const float* berhu,
+                           float berhu_weight, float silog_weight, float grad_weight, float* resid, float* out,
+                           float* ws, void* stream);
+int nasseg_depth_terms_bwd(const float* pred, const float* target, const float* resid, const float* berhu,
+                           const float* terms, const float* gscale, int B, int h, int w, int H, int W,
+                           float valid_min, float valid_max, float pred_min, float silog_lambda, int scales,
+                           float berhu_weight, float silog_weight, float grad_weight, float* dpred, void* stream);
+int nasseg_depth_terms_rows_fwd(const float* pred, const float* target, const int64_t* rows, int64_t n_rows, int B,
+                                int h, int w, int H, int W, float valid_min, float valid_max, float pred_min,
+                                float silog_lambda, int scales, const float* berhu, float berhu_weight,
+                                float silog_weight, float grad_weight, float* resid, float* out, float* ws,
+                                void* stream);
+int nasseg_depth_terms_rows_bwd(const float* pred, const float* target, const int64_t* rows, int64_t n_rows,
+                                const float* resid, const float* berhu, const float* terms, const float* gscale,
+                                int B, int h, int w, int H, int W, float valid_min, float valid_max, float pred_min,
+                                float silog_lambda, int scales, float berhu_weight, float silog_weight,
+                                float grad_weight, float* dpred, void* stream);
+
 /* ---- mean-IoU reward: helpers/miou_utils.pyx fast_cm :7-30, compute_iu :32-57,
  * compute_ius_accs :59-90; argmax + up-sampling of engine/inference.py:58-66 ------ */
 int nasseg_fast_cm(const uint8_t* preds, const uint8_t* gt, int64_t P, int n, int64_t* cm,
@@ -1031,6 +1086,26 @@ int nasseg_bf16_berhu_up_rows_fwd(const nasseg_bf16_t* pred, const float* target
 int nasseg_bf16_berhu_up_rows_bwd(const nasseg_bf16_t* pred, const float* target, const int64_t* rows, int64_t n_rows,
                                   const float* stats, const float* gscale, int B, int h, int w, int H, int W,
                                   float valid_min, float valid_max, int group, nasseg_bf16_t* dpred, void* stream);
+int nasseg_bf16_depth_terms_fwd(const nasseg_bf16_t* pred, const float* target, int B, int h, int w, int H, int W,
+                                float valid_min, float valid_max, float pred_min, float silog_lambda, int scales,
+                                const float* berhu, float berhu_weight, float silog_weight, float grad_weight,
+                                float* resid, float* out, float* ws, void* stream);
+int nasseg_bf16_depth_terms_bwd(const nasseg_bf16_t* pred, const float* target, const float* resid,
+                                const float* berhu, const float* terms, const float* gscale, int B, int h, int w,
+                                int H, int W, float valid_min, float valid_max, float pred_min, float silog_lambda,
+                                int scales, float berhu_weight, float silog_weight, float grad_weight,
+                                nasseg_bf16_t* dpred, void* stream);
+int nasseg_bf16_depth_terms_rows_fwd(const nasseg_bf16_t* pred, const float* target, const int64_t* rows,
+                                     int64_t n_rows, int B, int h, int w, int H, int W, float valid_min,
+                                     float valid_max, float pred_min, float silog_lambda, int scales,
+                                     const float* berhu, float berhu_weight, float silog_weight, float grad_weight,
+                                     float* resid, float* out, float* ws, void* stream);
+int nasseg_bf16_depth_terms_rows_bwd(const nasseg_bf16_t* pred, const float* target, const int64_t* rows,
+                                     int64_t n_rows, const float* resid, const float* berhu, const float* terms,
+                                     const float* gscale, int B, int h, int w, int H, int W, float valid_min,
+                                     float valid_max, float pred_min, float silog_lambda, int scales,
+                                     float berhu_weight, float silog_weight, float grad_weight, nasseg_bf16_t* dpred,
+                                     void* stream);
 int nasseg_bf16_depth_metrics(const nasseg_bf16_t* pred, int64_t ldp, int B, int h, int w, const float* gt, int H,
                               int W, float min_depth, float max_depth, double* acc, double* ws, void* stream);
 int nasseg_bf16_colred(int mode, const nasseg_bf16_t* a, int64_t lda, const nasseg_bf16_t* b, int64_t ldb,

@@ -164,6 +164,13 @@ __global__ __launch_bounds__(256) void berhu_masked_finalize_kernel(const float*
   }
 }
 
+// dB/dd of the berHu at d = pred - t, c constant: sign(d) if |d| <= c else d / c.  The one statement of the formula
+// at the prediction's size: berhu_masked_bwd_kernel and depth_terms_bwd_kernel both call it.
+__device__ __forceinline__ float berhu_slope(float d, float c) {
+  const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+  return (fabsf(d) <= c) ? sgn : d / c;
+}
+
 // dpred = g / n_valid * (sign(diff) if |diff| <= c else diff / c) on valid pixels, exactly 0 elsewhere
 template <bool kRows>
 __global__ __launch_bounds__(256) void berhu_masked_bwd_kernel(const act_t* __restrict__ pred,
@@ -178,9 +185,7 @@ __global__ __launch_bounds__(256) void berhu_masked_bwd_kernel(const act_t* __re
     const float t = masked_target<kRows>(target, rt, i, g);
     float r = 0.f;
     if (depth_valid(t, g.vmin, g.vmax)) {
-      const float d = lda1(pred + i) - t;
-      const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-      r = gn * ((fabsf(d) <= c) ? sgn : d / c);
+      r = gn * berhu_slope(lda1(pred + i) - t, c);
     }
     sta1(dpred + i, r);
   }
@@ -527,6 +532,275 @@ int up_bwd(const char* who, const act_t* pred, const float* target, RowTable<kRo
   return NASSEG_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Scale-invariant log and gradient-matching terms on top of the masked berHu (definition: include/nasseg.h,
+// "Depth terms"; INTEGRATION.md, "Depth"): the surrogates of what validate_depth scores, all functions of
+// r = ln max(p, pred_min) - ln t over the valid pixels of nasseg_berhu_masked_fwd (same sampling, same validity).
+//   forward   pass 1 (templated on the row table, as the berHu passes: only the address of an image's target
+//             differs) writes the residual map r - a NaN marks an invalid pixel - and the workgroup sums of r, r^2
+//             and the count; pass 2 is a stencil over r alone: every valid pixel of grid G_k (y, x multiples of 2^k)
+//             counts into M_k and adds |r_j - r_i| for its right and lower neighbour at stride 2^k into S_k, all K
+//             scales in one sweep; one finalize launch adds the workgroup partials in fp64 in a fixed order and writes
+//             total | D | L_gm | n | m | M_0..M_7.
+//   backward  one kernel, one store per pixel in the prediction's type: the berHu's part (berhu_slope, the formula
+//             berhu_masked_bwd_kernel uses) plus, where p > pred_min, (1 / p) * (silog part + the signs of the up to
+//             4 K neighbour differences read from r).
+// No float atomics; grids from the shapes alone.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kMaxScales = 8;
+constexpr int kTermParts = 3 + 2 * kMaxScales;  // ws rows of kMaxGrid floats: sum r | sum r^2 | count | S_0 | M_0 | S_1 ...
+constexpr int kTermOut = 16;                    // total | D | L_gm | n | m | M_0..M_7 | 3 unused
+
+__device__ __forceinline__ float resid_hole() { return __uint_as_float(0x7fc00000u); }
+__device__ __forceinline__ bool resid_valid(float r) { return (__float_as_uint(r) & 0x7f800000u) != 0x7f800000u; }
+
+// sum of red[0..255] into red[0]; every thread of the workgroup calls it
+__device__ __forceinline__ void tree256(float* red) {
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+}
+
+template <bool kRows>
+__global__ __launch_bounds__(256) void depth_resid_kernel(const act_t* __restrict__ pred,
+                                                          const float* __restrict__ target, RowTable<kRows> rt,
+                                                          int64_t n, MaskedGeom g, float pred_min,
+                                                          float* __restrict__ resid, float* __restrict__ part) {
+  __shared__ float red[256];
+  float s1 = 0.f, s2 = 0.f, cnt = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float t = masked_target<kRows>(target, rt, i, g);
+    float r = resid_hole();
+    if (depth_valid(t, g.vmin, g.vmax)) {
+      r = logf(fmaxf(lda1(pred + i), pred_min)) - logf(t);  // (each logarithm on its own, fp32)
+      s1 += r;
+      s2 += r * r;
+      cnt += 1.f;  // (at most n / gridDim.x + 256 < 2^24 per workgroup: exact in fp32)
+    }
+    resid[i] = r;
+  }
+  const float v[3] = {s1, s2, cnt};
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    red[threadIdx.x] = v[q];
+    tree256(red);
+    if (threadIdx.x == 0) part[q * kMaxGrid + blockIdx.x] = red[0];
+    __syncthreads();
+  }
+}
+
+// part: [2 K][kMaxGrid], row 2k = S_k, row 2k + 1 = M_k of the workgroup
+__global__ __launch_bounds__(256) void depth_gm_kernel(const float* __restrict__ resid, int64_t n, int h, int w, int K,
+                                                       float* __restrict__ part) {
+  __shared__ float red[256];
+  float S[kMaxScales], M[kMaxScales];
+#pragma unroll
+  for (int k = 0; k < kMaxScales; ++k) S[k] = 0.f, M[k] = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float ri = resid[i];
+    if (!resid_valid(ri)) continue;
+    const int x = (int)(i % w);
+    const int y = (int)((i / w) % h);
+    bool in = true;  // (G_k+1 is a subset of G_k)
+#pragma unroll
+    for (int k = 0; k < kMaxScales; ++k) {
+      const int s = 1 << k;
+      in = in && k < K && ((x | y) & (s - 1)) == 0;
+      if (in) {
+        M[k] += 1.f;
+        float a = 0.f;
+        if (x + s < w) {  // (inside the row, so inside the image)
+          const float rj = resid[i + s];
+          if (resid_valid(rj)) a += fabsf(rj - ri);
+        }
+        if (y + s < h) {  // (inside the image)
+          const float rj = resid[i + (int64_t)s * w];
+          if (resid_valid(rj)) a += fabsf(rj - ri);
+        }
+        S[k] += a;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kMaxScales; ++k) {
+    if (k < K) {  // (K is the launch's: every thread takes the same branch)
+      red[threadIdx.x] = S[k];
+      tree256(red);
+      if (threadIdx.x == 0) part[(2 * k) * kMaxGrid + blockIdx.x] = red[0];
+      __syncthreads();
+      red[threadIdx.x] = M[k];
+      tree256(red);
+      if (threadIdx.x == 0) part[(2 * k + 1) * kMaxGrid + blockIdx.x] = red[0];
+      __syncthreads();
+    }
+  }
+}
+
+// One workgroup: quantity q of the 3 + 2 K rows of part - thread t adds the partials of workgroups t, t + 256, ... in
+// fp64, then a fixed-order tree through LDS - and thread 0 writes out (kTermOut floats).  berhu: out of
+// nasseg_berhu_masked_fwd (null: no berHu in the total).
+__global__ __launch_bounds__(256) void depth_terms_finalize_kernel(const float* __restrict__ part, int nblk, int K,
+                                                                   float lambda, const float* __restrict__ berhu,
+                                                                   float bw, float sw, float gw,
+                                                                   float* __restrict__ out) {
+  __shared__ double red[256];
+  __shared__ double tot[kTermParts];
+  const int nq = 3 + 2 * K;
+  for (int q = 0; q < nq; ++q) {
+    const float* p = part + (int64_t)q * kMaxGrid;
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += 256) s += (double)p[b];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+      if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) tot[q] = red[0];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double n = tot[2];
+    const double m = n > 0.0 ? tot[0] / n : 0.0;
+    const double D = n > 0.0 ? tot[1] / n - (double)lambda * m * m : 0.0;
+    double L = 0.0;
+    for (int k = 0; k < kMaxScales; ++k) {
+      const double Mk = k < K ? tot[3 + 2 * k + 1] : 0.0;
+      if (Mk > 0.0) L += tot[3 + 2 * k] / Mk;
+      out[5 + k] = (float)Mk;
+    }
+    out[0] = (float)((double)bw * (berhu ? (double)berhu[0] : 0.0) + (double)sw * D + (double)gw * L);
+    out[1] = (float)D;
+    out[2] = (float)L;
+    out[3] = (float)n;
+    out[4] = (float)m;
+    out[13] = out[14] = out[15] = 0.f;
+  }
+}
+
+// sign(ri - rj) when j is valid, else 0; sign(0) = 0
+__device__ __forceinline__ float resid_sign(float ri, float rj) {
+  if (!resid_valid(rj)) return 0.f;
+  return ri > rj ? 1.f : (ri < rj ? -1.f : 0.f);
+}
+
+// dpred = up * [ bw * berHu' + (p > pred_min) / p * ( sw * (2 / n)(r - lambda m)
+//                + gw * sum_k [i in G_k] / M_k * sum_{j = i +- (0, s), i +- (s, 0), valid, in the image} sign(r_i - r_j) ) ]
+// on valid pixels, exactly 0 elsewhere; up = gscale[0] (null: 1)
+template <bool kRows>
+__global__ __launch_bounds__(256) void depth_terms_bwd_kernel(const act_t* __restrict__ pred,
+                                                              const float* __restrict__ target, RowTable<kRows> rt,
+                                                              const float* __restrict__ resid,
+                                                              const float* __restrict__ berhu,
+                                                              const float* __restrict__ terms,
+                                                              const float* __restrict__ gscale, int64_t n,
+                                                              MaskedGeom g, float pred_min, float lambda, int K,
+                                                              float bw, float sw, float gw,
+                                                              act_t* __restrict__ dpred) {
+  const float up = gscale ? gscale[0] : 1.f;
+  const float c = berhu[1];
+  const float nv = berhu[2];
+  const float gb = nv > 0.f ? (up * bw) / nv : 0.f;
+  const float nt = terms[3];
+  const float gs = nt > 0.f ? up * sw * 2.f / nt : 0.f;
+  const float lm = lambda * terms[4];
+  float gk[kMaxScales];
+#pragma unroll
+  for (int k = 0; k < kMaxScales; ++k) {
+    const float Mk = terms[5 + k];
+    gk[k] = (k < K && Mk > 0.f) ? up * gw / Mk : 0.f;
+  }
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float t = masked_target<kRows>(target, rt, i, g);
+    float d = 0.f;
+    if (depth_valid(t, g.vmin, g.vmax)) {
+      const float p = lda1(pred + i);
+      d = gb * berhu_slope(p - t, c);
+      const float ri = resid[i];
+      if (p > pred_min && resid_valid(ri)) {  // (a clamped pixel: no gradient from the two terms)
+        float acc = gs * (ri - lm);
+        const int x = (int)(i % g.w);
+        const int y = (int)((i / g.w) % g.h);
+        bool in = true;
+#pragma unroll
+        for (int k = 0; k < kMaxScales; ++k) {
+          const int s = 1 << k;
+          in = in && k < K && ((x | y) & (s - 1)) == 0;
+          if (in) {
+            float sg = 0.f;
+            if (x + s < g.w) sg += resid_sign(ri, resid[i + s]);
+            if (x - s >= 0) sg += resid_sign(ri, resid[i - s]);
+            if (y + s < g.h) sg += resid_sign(ri, resid[i + (int64_t)s * g.w]);
+            if (y - s >= 0) sg += resid_sign(ri, resid[i - (int64_t)s * g.w]);
+            acc = fmaf(gk[k], sg, acc);
+          }
+        }
+        d += acc / p;
+      }
+    }
+    sta1(dpred + i, d);
+  }
+}
+
+inline bool terms_config(float valid_min, float valid_max, float pred_min, float lambda, int K, float bw, float sw,
+                         float gw) {
+  return valid_min >= 0.f && valid_max == valid_max && pred_min > 0.f && pred_min < INFINITY && lambda >= 0.f &&
+         lambda <= 1.f && K >= 0 && K <= kMaxScales && bw >= 0.f && bw < INFINITY && sw >= 0.f && sw < INFINITY &&
+         gw >= 0.f && gw < INFINITY;
+}
+#define TERMS_CHECK(who)                                                                                       \
+  NASSEG_REQUIRE(terms_config(valid_min, valid_max, pred_min, silog_lambda, scales, berhu_weight, silog_weight, \
+                              grad_weight),                                                                    \
+                 "%s: valid_min >= 0, pred_min > 0, 0 <= silog_lambda <= 1, 0 <= scales <= 8 and finite weights "  \
+                 ">= 0 are expected", who)
+
+template <bool kRows>
+int terms_fwd(const char* who, const act_t* pred, const float* target, RowTable<kRows> rt, int B, int h, int w, int H,
+              int W, float valid_min, float valid_max, float pred_min, float silog_lambda, int scales,
+              const float* berhu, float berhu_weight, float silog_weight, float grad_weight, float* resid, float* out,
+              float* ws, void* stream) {
+  MaskedGeom g;
+  NASSEG_REQUIRE(masked_geom(B, h, w, H, W, valid_min, valid_max, &g), "%s: bad shape", who);
+  NASSEG_REQUIRE(pred && target && resid && out && ws, "%s: null pointer", who);
+  ROWS_CHECK(who);
+  TERMS_CHECK(who);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = (int64_t)B * h * w;
+  const int grid = red_grid(n);
+  hipLaunchKernelGGL(depth_resid_kernel<kRows>, dim3(grid), dim3(256), 0, s, pred, target, rt, n, g, pred_min, resid,
+                     ws);
+  NASSEG_LAUNCH_CHECK("depth_resid");
+  if (scales > 0) {
+    hipLaunchKernelGGL(depth_gm_kernel, dim3(grid), dim3(256), 0, s, (const float*)resid, n, h, w, scales,
+                       ws + 3 * kMaxGrid);
+    NASSEG_LAUNCH_CHECK("depth_gm");
+  }
+  hipLaunchKernelGGL(depth_terms_finalize_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, grid, scales,
+                     silog_lambda, berhu, berhu_weight, silog_weight, grad_weight, out);
+  NASSEG_LAUNCH_CHECK("depth_terms_finalize");
+  return NASSEG_OK;
+}
+
+template <bool kRows>
+int terms_bwd(const char* who, const act_t* pred, const float* target, RowTable<kRows> rt, const float* resid,
+              const float* berhu, const float* terms, const float* gscale, int B, int h, int w, int H, int W,
+              float valid_min, float valid_max, float pred_min, float silog_lambda, int scales, float berhu_weight,
+              float silog_weight, float grad_weight, act_t* dpred, void* stream) {
+  MaskedGeom g;
+  NASSEG_REQUIRE(masked_geom(B, h, w, H, W, valid_min, valid_max, &g), "%s: bad shape", who);
+  NASSEG_REQUIRE(pred && target && resid && berhu && terms && dpred, "%s: null pointer", who);
+  ROWS_CHECK(who);
+  TERMS_CHECK(who);
+  const int64_t n = (int64_t)B * h * w;
+  hipLaunchKernelGGL(depth_terms_bwd_kernel<kRows>, dim3(red_grid(n) * 2), dim3(256), 0, (hipStream_t)stream, pred,
+                     target, rt, resid, berhu, terms, gscale, n, g, pred_min, silog_lambda, scales, berhu_weight,
+                     silog_weight, grad_weight, dpred);
+  NASSEG_LAUNCH_CHECK("depth_terms_bwd");
+  return NASSEG_OK;
+}
+
 const RowTable<false> kNoRows = {};
 
 }  // namespace
@@ -610,6 +884,57 @@ int NASSEG_FN(berhu_up_rows_bwd)(const act_t* pred, const float* target, const i
   const RowTable<true> rt = {rows, n_rows};
   return up_bwd<true>("berhu_up_rows_bwd", pred, target, rt, stats, gscale, B, h, w, H, W, valid_min, valid_max,
                       group, dpred, stream);
+}
+
+#if NASSEG_FP32_ONLY
+// floats: [3 + 2 * 8][1024] workgroup partials, whatever the sizes
+int64_t nasseg_depth_terms_workspace(void) { return (int64_t)kTermParts * kMaxGrid; }
+#endif
+
+// Scale-invariant log + gradient-matching terms (definition: include/nasseg.h, "Depth terms").  berhu: out of
+// nasseg_berhu_masked_fwd on the same arguments (null: the total has no berHu); resid: fp32 [B][h][w], written;
+// out: 16 floats = total | D | L_gm | n | m | M_0..M_7 | 3 unused; ws: nasseg_depth_terms_workspace() floats.
+int NASSEG_FN(depth_terms_fwd)(const act_t* pred, const float* target, int B, int h, int w, int H, int W,
+                               float valid_min, float valid_max, float pred_min, float silog_lambda, int scales,
+                               const float* berhu, float berhu_weight, float silog_weight, float grad_weight,
+                               float* resid, float* out, float* ws, void* stream) {
+  return terms_fwd<false>("depth_terms_fwd", pred, target, kNoRows, B, h, w, H, W, valid_min, valid_max, pred_min,
+                          silog_lambda, scales, berhu, berhu_weight, silog_weight, grad_weight, resid, out, ws,
+                          stream);
+}
+
+// resid, terms: resid and out of nasseg_depth_terms_fwd; berhu: out of nasseg_berhu_masked_fwd; gscale: device scalar
+// upstream gradient of the total (null = 1).  dpred: the gradient of all three terms, written once.
+int NASSEG_FN(depth_terms_bwd)(const act_t* pred, const float* target, const float* resid, const float* berhu,
+                               const float* terms, const float* gscale, int B, int h, int w, int H, int W,
+                               float valid_min, float valid_max, float pred_min, float silog_lambda, int scales,
+                               float berhu_weight, float silog_weight, float grad_weight, act_t* dpred,
+                               void* stream) {
+  return terms_bwd<false>("depth_terms_bwd", pred, target, kNoRows, resid, berhu, terms, gscale, B, h, w, H, W,
+                          valid_min, valid_max, pred_min, silog_lambda, scales, berhu_weight, silog_weight,
+                          grad_weight, dpred, stream);
+}
+
+// row-indexed twins (see nasseg_berhu_masked_rows_fwd): target is the cache [n_rows][H][W], read in place
+int NASSEG_FN(depth_terms_rows_fwd)(const act_t* pred, const float* target, const int64_t* rows, int64_t n_rows,
+                                    int B, int h, int w, int H, int W, float valid_min, float valid_max,
+                                    float pred_min, float silog_lambda, int scales, const float* berhu,
+                                    float berhu_weight, float silog_weight, float grad_weight, float* resid,
+                                    float* out, float* ws, void* stream) {
+  const RowTable<true> rt = {rows, n_rows};
+  return terms_fwd<true>("depth_terms_rows_fwd", pred, target, rt, B, h, w, H, W, valid_min, valid_max, pred_min,
+                         silog_lambda, scales, berhu, berhu_weight, silog_weight, grad_weight, resid, out, ws, stream);
+}
+
+int NASSEG_FN(depth_terms_rows_bwd)(const act_t* pred, const float* target, const int64_t* rows, int64_t n_rows,
+                                    const float* resid, const float* berhu, const float* terms, const float* gscale,
+                                    int B, int h, int w, int H, int W, float valid_min, float valid_max,
+                                    float pred_min, float silog_lambda, int scales, float berhu_weight,
+                                    float silog_weight, float grad_weight, act_t* dpred, void* stream) {
+  const RowTable<true> rt = {rows, n_rows};
+  return terms_bwd<true>("depth_terms_rows_bwd", pred, target, rt, resid, berhu, terms, gscale, B, h, w, H, W,
+                         valid_min, valid_max, pred_min, silog_lambda, scales, berhu_weight, silog_weight,
+                         grad_weight, dpred, stream);
 }
 
 }  // extern "C"

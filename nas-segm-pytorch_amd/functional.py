@@ -3142,6 +3142,111 @@ def berhu_loss_upsampled(pred, target, valid_min=0.0, valid_max=float("inf"), re
     return out if return_parts else out[0]
 
 
+def _depth_terms_config(who, valid_min, berhu_weight, silog_weight, silog_lambda, grad_weight, grad_scales, pred_min):
+    """(berhu_weight, silog_weight, silog_lambda, grad_weight, scales, pred_min) as the kernels take them - a term
+    that is None has weight 0, and without a gradient-matching term scales is 0 (its pass is not launched);
+    ValueError where the definition (include/nasseg.h, "Depth terms") has no meaning"""
+    def weight(name, v):
+        v = float(v)
+        if not 0.0 <= v < float("inf"):
+            raise ValueError("{}: {} must be a finite number >= 0 (got {})".format(who, name, v))
+        return v
+
+    bw = weight("berhu_weight", berhu_weight)
+    sw = 0.0 if silog_weight is None else weight("silog_weight", silog_weight)
+    gw = 0.0 if grad_weight is None else weight("grad_weight", grad_weight)
+    lam, pmin = float(silog_lambda), float(pred_min)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError("{}: silog_lambda must lie in [0, 1] (got {})".format(who, silog_lambda))
+    if isinstance(grad_scales, bool) or int(grad_scales) != grad_scales or not 1 <= int(grad_scales) <= 8:
+        raise ValueError("{}: grad_scales must be an integer in [1, 8] (got {!r})".format(who, grad_scales))
+    if not 0.0 < pmin < float("inf"):
+        raise ValueError("{}: pred_min must be a finite number > 0 (got {})".format(who, pred_min))
+    if not float(valid_min) >= 0.0:
+        raise ValueError("{}: the scale-invariant and gradient-matching terms take logarithms of the valid targets: "
+                         "valid_min >= 0 is required (got {})".format(who, valid_min))
+    return bw, sw, lam, gw, (0 if grad_weight is None else int(grad_scales)), pmin
+
+
+class _DepthCriterion(torch.autograd.Function):
+    """nasseg_berhu_masked_fwd + nasseg_depth_terms_fwd / nasseg_depth_terms_bwd; with ``rows`` their row-indexed
+    twins on the cache ``target``.  Outputs: the total (a scalar of its own) and - not differentiable - berHu, D,
+    L_gm and n_valid (0-dim, fp32).  ``terms``: _depth_terms_config's tuple"""
+
+    @staticmethod
+    def forward(ctx, pred, target, valid_min, valid_max, terms, rows=None):
+        n_rows = None if rows is None else _cache_rows("depth_criterion", pred, target, rows)
+        require_device(pred, target)
+        if pred.dtype not in (torch.float32, torch.bfloat16) or pred.dim() != 4 or pred.shape[1] != 1:
+            raise NassegError("depth_criterion: the prediction must be fp32 or bf16 of shape (B, 1, h, w) (got {} {})"
+                              .format(pred.dtype, tuple(pred.shape)))
+        if target.dtype != torch.float32 or target.dim() != 3 or (rows is None and target.shape[0] != pred.shape[0]):
+            raise NassegError("depth_criterion: the target must be fp32 of shape (B, H, W) (got {} {})".format(
+                target.dtype, tuple(target.shape)))
+        p, t = pred.contiguous(), target.contiguous()  # (one channel: NCHW and NHWC are the same memory)
+        B, _, h, w = p.shape
+        geom = (B, h, w, int(t.shape[1]), int(t.shape[2]), float(valid_min), float(valid_max))
+        bw, sw, lam, gw, scales, pmin = terms
+        berhu, out = _vec(p, 3), _vec(p, 16)
+        resid = torch.empty((B, h, w), device=p.device, dtype=torch.float32)
+        ws_b = _ws(p, lib.query("nasseg_berhu_masked_workspace"))
+        ws_t = _ws(p, lib.query("nasseg_depth_terms_workspace"))
+        table = () if rows is None else (ptr(rows), n_rows)
+        mid = "_rows" if rows is not None else ""
+        stream = current_stream()
+        lib.call(_k("nasseg_berhu_masked{}_fwd".format(mid), p), ptr(p), ptr(t), *table, *geom, ptr(berhu), ptr(ws_b),
+                 stream)
+        lib.call(_k("nasseg_depth_terms{}_fwd".format(mid), p), ptr(p), ptr(t), *table, *geom, pmin, lam, scales,
+                 ptr(berhu), bw, sw, gw, ptr(resid), ptr(out), ptr(ws_t), stream)
+        ctx.save_for_backward(*((p, t, resid, berhu, out) + (() if rows is None else (rows,))))
+        ctx.n_rows, ctx.mid = n_rows, mid
+        ctx.cfg = geom + (pmin, lam, scales, bw, sw, gw)
+        # (the total under a tensor of its own, as _BerHuMasked.forward returns its loss: it may be updated in place)
+        parts = (_own_scalar(berhu, 0), _own_scalar(out, 1), _own_scalar(out, 2), _own_scalar(out, 3))
+        ctx.mark_non_differentiable(*parts)
+        return (_own_scalar(out, 0),) + parts
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        p, t, resid, berhu, out = ctx.saved_tensors[:5]
+        g = g.to(torch.float32).contiguous().view(1)
+        d = torch.empty_like(p)
+        table = () if ctx.n_rows is None else (ptr(ctx.saved_tensors[5]), ctx.n_rows)
+        lib.call(_k("nasseg_depth_terms{}_bwd".format(ctx.mid), p), ptr(p), ptr(t), *table, ptr(resid), ptr(berhu),
+                 ptr(out), ptr(g), *ctx.cfg, ptr(d), current_stream())
+        return (d, None, None, None, None) + (() if ctx.n_rows is None else (None,))
+
+
+def depth_criterion(pred, target, valid_min=0.0, valid_max=float("inf"), berhu_weight=1.0, silog_weight=None,
+                    silog_lambda=0.5, grad_weight=None, grad_scales=4, pred_min=1e-3, rows=None, return_parts=False):
+    """The depth criterion that matches the depth score: ``berhu_weight * berHu + silog_weight * D + grad_weight *
+    L_gm`` of a depth head against a full-size target with holes (absent from the reference; definition:
+    include/nasseg.h, "Depth terms"; INTEGRATION.md, "Depth").
+
+    pred (B, 1, h, w) fp32 or bf16, target (B, H, W) fp32 at ANY size; sampling and validity are
+    ``berhu_loss_masked``'s (nearest sampling of the target at the prediction's size; a pixel counts iff its target t
+    is finite and ``valid_min < t <= valid_max``).  With r = ln max(p, pred_min) - ln t over the n valid pixels:
+    D = mean(r^2) - silog_lambda * mean(r)^2 is the scale-invariant log term (Eigen et al. 2014, eq. 4) - the
+    ``silog`` score of ``validate_depth`` is sqrt(D) at silog_lambda = 1; the root is left out so that the gradient
+    stays finite at a perfect prediction.  L_gm = sum over k < grad_scales of (sum over the pixels of the grid with
+    stride s = 2^k of |r_right - r| + |r_below - r|, neighbours at distance s inside the image, both ends valid) /
+    (valid pixels of that grid) is the multi-scale gradient-matching term (MegaDepth, MiDaS): it rewards sharp depth
+    edges.  A term whose weight is None is left out.  A pixel with p <= pred_min gets no gradient from the two terms -
+    they sit on top of the berHu, which still pulls such a pixel up.  No valid pixel: loss 0, gradient 0.
+    ``valid_min >= 0``, ``pred_min > 0``, ``0 <= silog_lambda <= 1``, ``1 <= grad_scales <= 8`` and weights >= 0:
+    anything else is a ValueError.  One autograd node; the backward is one kernel that writes the gradient of all
+    three terms once.  Returns a 0-dim tensor that may be updated in place; ``return_parts``: (loss, berhu, D, L_gm,
+    n_valid), all 0-dim fp32, the last four not differentiable.  No host synchronisation: capturable; the same
+    inputs give the same bits.  ``rows``: as in ``berhu_loss_masked``."""
+    terms = _depth_terms_config("depth_criterion", valid_min, berhu_weight, silog_weight, silog_lambda, grad_weight,
+                                grad_scales, pred_min)
+    if rows is None:
+        out = _DepthCriterion.apply(pred, target, valid_min, valid_max, terms)
+    else:
+        out = _DepthCriterion.apply(pred, target, valid_min, valid_max, terms, rows)
+    return out if return_parts else out[0]
+
+
 def depth_metrics(pred, gt, min_depth=1e-3, max_depth=10.0, acc=None):
     """Fused bilinear up-sampling -> validity mask -> clamp -> sums of the depth scores: the depth counterpart of
     ``argmax_confusion``.

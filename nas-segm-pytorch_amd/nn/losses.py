@@ -14,22 +14,64 @@ class BerHuLoss(nn.Module):
     ``full_size=True``: ``F.berhu_loss_upsampled`` instead - the prediction is up-sampled bilinearly to the target
     inside the kernels and the loss is taken over the TARGET's valid pixels, every one of them: the resolution
     ``validate_depth`` scores at (without it, each prediction pixel sees the one target pixel nearest sampling
-    picks).  The training steps hand every head the same full-size target either way."""
+    picks).  The training steps hand every head the same full-size target either way.
+    ``silog_weight`` / ``grad_weight`` (numbers; None: no such term): the loss becomes ``F.depth_criterion`` -
+    ``berhu_weight * berHu + silog_weight * D + grad_weight * L_gm`` over the same valid pixels, with
+    r = ln max(pred, pred_min) - ln target: D = mean(r^2) - silog_lambda * mean(r)^2 is the scale-invariant log term
+    (Eigen et al. 2014; ``validate_depth``'s ``silog`` is sqrt(D) at silog_lambda = 1 - the root is left out so that
+    the gradient stays finite at a perfect prediction) and L_gm the gradient-matching term over ``grad_scales``
+    strides 1, 2, 4, ... (MegaDepth, MiDaS), which rewards sharp depth edges: the surrogates of what a depth
+    candidate is scored on.  A pixel with pred <= pred_min gets no gradient from the two terms; they sit on top of
+    the berHu, which still pulls such a pixel up.  The terms are defined at the prediction's size only: with
+    ``full_size=True`` they are a ValueError, and so are ``valid_min < 0``, a ``silog_lambda`` outside [0, 1],
+    ``grad_scales`` outside 1..8, ``pred_min <= 0`` and a negative weight.  With both weights None the criterion
+    is, launch for launch, the one it was without them."""
 
-    def __init__(self, valid_min=0.0, valid_max=float("inf"), full_size=False):
+    def __init__(self, valid_min=0.0, valid_max=float("inf"), full_size=False, *, berhu_weight=1.0, silog_weight=None,
+                 silog_lambda=0.5, grad_weight=None, grad_scales=4, pred_min=1e-3):
         super(BerHuLoss, self).__init__()
         self.valid_min = float(valid_min)
         self.valid_max = float(valid_max)
         self.full_size = bool(full_size)
+        self.berhu_weight = berhu_weight
+        self.silog_weight = silog_weight
+        self.silog_lambda = silog_lambda
+        self.grad_weight = grad_weight
+        self.grad_scales = grad_scales
+        self.pred_min = pred_min
+        if self.has_terms:
+            if self.full_size:
+                raise ValueError("BerHuLoss: full_size=True has no scale-invariant or gradient-matching term (those "
+                                 "terms are defined at the prediction's size only)")
+        elif float(berhu_weight) != 1.0:
+            raise ValueError("BerHuLoss: berhu_weight weighs the berHu against silog_weight / grad_weight; without "
+                             "one of them it would be ignored (got {})".format(berhu_weight))
+        # (the logarithms need valid_min >= 0 only where a term takes them)
+        F._depth_terms_config("BerHuLoss", self.valid_min if self.has_terms else 0.0, **self._terms())
+
+    @property
+    def has_terms(self):
+        return self.silog_weight is not None or self.grad_weight is not None
+
+    def _terms(self):
+        """the keyword arguments of ``F.depth_criterion`` for the terms this criterion has"""
+        return {name: getattr(self, name) for name in ("berhu_weight", "silog_weight", "silog_lambda", "grad_weight",
+                                                       "grad_scales", "pred_min")}
 
     def config(self):
         """what a recorded step carries by value (the stepper cache's key, engine/trainer.py): the loss kind and
-        the two bounds, which are kernel arguments"""
-        return ("berhu_up" if self.full_size else "berhu", self.valid_min, self.valid_max)
+        the two bounds, which are kernel arguments - and, with a term, the terms' values, which are too"""
+        cfg = ("berhu_up" if self.full_size else "berhu", self.valid_min, self.valid_max)
+        if self.has_terms:
+            cfg = cfg + (("terms", self.berhu_weight, self.silog_weight, self.silog_lambda, self.grad_weight,
+                          self.grad_scales, self.pred_min),)
+        return cfg
 
     def forward(self, pred, target, rows=None):
         """``rows`` (an int64 device tensor, one entry per image): ``target`` is a cache (N, H, W) and image b meets
         ``target[rows[b]]``, read in place (the task0 depth cache)"""
+        if self.has_terms:
+            return F.depth_criterion(pred, target, self.valid_min, self.valid_max, rows=rows, **self._terms())
         loss = F.berhu_loss_upsampled if self.full_size else F.berhu_loss_masked
         if rows is None:
             return loss(pred, target, self.valid_min, self.valid_max)
@@ -39,6 +81,10 @@ class BerHuLoss(nn.Module):
         s = "valid_min={}, valid_max={}".format(self.valid_min, self.valid_max)
         if self.full_size:
             s += ", full_size=True"
+        if self.has_terms:
+            s += ", berhu_weight={}, silog_weight={}, silog_lambda={}, grad_weight={}, grad_scales={}, pred_min={}".format(
+                self.berhu_weight, self.silog_weight, self.silog_lambda, self.grad_weight, self.grad_scales,
+                self.pred_min)
         return s
 
 
