@@ -112,7 +112,11 @@ int64_t nasseg_irdw_rows(int B, int H, int W, int K, int C, int stride, int back
 int64_t nasseg_irdw_config(int B, int H, int W, int K, int C, int stride, int backward);
 /* Training-mode BatchNorm statistics of z1 = W1 pro(x) WITHOUT computing z1: z1 is linear in pro(x), so its first and
  * second moments per output channel follow from the K-vector and K x K matrix of moments of pro(x) (one pass over the
- * block's input).  Writes what nasseg_bn_finalize writes for the stored map (to the rounding of the sums).
+ * block's input).  The moments are taken about a pivot - per input channel pro(x) of the block's first pixel where
+ * sixteen pixels spread over the block keep to one side of 0, and 0 otherwise (the sums are then the raw ones); the
+ * same in every workgroup - so that the variance is not the difference of two sums |mean|^2 / var times its size: with
+ * |mean| = 200 std it is within 1e-4 of the float64 value, as from every other statistics producer.  Writes what
+ * nasseg_bn_finalize writes for the stored map (to the rounding of the centred sums: fp32 per workgroup, fp64 after).
  * ws: nasseg_irdw_stats_workspace(K) floats. */
 int64_t nasseg_irdw_stats_workspace(int K);
 int nasseg_irdw_stats(const float* x, const float* w1, const float* in_scale, const float* in_shift, int in_act, int B,

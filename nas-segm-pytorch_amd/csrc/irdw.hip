@@ -536,17 +536,38 @@ __global__ __launch_bounds__(64 * kIrMaxWaves, NASSEG_IR_BWD_MINB) void irdw_bwd
 // - a K x K matrix and a K-vector from ONE pass over the block's input (K = 16 ... 32 channels where z1 has 96 ... 192),
 // then K^2 multiply-adds per output channel.  S = X^T X is itself a matrix product with the pixels as the reduction
 // axis: v_mfma_f32_16x16x4_f32 with A[m][k] = B[k][m] = x~[pixel k][channel m], four pixels per instruction.
+//
+// The moments are CENTRED: raw sums would leave var = w^T S w / M - mu^2 the difference of two numbers |mean|^2 / var
+// times its size, and the workgroups' fp32 accumulators keep 24 bits of them (|mean| = 50 std: 3e-3 of the variance
+// lost, 200 std: 3e-2).  Every workgroup subtracts the same pivot c (kMomSamples float4 loads in one wave, their maximum
+// and one barrier: the same bits everywhere - no sum whose order matters, no extra launch) before the outer product:
+//   s' = sum_p (x~[p] - c),   S' = sum_p (x~[p] - c)(x~[p] - c)^T,
+//   mean = w_n . c + w_n . s' / M,   var = w_n^T S' w_n / M - (w_n . s' / M)^2
+// Per input channel, c[k] = x~[pixel 0][k] where kMomSamples pixels spread evenly over the whole block (pixels
+// i M / kMomSamples: not neighbours, which a real map correlates) all lie nearer to pixel 0 than 0 does,
+// |x~[0][k]| > max_i |x~[p_i][k] - x~[0][k]|, and c[k] = 0 otherwise.
+// - Centred, the terms of the difference are of the variance's own size IF pixel 0 is a few deviations from the mean.
+//   That is an assumption about the map, not a fact: what the samples do establish is that the map's spread, as far
+//   as they saw it, is below |c|, so that centring on c cannot lose more than the raw sums would.
+// - Not centred, the samples reach across 0 (or past 2 c): the mean is within the sampled spread of 0 - with sixteen
+//   samples of a bell-shaped channel, below 6 to 7 deviations, where raw fp32 sums lose less than 5e-5 of the
+//   variance (1e-6 (mean / std)^2, measured: 1.06e-4 at 10 deviations) - and the sums, x~ - 0 being x~, are bit for
+//   bit those of the uncentred kernel: a step whose maps are spread about 0 computes exactly what it did.
+// The pivot is a value of the data or 0, so integer inputs keep integer (and smaller) sums.  It is subtracted BEFORE
+// the masks: pixels past M and padded channel quads contribute exact zeros.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kMomTile = 64;  // pixels per LDS tile
 constexpr int kMomGrid = 512;
+constexpr int kMomSamples = 16;  // pixels that decide a channel's pivot
 
 template <int KT, bool PRO>
 __global__ __launch_bounds__(256) void ir_moments_kernel(const act_t* __restrict__ x, const float* __restrict__ in_scale,
                                                          const float* __restrict__ in_shift, int in_act, int K, int M,
-                                                         float* __restrict__ rows) {
+                                                         float* __restrict__ rows, float* __restrict__ pivot) {
   constexpr int KP = 16 * KT, Q = KP / 4, LSK = KP + 4, IT = (kMomTile * Q) / 256;  // float4 items per thread and tile
   __shared__ float xs[kMomTile * LSK];
   __shared__ float red[KP * KP > 256 * 4 ? KP * KP : 256 * 4];
+  __shared__ float pvs[KP];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, kg = lane >> 4;
   const int quad = tid % Q, k0 = 4 * quad;  // (256 % Q == 0: a thread's items all belong to one channel quad)
@@ -557,6 +578,16 @@ __global__ __launch_bounds__(256) void ir_moments_kernel(const act_t* __restrict
     if (in_shift) psh = ld4(in_shift + k0);
   }
   const float plo = in_act ? 0.f : -INFINITY, phi = in_act == NASSEG_ACT_RELU6 ? 6.f : INFINITY;
+  auto prologue = [&](float4 v) {
+    if (PRO) {
+      v = fma4(v, psc, psh);
+      v.x = __builtin_amdgcn_fmed3f(v.x, plo, phi);
+      v.y = __builtin_amdgcn_fmed3f(v.y, plo, phi);
+      v.z = __builtin_amdgcn_fmed3f(v.z, plo, phi);
+      v.w = __builtin_amdgcn_fmed3f(v.w, plo, phi);
+    }
+    return v;
+  };
   f32x4 acc[KT][KT];
 #pragma unroll
   for (int ta = 0; ta < KT; ++ta)
@@ -573,18 +604,43 @@ __global__ __launch_bounds__(256) void ir_moments_kernel(const act_t* __restrict
     }
   };
   if ((int)blockIdx.x < ntiles) issue(blockIdx.x);
+  // the pivot of every channel quad (0 for a padded quad): wave 0 alone reads the kMomSamples pixels - every workgroup
+  // of the grid asks for the same few cache lines at the same moment, and four times the requests queue four times as
+  // long at their L2 channels - each lane all of them (lanes of one quad share the addresses: no shuffle, and a
+  // maximum is the same in any order), behind the first tile, whose loads they must not hold up.  The other waves take
+  // it from LDS; workgroup 0 hands it on to the finaliser when it is done.
+  float4 piv = f4zero();
+  if (wave == 0) {
+    if (kok) {
+      float4 smp[kMomSamples];
+#pragma unroll
+      for (int i = 0; i < kMomSamples; ++i)  // (pixel i M / kMomSamples < M; pixel 0 first)
+        smp[i] = lda4(x + (size_t)(((int64_t)i * M) / kMomSamples) * K + k0);
+      piv = prologue(smp[0]);
+      float4 dev = f4zero();
+#pragma unroll
+      for (int i = 1; i < kMomSamples; ++i) {
+        const float4 v = prologue(smp[i]);
+        dev.x = fmaxf(dev.x, fabsf(v.x - piv.x));
+        dev.y = fmaxf(dev.y, fabsf(v.y - piv.y));
+        dev.z = fmaxf(dev.z, fabsf(v.z - piv.z));
+        dev.w = fmaxf(dev.w, fabsf(v.w - piv.w));
+      }
+      piv.x = fabsf(piv.x) > dev.x ? piv.x : 0.f;  // (a NaN in pixel 0 or an infinite distance: not centred)
+      piv.y = fabsf(piv.y) > dev.y ? piv.y : 0.f;
+      piv.z = fabsf(piv.z) > dev.z ? piv.z : 0.f;
+      piv.w = fabsf(piv.w) > dev.w ? piv.w : 0.f;
+    }
+    if (lane < Q) *reinterpret_cast<float4*>(&pvs[k0]) = piv;  // (lane < Q: quad == lane)
+  }
+  __syncthreads();
+  piv = *reinterpret_cast<const float4*>(&pvs[k0]);
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
 #pragma unroll
     for (int u = 0; u < IT; ++u) {
       const int px = (tid + 256 * u) / Q;
-      float4 v = raw[u];
-      if (PRO) {
-        v = fma4(v, psc, psh);
-        v.x = __builtin_amdgcn_fmed3f(v.x, plo, phi);
-        v.y = __builtin_amdgcn_fmed3f(v.y, plo, phi);
-        v.z = __builtin_amdgcn_fmed3f(v.z, plo, phi);
-        v.w = __builtin_amdgcn_fmed3f(v.w, plo, phi);
-      }
+      float4 v = prologue(raw[u]);
+      v = make_float4(v.x - piv.x, v.y - piv.y, v.z - piv.z, v.w - piv.w);  // (centred first, masked second)
       v = keep_if(v, kok && tile * kMomTile + px < M);
       *reinterpret_cast<float4*>(&xs[px * LSK + k0]) = v;
       csum = add4(csum, v);
@@ -630,12 +686,14 @@ __global__ __launch_bounds__(256) void ir_moments_kernel(const act_t* __restrict
     for (int u = qd; u < 256; u += Q) sacc += red[4 * u + c];
     out[KP * KP + tid] = sacc;
   }
+  if (blockIdx.x == 0 && tid < Q) *reinterpret_cast<float4*>(pivot + k0) = piv;
 }
 
-// mean / variance of z1 per output channel from the summed moments, and everything nasseg_bn_finalize writes.
-// 256 threads = 8 output channels x 32 lanes: lane k of a channel n forms w[n][k] * (S[k][.] . w[n][.]) and
-// w[n][k] * s[k]; the 32 lanes meet with shuffles (fp64 throughout).
-__global__ __launch_bounds__(256) void ir_moments_finalize(const float* __restrict__ mom, const float* __restrict__ w1,
+// mean / variance of z1 per output channel from the summed centred moments and the pivot, and everything
+// nasseg_bn_finalize writes.  256 threads = 8 output channels x 32 lanes: lane k of a channel n forms
+// w[n][k] * (S'[k][.] . w[n][.]), w[n][k] * s'[k] and w[n][k] * c[k]; the 32 lanes meet with shuffles (fp64 throughout).
+__global__ __launch_bounds__(256) void ir_moments_finalize(const float* __restrict__ mom, const float* __restrict__ pivot,
+                                                           const float* __restrict__ w1,
                                                            int K, int KP, int C, double M, float eps, float momentum,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            float* __restrict__ mean, float* __restrict__ invstd,
@@ -643,8 +701,10 @@ __global__ __launch_bounds__(256) void ir_moments_finalize(const float* __restri
                                                            float* __restrict__ running_mean,
                                                            float* __restrict__ running_var, int64_t* nbt) {
   __shared__ float S[32 * 32 + 32];
+  __shared__ float cv[32];
   __shared__ float wn[8][32];
   for (int e = threadIdx.x; e < KP * KP + KP; e += 256) S[e] = mom[e];
+  if (threadIdx.x < 32) cv[threadIdx.x] = (int)threadIdx.x < KP ? pivot[threadIdx.x] : 0.f;
   const int nl = threadIdx.x >> 5, k = threadIdx.x & 31;
   const int n = blockIdx.x * 8 + nl;
   wn[nl][k] = (n < C && k < K) ? w1[(size_t)n * K + k] : 0.f;
@@ -655,15 +715,17 @@ __global__ __launch_bounds__(256) void ir_moments_finalize(const float* __restri
   if (k < K) {
     for (int l = 0; l < K; ++l) r += (double)S[k * KP + l] * (double)wn[nl][l];
   }
-  double wsw = wk * r, ws = k < K ? wk * (double)S[KP * KP + k] : 0.0;
+  double wsw = wk * r, ws = k < K ? wk * (double)S[KP * KP + k] : 0.0, wc = k < K ? wk * (double)cv[k] : 0.0;
 #pragma unroll
   for (int off = 16; off >= 1; off >>= 1) {  // (lanes 32 nl' .. 32 nl' + 31 of a wave: a fixed tree)
     wsw += __shfl_xor(wsw, off);
     ws += __shfl_xor(ws, off);
+    wc += __shfl_xor(wc, off);
   }
   if (n >= C || k != 0) return;
-  const double mu = ws / M;
-  double var = wsw / M - mu * mu;
+  const double dmu = ws / M;  // (the mean of the centred map: a few deviations at most)
+  const double mu = wc + dmu;
+  double var = wsw / M - dmu * dmu;
   if (var < 0.0) var = 0.0;
   const double is = 1.0 / sqrt(var + (double)eps);
   mean[n] = (float)mu;
@@ -738,16 +800,18 @@ int64_t nasseg_irdw_config(int B, int H, int W, int K, int C, int stride, int ba
 #endif
 
 #if NASSEG_FP32_ONLY
-// floats of workspace nasseg_irdw_stats needs (partial moment rows + their sum)
+// floats of workspace nasseg_irdw_stats needs (partial moment rows + their sum + the pivot)
 int64_t nasseg_irdw_stats_workspace(int K) {
   const int KP = K <= 16 ? 16 : 32;
-  return (int64_t)(kMomGrid + 64 + 1) * (KP * KP + KP);
+  return (int64_t)(kMomGrid + 64 + 1) * (KP * KP + KP) + KP;
 }
 #endif
 
 // Training-mode BatchNorm statistics of z1 = W1 pro(x) [B*H*W][C] WITHOUT computing z1 (see ir_moments_kernel): what
 // nasseg_bn_finalize writes for the stored map - mean, invstd, scale = gamma * invstd, shift, running statistics,
-// num_batches_tracked - to the rounding of the sums (moments in fp32 per workgroup, everything after that in fp64).
+// num_batches_tracked - to the rounding of the sums (moments in fp32 per workgroup, a channel whose sampled pixels
+// keep to one side of 0 centred on the block's first pixel - the rule is at ir_moments_kernel - so that a mean far from
+// 0 costs no digits of the variance; everything after that in fp64).
 // K % 4 == 0, K <= 32, C <= 16384; ws: nasseg_irdw_stats_workspace(K) floats.
 int NASSEG_FN(irdw_stats)(const act_t* x, const float* w1, const float* in_scale, const float* in_shift, int in_act,
                           int B, int H, int W, int K, int C, float eps, float momentum, const float* gamma,
@@ -764,15 +828,16 @@ int NASSEG_FN(irdw_stats)(const act_t* x, const float* w1, const float* in_scale
   const int grid = ntiles < kMomGrid ? ntiles : kMomGrid;
   const bool pro = in_scale || in_shift || in_act;
   hipStream_t s = (hipStream_t)stream;
-  if (KP == 16 && pro) hipLaunchKernelGGL((ir_moments_kernel<1, true>), dim3(grid), dim3(256), 0, s, x, in_scale, in_shift, in_act, K, M, ws);
-  else if (KP == 16) hipLaunchKernelGGL((ir_moments_kernel<1, false>), dim3(grid), dim3(256), 0, s, x, in_scale, in_shift, in_act, K, M, ws);
-  else if (pro) hipLaunchKernelGGL((ir_moments_kernel<2, true>), dim3(grid), dim3(256), 0, s, x, in_scale, in_shift, in_act, K, M, ws);
-  else hipLaunchKernelGGL((ir_moments_kernel<2, false>), dim3(grid), dim3(256), 0, s, x, in_scale, in_shift, in_act, K, M, ws);
-  NASSEG_LAUNCH_CHECK("ir_moments_kernel");
   float* total = ws + (size_t)(kMomGrid + 64) * per;
+  float* pivot = total + per;
+  if (KP == 16 && pro) hipLaunchKernelGGL((ir_moments_kernel<1, true>), dim3(grid), dim3(256), 0, s, x, in_scale, in_shift, in_act, K, M, ws, pivot);
+  else if (KP == 16) hipLaunchKernelGGL((ir_moments_kernel<1, false>), dim3(grid), dim3(256), 0, s, x, in_scale, in_shift, in_act, K, M, ws, pivot);
+  else if (pro) hipLaunchKernelGGL((ir_moments_kernel<2, true>), dim3(grid), dim3(256), 0, s, x, in_scale, in_shift, in_act, K, M, ws, pivot);
+  else hipLaunchKernelGGL((ir_moments_kernel<2, false>), dim3(grid), dim3(256), 0, s, x, in_scale, in_shift, in_act, K, M, ws, pivot);
+  NASSEG_LAUNCH_CHECK("ir_moments_kernel");
   const int rc = nasseg_rows_sum(ws, grid, per, total, stream);
   if (rc != NASSEG_OK) return rc;
-  hipLaunchKernelGGL(ir_moments_finalize, dim3(cdiv(C, 8)), dim3(256), 0, s, total, w1, K, KP, C, (double)M, eps, momentum,
+  hipLaunchKernelGGL(ir_moments_finalize, dim3(cdiv(C, 8)), dim3(256), 0, s, total, pivot, w1, K, KP, C, (double)M, eps, momentum,
                      gamma, beta, mean, invstd, scale, shift, running_mean, running_var, num_batches_tracked);
   NASSEG_LAUNCH_CHECK("ir_moments_finalize");
   return NASSEG_OK;

@@ -262,6 +262,81 @@ def test_fused_chain_kernels_against_torch_cpu_autograd(kind, irdw, batch, monke
             assert_close(gb[k], cb[k], 1e-6, 2e-5, "{}: buffer {}".format(kind, k))
 
 
+@pytest.mark.parametrize("kind", ["ir_16_24_s2", "ir_24_24"])
+def test_inverted_residual_whose_input_mean_dwarfs_its_deviation(kind, monkeypatch):
+    """InvertedResidual on an input with |mean| = 50 std per channel (either sign), forward and backward, with the
+    expansion rebuilt (its statistics from the moments of this input, nasseg_irdw_stats) and stored (statistics from the
+    sums over z1 itself), both against torch CPU autograd in float64: output, input gradient, every weight and BatchNorm
+    parameter gradient, the running statistics of every BatchNorm.  The two forms run the same arithmetic downstream of
+    the statistics, so the rebuilt form's distance from float64 is at most twice the stored form's (the row sums are
+    partitioned differently) plus the tolerance of test_fused_chain_kernels_against_torch_cpu_autograd - ELEMENT BY
+    ELEMENT, which bounds the largest error of a tensor by twice the stored form's largest and is stricter than that:
+    ir_24_24: one pre-activation of the float64 reference sits 2e-7 from a ReLU6 kink and takes the other branch in
+    fp32 - in both forms alike, the rebuilt z1 has the stored one's bits: dx is 0.5 off in the 3 x 3 pixels around it and
+    the gradients of the first conv and BatchNorm move with it, by the same amount in both forms.  Against the stored
+    form's largest error every other element of those tensors would be allowed 1.0; against its own element only the
+    ones the flip moved are, by what it moved them.  (With raw moments the rebuilt form's output was 1.3e-4 from
+    float64 where the stored form's is 4.6e-5, its weight gradients 3 - 5 times the stored form's.)"""
+    Fm = lower_thresholds(monkeypatch)
+    monkeypatch.setattr(Fm, "_IRDW_MIN_PIXELS", 0)
+    mods, cin, _, residual, relu_in = build(kind)
+    randomise(mods, 5)
+    ref64 = copy.deepcopy(mods).double().train()
+    mods = mods.to(DEV).train()
+    state = copy.deepcopy(mods.state_dict())
+    g = torch.Generator().manual_seed(17)
+    std = torch.rand(cin, generator=g) + 0.5
+    sign = torch.where(torch.rand(cin, generator=g) > 0.5, 1.0, -1.0)
+    x0 = (torch.randn(2, cin, 24, 40, generator=g) + 50.0 * sign.view(1, cin, 1, 1)) * std.view(1, cin, 1, 1)
+    xd = x0.double().requires_grad_(True)
+    yd = torch_reference(ref64._modules.values(), xd, xd if residual else None, relu_in)
+    cot = rnd(*yd.shape, seed=3)
+    yd.backward(cot.double())
+    want = {"y": yd.detach(), "dx": xd.grad}
+    want.update(("d" + k, p.grad) for k, p in ref64.named_parameters())
+    want.update((k, b) for k, b in ref64.named_buffers() if b.dtype != torch.int64)
+    got = {}
+    for irdw in (True, False):
+        monkeypatch.setattr(Fm, "IRDW", irdw)
+        mods.load_state_dict(state)
+        for q in mods.parameters():
+            q.grad = None
+        seen = []
+        orig = Fm.lib.call
+
+        def rec(fn, *a):
+            seen.append(fn)
+            return orig(fn, *a)
+
+        monkeypatch.setattr(Fm.lib, "call", rec)
+        xg = dev(x0.clone()).requires_grad_(True)
+        yg = mods(xg, residual=xg if residual else None, relu_in=relu_in)
+        yg.backward(dev(cot))
+        monkeypatch.setattr(Fm.lib, "call", orig)
+        assert ("nasseg_irdw_stats" in seen) == irdw and ("nasseg_irdw_fwd" in seen) == irdw, sorted(set(seen))
+        out = {"y": yg.detach(), "dx": xg.grad}
+        out.update(("d" + k, p.grad) for k, p in mods.named_parameters())
+        out.update((k, b) for k, b in mods.named_buffers() if b.dtype != torch.int64)
+        got[irdw] = dict((k, v.detach().cpu().double().clone()) for k, v in out.items())
+    assert set(got[True]) == set(want) and len([k for k in want if k.endswith("running_var")]) == 3
+    failed = []
+    for k in sorted(want):
+        w = want[k].detach()
+        e_on, e_off = (got[True][k] - w).abs(), (got[False][k] - w).abs()
+        buf = k.endswith("running_mean") or k.endswith("running_var")
+        tol = 1e-6 + 2e-5 * w.abs() if buf else 1e-4 * float(w.abs().max()) + 1e-4 * w.abs()
+        bad = e_on > 2.0 * e_off + tol  # (per element: see the docstring)
+        # (dx: an element whose pre-activation sits within rounding of a ReLU6 kink may take the other branch in
+        #  either form - at most 2e-5 of the elements, as in the test above)
+        share = float(bad.double().mean())
+        print("IRCHAIN {} {:28s} rebuilt {:.2e} stored {:.2e} (|ref| max {:.2e})".format(
+            kind, k, float(e_on.max()), float(e_off.max()), float(w.abs().max())))
+        if share > (2e-5 if k == "dx" else 0.0):
+            failed.append("{}: rebuilt {:.2e}, stored {:.2e}, {:.1e} of the elements off".format(
+                k, float(e_on.max()), float(e_off.max()), share))
+    assert not failed, "; ".join(failed)
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 @pytest.mark.parametrize("kind", ["sep3x3_r2", "ir_16_24_s2", "stem_stage1_2"])
 def test_the_rebuilt_conv_output_trains_like_the_stored_one(kind, dtype, monkeypatch):

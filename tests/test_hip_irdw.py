@@ -10,6 +10,7 @@ fp32 and bf16 storage."""
 import pytest
 import torch
 
+import _irdw_stats_ref as R
 from _util import assert_close
 
 pytestmark = pytest.mark.gpu
@@ -212,3 +213,94 @@ def test_statistics_of_the_expansion_from_the_moments_of_its_input(case, dtype, 
     assert float(((got[3] - ref[3]).abs()).max()) < 10 * rel * (1.0 + float((ref[0].abs() / std).max())), "shift"
     assert_close(got[4], ref[4], rel * float(std.max()) + 1e-6, rel, "running_mean")
     assert_close(got[5], ref[5], 10 * rel * float(ref[5].abs().max()), 10 * rel, "running_var")
+
+
+MEAN_CASES = [
+    # B, K, C, H, W
+    (1, 16, 96, 7, 9),       # M = 63: one ragged tile - the masked pixels contribute nothing after the centring
+    (1, 8, 48, 5, 13),       # M = 65: a second tile of one pixel; K < 16 - the padded channel quads stay zero
+    (1, 4, 16, 33, 31),      # K = 4
+    (2, 24, 144, 61, 67),    # M = 8174: K padded to 32 (two tiles of K), 128 workgroups
+    (1, 32, 192, 181, 223),  # M = 40363: more tiles than the 512 workgroups - they loop, the accumulators grow; K = 32
+]
+
+
+@pytest.mark.parametrize("ratio", [10.0, 50.0, 200.0], ids=lambda r: "ratio{:g}".format(r))
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("pro", R.PROS, ids=lambda p: "pro{}".format(p))
+@pytest.mark.parametrize("case", MEAN_CASES, ids=lambda c: "B{}_{}to{}_{}x{}".format(*c))
+def test_statistics_from_the_moments_when_the_mean_dwarfs_the_deviation(case, pro, dtype, ratio):
+    """nasseg_irdw_stats where |mean| = ratio * std in every channel of pro(x) (either sign; behind a ReLU / ReLU6 or a
+    bottleneck BatchNorm whose beta has drifted) against the float64 reference of tests/_irdw_stats_ref.py on the
+    values as stored: the variance - read from invstd and from running_var - to 1e-4 (relative), the bound of every
+    other statistics producer in this regime, and to 8 x the error of nasseg_bn_stats over the stored z1 + 1e-6; the
+    mean to 2e-5 deviations + 2 ulp of its fp32 value; scale * z1 + shift at 256 pixels to (2e-4, 1e-4).
+    Uncentred moments (var = w^T S w / M - mu^2 from fp32 sums of the raw products) lose 3e-3 of the variance at ratio
+    50 and 3e-2 at ratio 200; the kernel centres every input channel whose sampled pixels keep to one side of 0 - all of
+    them here but the ones a ReLU clamps to a constant 0 - on the block's first pixel."""
+    Fm = F()
+    lib, ptr, stream = Fm.lib, Fm.ptr, Fm.current_stream
+    B, K, C, H, W = case
+    M = B * H * W
+    x, w1, (isc, ish, iact) = R.make_inputs(B, K, C, H, W, ratio, pro, seed=1)
+    x = x.to(dtype)
+    g = torch.Generator().manual_seed(23)
+    gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.2
+    eps, mom = 1e-5, 0.1
+    zero = torch.zeros(C)
+    ref = R.statistics(x.float(), w1, isc, ish, iact, gamma, beta, eps, mom, zero, zero)
+    mean64, var64, std64 = ref["mean"], ref["var"], ref["var"].sqrt()
+    assert float(var64.min()) > 0.0
+    worst = float((mean64.abs() / std64).max())
+    if ratio == 200.0:
+        assert worst > 100.0, "no output channel with |mean| > 100 std ({:.1f})".format(worst)
+    xd, w1d = dev(x), dev(w1)
+    iscd, ishd = (None, None) if isc is None else (isc.to(DEV), ish.to(DEV))
+    gd, bd = gamma.to(DEV), beta.to(DEV)
+
+    def buffers():
+        return [torch.full((C,), float("nan"), device=DEV) for _ in range(4)] + [
+            torch.zeros(C, device=DEV), torch.zeros(C, device=DEV), torch.full((), 7, device=DEV, dtype=torch.int64)]
+
+    got = buffers()
+    ws = torch.full((lib.query("nasseg_irdw_stats_workspace", K),), float("nan"), device=DEV)
+    lib.call(Fm._k("nasseg_irdw_stats", xd), ptr(xd), ptr(w1d), ptr(iscd), ptr(ishd), iact, B, H, W, K, C, eps, mom,
+             ptr(gd), ptr(bd), *[ptr(b) for b in got], ptr(ws), stream())
+    # the sibling to measure against: the stored expansion (general forward kernel) and nasseg_bn_stats over it
+    z1 = torch.empty((B, C, H, W), device=DEV, dtype=dtype).contiguous(memory_format=torch.channels_last)
+    lib.call(Fm._k("nasseg_conv_fwd", xd), ptr(xd), K, ptr(w1d), ptr(z1), C, ptr(iscd), ptr(ishd), iact, None, None, 0,
+             None, 0, B, H, W, K, H, W, C, 1, 1, 1, 0, 1, 0, None, stream())
+    sto = buffers()
+    ws1 = torch.empty(lib.query("nasseg_colred_workspace", 1, M, C), device=DEV)
+    lib.call(Fm._k("nasseg_bn_stats", z1), ptr(z1), C, M, C, eps, mom, ptr(gd), ptr(bd), *[ptr(b) for b in sto],
+             ptr(ws1), stream())
+    got = [b.cpu().double() for b in got]
+    sto = [b.cpu().double() for b in sto]
+    assert int(got[6]) == 8 == int(sto[6])
+    e32, m32 = R.f32(eps), R.f32(mom)
+
+    def variance_errors(b):  # (from invstd, from running_var: running statistics start at 0 - no cancellation here)
+        v_is = 1.0 / b[1] ** 2 - e32
+        v_rv = b[5] / m32 * (M - 1) / M
+        return float(((v_is - var64) / var64).abs().max()), float(((v_rv - var64) / var64).abs().max())
+
+    err, err_sto = variance_errors(got), variance_errors(sto)
+    mean_err = (got[0] - mean64).abs() / std64
+    mean_tol = 2e-5 + 2.0 * R.ulp32(mean64) / std64
+    print("IRMOM {}to{} M={} pro{} {} ratio {:g} (|mean|/std <= {:.0f}): moments {:.2e} {:.2e} stored {:.2e} {:.2e} "
+          "mean {:.2e} of {:.2e}".format(K, C, M, pro, "bf16" if dtype == torch.bfloat16 else "fp32", ratio, worst,
+                                         err[0], err[1], err_sto[0], err_sto[1], float(mean_err.max()),
+                                         float(mean_tol[mean_err.argmax()])))
+    for b in got[:6]:
+        assert bool(torch.isfinite(b).all())
+    for e, es, what in zip(err, err_sto, ("invstd", "running_var")):
+        assert e < 1e-4, "variance from {} off by {:.2e} (relative) at |mean| = {:g} std".format(what, e, ratio)
+        assert e <= 8.0 * es + 1e-6, "variance from {}: {:.2e}, of the stored map {:.2e}".format(what, e, es)
+    assert bool((mean_err <= mean_tol).all()), "mean off by {:.2e} deviations".format(float(mean_err.max()))
+    rm_err = (got[4] / m32 - mean64).abs() / std64
+    assert bool((rm_err <= 2e-5 + 2.0 * R.ulp32(mean64) / std64).all()), "running_mean"
+    # scale * z1 + shift at 256 pixels, evaluated in float64
+    zs = ref["z1"].permute(0, 2, 3, 1).reshape(M, C)
+    zs = zs[torch.randperm(M, generator=g)[:256]]
+    want = (zs - mean64) * ref["invstd"] * gamma.double() + beta.double()
+    assert_close(zs * got[2] + got[3], want, 2e-4, 1e-4, "normalised output")
