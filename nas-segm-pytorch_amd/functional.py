@@ -2512,7 +2512,7 @@ class _LogSoftmaxNLL(torch.autograd.Function):
                  ptr(out), ptr(ws), current_stream())
         ctx.save_for_backward(logits, target, out)
         ctx.cfg = (esz, int(ignore_index))
-        return out[0]  # (a view, not a clone: a 4-byte copy node in a recorded step cannot be re-created, graph_dag.py)
+        return _own_scalar(out, 0)  # (it may be updated in place; backward reads out[1] only)
 
     @staticmethod
     def backward(ctx, g):
@@ -2574,8 +2574,10 @@ def log_softmax_nll_mse(logits, target, teacher, ignore_index=255):
 
 
 def _own_scalar(t, index):
-    """element ``index`` of the fp32 vector ``t`` under a 0-dim tensor of its own (no view, no copy: see
-    _BerHuMasked.forward)"""
+    """element ``index`` of the fp32 vector ``t`` under a 0-dim tensor of its own: what a loss node returns.  Not a
+    view of ``t`` - a caller may update a loss in place (``loss += aux_weight * aux_loss``, the reference's idiom),
+    which autograd refuses on a view made inside a Function - and not a copy (a 4-byte copy node in a recorded step
+    cannot be re-created, graph_dag.py).  A node's backward must not read the element it gave away like this."""
     return torch.empty(0, device=t.device, dtype=torch.float32).set_(t.untyped_storage(), t.storage_offset() + index,
                                                                      (), ())
 
@@ -2964,12 +2966,12 @@ class _BerHu(torch.autograd.Function):
         ws = _ws(p, lib.query("nasseg_ce_workspace"))
         lib.call(_k("nasseg_berhu_fwd", p), ptr(p), ptr(t), p.numel(), ptr(out), ptr(ws), current_stream())
         ctx.save_for_backward(p, t, out)
-        return out[0]
+        return _own_scalar(out, 0)  # (it may be updated in place; backward reads c = out[1] only)
 
     @staticmethod
     def backward(ctx, g):
         p, t, out = ctx.saved_tensors
-        g = g.to(torch.float32).contiguous().view(1)
+        g = _upstream(g)
         d = torch.empty_like(p)
         lib.call(_k("nasseg_berhu_bwd", p), ptr(p), ptr(t), ptr(out), ptr(g), p.numel(), ptr(d),
                  current_stream())
@@ -2981,75 +2983,120 @@ def berhu_loss(pred, target):
     return _BerHu.apply(pred, target)
 
 
-def _cache_rows(who, pred, target, rows):
-    """the checks of ``rows=``: ``target`` is a cache (N, H, W), fp32 and contiguous as it stands - it is never
-    copied -, ``rows`` an int64 device tensor of one cache row per image of ``pred``.  An index that can be read
-    without a synchronisation (a host tensor) is checked against [0, N) before it is refused for being on the host;
-    on the device the kernels clamp (a memory-safety net, as in ``gather_rows``).  Returns N."""
-    if not torch.is_tensor(rows) or rows.dtype != torch.int64 or rows.dim() != 1 or not rows.is_contiguous():
-        raise NassegError("{}: rows must be a contiguous 1-D int64 tensor".format(who))
-    if not torch.is_tensor(target) or target.dtype != torch.float32 or target.dim() != 3 or target.shape[0] < 1:
-        raise NassegError("{}: with rows, the target must be an fp32 cache of shape (N, H, W) (got {} {})".format(
-            who, getattr(target, "dtype", None), tuple(getattr(target, "shape", ()))))
-    n_rows = int(target.shape[0])
-    if rows.shape[0] != pred.shape[0]:
-        raise NassegError("{}: one cache row per image expected ({} rows for {} images)".format(
-            who, rows.shape[0], pred.shape[0]))
-    if not rows.is_cuda and rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n_rows):
-        raise IndexError("{}: cache row index out of range [0, {})".format(who, n_rows))
+def _depth_inputs(who, pred, target, rows):
+    """(p, t, rows, n_rows, (B, h, w, H, W)) as the depth losses' kernels read them: a contiguous prediction
+    (B, 1, h, w), fp32 or bf16, and a contiguous fp32 target (B, H, W) of any size.  ``who``: the public function the
+    user called, named by every error.
+    With ``rows`` the target is a cache (N, H, W), fp32 and contiguous as it stands - it is never copied -, ``rows``
+    an int64 device tensor of one cache row per image of ``pred``, and n_rows = N (None without).  An index that can be
+    read without a synchronisation (a host tensor) is checked against [0, N) before it is refused for being on the
+    host; on the device the kernels clamp (a memory-safety net, as in ``gather_rows``)."""
+    n_rows = None
+    if rows is not None:
+        if not torch.is_tensor(rows) or rows.dtype != torch.int64 or rows.dim() != 1 or not rows.is_contiguous():
+            raise NassegError("{}: rows must be a contiguous 1-D int64 tensor".format(who))
+        if not torch.is_tensor(target) or target.dtype != torch.float32 or target.dim() != 3 or target.shape[0] < 1:
+            raise NassegError("{}: with rows, the target must be an fp32 cache of shape (N, H, W) (got {} {})".format(
+                who, getattr(target, "dtype", None), tuple(getattr(target, "shape", ()))))
+        n_rows = int(target.shape[0])
+        if rows.shape[0] != pred.shape[0]:
+            raise NassegError("{}: one cache row per image expected ({} rows for {} images)".format(
+                who, rows.shape[0], pred.shape[0]))
+        if not rows.is_cuda and rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n_rows):
+            raise IndexError("{}: cache row index out of range [0, {})".format(who, n_rows))
     require_device(pred, target, rows)
-    if not target.is_contiguous():
+    if rows is not None and not target.is_contiguous():
         raise NassegError("{}: with rows, the target cache must be contiguous (it is read in place)".format(who))
-    return n_rows
+    if pred.dtype not in (torch.float32, torch.bfloat16) or pred.dim() != 4 or pred.shape[1] != 1:
+        raise NassegError("{}: the prediction must be fp32 or bf16 of shape (B, 1, h, w) (got {} {})".format(
+            who, pred.dtype, tuple(pred.shape)))
+    if target.dtype != torch.float32 or target.dim() != 3 or (rows is None and target.shape[0] != pred.shape[0]):
+        raise NassegError("{}: the target must be fp32 of shape (B, H, W) (got {} {})".format(
+            who, target.dtype, tuple(target.shape)))
+    p, t = pred.contiguous(), target.contiguous()  # (one channel: NCHW and NHWC are the same memory)
+    B, _, h, w = p.shape
+    return p, t, rows, n_rows, (B, h, w, int(t.shape[1]), int(t.shape[2]))
 
 
-class _BerHuMasked(torch.autograd.Function):
-    """nasseg_berhu_masked_fwd / _bwd; with ``rows`` their row-indexed twins on the cache ``target``"""
+def _depth_entry(base, end, p, rows, n_rows):
+    """(entry point, the arguments that follow ptr(t)) of the depth loss ``base`` + ``end`` ("_fwd" | "_bwd") for a
+    prediction stored like ``p``: with ``rows`` the row-indexed twin ``base``_rows``end`` and its table (rows, N),
+    without them the plain entry point and nothing"""
+    if rows is None:
+        return _k(base + end, p), ()
+    return _k(base + "_rows" + end, p), (ptr(rows), n_rows)
+
+
+# What _DepthCriterion returns; a part its combination does not produce is None.  berhu, silog (D) and grad_match
+# (L_gm) are the terms'; c is the berHu's threshold when it runs alone.
+_DepthParts = collections.namedtuple("_DepthParts", "loss berhu c n_valid silog grad_match")
+
+
+class _DepthCriterion(torch.autograd.Function):
+    """The depth criterion against a full-size target with holes, one node and one dpred.  ``sampling`` "masked": the
+    target sampled (nearest) at the prediction's size, nasseg_berhu_masked_fwd / _bwd; with ``terms``
+    (_depth_terms_config's tuple, else None) nasseg_depth_terms_fwd adds the scale-invariant and gradient-matching
+    terms to that berHu and nasseg_depth_terms_bwd writes the gradient of all three.  "up": the prediction up-sampled
+    bilinearly to the target's size, nasseg_berhu_up_fwd / _bwd, ``group`` the backward's lanes per prediction pixel
+    (0: from the shapes); the library has no terms there.  ``rows`` (or None): the row-indexed twins of the same entry
+    points on the cache ``target`` (_depth_entry).
+    Outputs: the fields of _DepthParts, 0-dim fp32 scalars of their own on the kernels' output vectors - the loss may
+    be updated in place, the others are not differentiable.  Kept for backward: p, t, the berHu's
+    {loss, c, n_valid} and rows, with the terms also their residuals and 16 floats."""
 
     @staticmethod
-    def forward(ctx, pred, target, valid_min, valid_max, rows=None):
-        n_rows = None if rows is None else _cache_rows("berhu_loss_masked", pred, target, rows)
-        require_device(pred, target)
-        if pred.dtype not in (torch.float32, torch.bfloat16) or pred.dim() != 4 or pred.shape[1] != 1:
-            raise NassegError("berhu_loss_masked: the prediction must be fp32 or bf16 of shape (B, 1, h, w) (got {} {})"
-                              .format(pred.dtype, tuple(pred.shape)))
-        if target.dtype != torch.float32 or target.dim() != 3 or (rows is None and target.shape[0] != pred.shape[0]):
-            raise NassegError("berhu_loss_masked: the target must be fp32 of shape (B, H, W) (got {} {})".format(
-                target.dtype, tuple(target.shape)))
-        p, t = pred.contiguous(), target.contiguous()  # (one channel: NCHW and NHWC are the same memory)
-        B, _, h, w = p.shape
-        H, W = t.shape[1], t.shape[2]
-        cfg = (B, h, w, H, W, float(valid_min), float(valid_max))
-        out = _vec(p, 3)
-        ws = _ws(p, lib.query("nasseg_berhu_masked_workspace"))
-        if rows is None:
-            lib.call(_k("nasseg_berhu_masked_fwd", p), ptr(p), ptr(t), *cfg, ptr(out), ptr(ws), current_stream())
-            ctx.save_for_backward(p, t, out)
+    def forward(ctx, pred, target, valid_min, valid_max, sampling, group, terms, rows):
+        up = sampling == "up"
+        who = "depth_criterion" if terms is not None else "berhu_loss_upsampled" if up else "berhu_loss_masked"
+        if sampling not in ("masked", "up") or (up and terms is not None):
+            raise NassegError("depth_criterion: sampling is \"masked\" or \"up\" (got {!r}), and the scale-invariant "
+                              "and gradient-matching terms are defined at the prediction's size only".format(sampling))
+        p, t, rows, n_rows, dims = _depth_inputs(who, pred, target, rows)
+        if up:
+            base, n_ws = "nasseg_berhu_up", lib.query("nasseg_berhu_up_workspace", *dims)
+            if n_ws <= 0:
+                raise NassegError("berhu_loss_upsampled: prediction {} against target {} is empty or exceeds "
+                                  "B*H*W < 2^32, B*h*w < 2^31".format(tuple(pred.shape), tuple(target.shape)))
         else:
-            lib.call(_k("nasseg_berhu_masked_rows_fwd", p), ptr(p), ptr(t), ptr(rows), n_rows, *cfg, ptr(out), ptr(ws),
-                     current_stream())
-            ctx.save_for_backward(p, t, out, rows)
-        ctx.n_rows = n_rows
-        ctx.cfg = cfg
-        # The loss is out[0] under a tensor of its own, not a view of ``out``: a caller may update it in place
-        # (``loss += aux_weight * aux_loss``, the reference's idiom) - autograd refuses that on a view made inside a
-        # Function - and nothing is copied (a 4-byte copy node in a recorded step cannot be re-created, graph_dag.py).
-        # backward reads c and n_valid (out[1], out[2]) only.
-        return torch.empty(0, device=p.device, dtype=torch.float32).set_(out.untyped_storage(), out.storage_offset(),
-                                                                          (), ())
+            base, n_ws = "nasseg_berhu_masked", lib.query("nasseg_berhu_masked_workspace")
+        geom = dims + (float(valid_min), float(valid_max))
+        stats, ws = _vec(p, 3), _ws(p, n_ws)
+        name, table = _depth_entry(base, "_fwd", p, rows, n_rows)
+        lib.call(name, ptr(p), ptr(t), *table, *geom, ptr(stats), ptr(ws), current_stream())
+        resid = out = None
+        if terms is None:
+            cfg = geom + ((int(group),) if up else ())
+            parts = _DepthParts(_own_scalar(stats, 0), None, _own_scalar(stats, 1), _own_scalar(stats, 2), None, None)
+        else:
+            bw, sw, lam, gw, scales, pmin = terms
+            base, cfg = "nasseg_depth_terms", geom + (pmin, lam, scales, bw, sw, gw)
+            resid, out = torch.empty(dims[:3], device=p.device, dtype=torch.float32), _vec(p, 16)
+            ws = _ws(p, lib.query("nasseg_depth_terms_workspace"))
+            name, table = _depth_entry(base, "_fwd", p, rows, n_rows)
+            lib.call(name, ptr(p), ptr(t), *table, *geom, pmin, lam, scales, ptr(stats), bw, sw, gw, ptr(resid),
+                     ptr(out), ptr(ws), current_stream())
+            parts = _DepthParts(_own_scalar(out, 0), _own_scalar(stats, 0), None, _own_scalar(out, 3),
+                                _own_scalar(out, 1), _own_scalar(out, 2))
+        ctx.save_for_backward(p, t, stats, rows, resid, out)
+        ctx.cfg = (base, n_rows, cfg)  # (base: the backward's entry point)
+        ctx.mark_non_differentiable(*[o for o in parts[1:] if o is not None])
+        ctx.set_materialize_grads(False)  # (no zero-fill launch per part that backward ignores)
+        return tuple(parts)
 
     @staticmethod
-    def backward(ctx, g):
-        p, t, out = ctx.saved_tensors[:3]
-        g = g.to(torch.float32).contiguous().view(1)
+    def backward(ctx, g, *unused):
+        p, t, stats, rows, resid, out = ctx.saved_tensors
+        base, n_rows, cfg = ctx.cfg
+        g = _upstream(g)
         d = torch.empty_like(p)
-        if ctx.n_rows is None:
-            lib.call(_k("nasseg_berhu_masked_bwd", p), ptr(p), ptr(t), ptr(out), ptr(g), *ctx.cfg, ptr(d),
-                     current_stream())
-            return d, None, None, None
-        lib.call(_k("nasseg_berhu_masked_rows_bwd", p), ptr(p), ptr(t), ptr(ctx.saved_tensors[3]), ctx.n_rows, ptr(out),
-                 ptr(g), *ctx.cfg, ptr(d), current_stream())
-        return d, None, None, None, None
+        name, table = _depth_entry(base, "_bwd", p, rows, n_rows)
+        kept = (ptr(stats),) if out is None else (ptr(resid), ptr(stats), ptr(out))
+        lib.call(name, ptr(p), ptr(t), *table, *kept, ptr(g), *cfg, ptr(d), current_stream())
+        return (d,) + (None,) * 7
+
+
+def _depth_criterion(pred, target, valid_min, valid_max, sampling="masked", group=0, terms=None, rows=None):
+    return _DepthParts(*_DepthCriterion.apply(pred, target, valid_min, valid_max, sampling, group, terms, rows))
 
 
 def berhu_loss_masked(pred, target, valid_min=0.0, valid_max=float("inf"), rows=None):
@@ -3063,61 +3110,7 @@ def berhu_loss_masked(pred, target, valid_min=0.0, valid_max=float("inf"), rows=
     ``rows`` (an int64 device tensor of B entries): ``target`` is a cache (N, H, W), fp32 and contiguous, and image b
     meets ``target[rows[b]]`` - read in place by the kernels, bit for bit the call on the gathered ``target[rows]``,
     which is never made (the task0 depth cache, engine/trainer.py).  Repeated and unordered rows are legal."""
-    if rows is None:
-        return _BerHuMasked.apply(pred, target, valid_min, valid_max)
-    return _BerHuMasked.apply(pred, target, valid_min, valid_max, rows)
-
-
-class _BerHuUpsampled(torch.autograd.Function):
-    """nasseg_berhu_up_fwd / _bwd.  Outputs: the loss (a scalar of its own), and - not differentiable - c and n_valid
-    (0-dim, fp32).  ``group``: the backward's lanes per prediction pixel (0: from the shapes)"""
-
-    @staticmethod
-    def forward(ctx, pred, target, valid_min, valid_max, group, rows=None):
-        n_rows = None if rows is None else _cache_rows("berhu_loss_upsampled", pred, target, rows)
-        require_device(pred, target)
-        if pred.dtype not in (torch.float32, torch.bfloat16) or pred.dim() != 4 or pred.shape[1] != 1:
-            raise NassegError("berhu_loss_upsampled: the prediction must be fp32 or bf16 of shape (B, 1, h, w) "
-                              "(got {} {})".format(pred.dtype, tuple(pred.shape)))
-        if target.dtype != torch.float32 or target.dim() != 3 or (rows is None and target.shape[0] != pred.shape[0]):
-            raise NassegError("berhu_loss_upsampled: the target must be fp32 of shape (B, H, W) (got {} {})".format(
-                target.dtype, tuple(target.shape)))
-        p, t = pred.contiguous(), target.contiguous()  # (one channel: NCHW and NHWC are the same memory)
-        B, _, h, w = p.shape
-        H, W = int(t.shape[1]), int(t.shape[2])
-        n_ws = lib.query("nasseg_berhu_up_workspace", B, h, w, H, W)
-        if n_ws <= 0:
-            raise NassegError("berhu_loss_upsampled: prediction {} against target {} is empty or exceeds "
-                              "B*H*W < 2^32, B*h*w < 2^31".format(tuple(pred.shape), tuple(target.shape)))
-        cfg = (B, h, w, H, W, float(valid_min), float(valid_max))
-        out = _vec(p, 3)
-        ws = _ws(p, n_ws)
-        if rows is None:
-            lib.call(_k("nasseg_berhu_up_fwd", p), ptr(p), ptr(t), *cfg, ptr(out), ptr(ws), current_stream())
-            ctx.save_for_backward(p, t, out)
-        else:
-            lib.call(_k("nasseg_berhu_up_rows_fwd", p), ptr(p), ptr(t), ptr(rows), n_rows, *cfg, ptr(out), ptr(ws),
-                     current_stream())
-            ctx.save_for_backward(p, t, out, rows)
-        ctx.n_rows = n_rows
-        ctx.cfg = cfg + (int(group),)
-        # (the loss under a tensor of its own, as _BerHuMasked.forward returns it: it may be updated in place;
-        #  backward reads out[1], out[2] only)
-        c, n_valid = _own_scalar(out, 1), _own_scalar(out, 2)
-        ctx.mark_non_differentiable(c, n_valid)
-        return _own_scalar(out, 0), c, n_valid
-
-    @staticmethod
-    def backward(ctx, g, *unused):
-        p, t, out = ctx.saved_tensors[:3]
-        g = g.to(torch.float32).contiguous().view(1)
-        d = torch.empty_like(p)
-        if ctx.n_rows is None:
-            lib.call(_k("nasseg_berhu_up_bwd", p), ptr(p), ptr(t), ptr(out), ptr(g), *ctx.cfg, ptr(d), current_stream())
-            return d, None, None, None, None
-        lib.call(_k("nasseg_berhu_up_rows_bwd", p), ptr(p), ptr(t), ptr(ctx.saved_tensors[3]), ctx.n_rows, ptr(out),
-                 ptr(g), *ctx.cfg, ptr(d), current_stream())
-        return d, None, None, None, None, None
+    return _depth_criterion(pred, target, valid_min, valid_max, rows=rows).loss
 
 
 def berhu_loss_upsampled(pred, target, valid_min=0.0, valid_max=float("inf"), return_parts=False, rows=None):
@@ -3135,11 +3128,8 @@ def berhu_loss_upsampled(pred, target, valid_min=0.0, valid_max=float("inf"), re
     No host synchronisation: capturable.
     ``rows``: as in ``berhu_loss_masked`` - ``target`` is a cache (N, H, W) read in place through the B cache rows;
     B*H*W < 2^32 bounds the batch, the cache may be larger."""
-    if rows is None:
-        out = _BerHuUpsampled.apply(pred, target, valid_min, valid_max, 0)
-    else:
-        out = _BerHuUpsampled.apply(pred, target, valid_min, valid_max, 0, rows)
-    return out if return_parts else out[0]
+    out = _depth_criterion(pred, target, valid_min, valid_max, "up", rows=rows)
+    return (out.loss, out.c, out.n_valid) if return_parts else out.loss
 
 
 def _depth_terms_config(who, valid_min, berhu_weight, silog_weight, silog_lambda, grad_weight, grad_scales, pred_min):
@@ -3168,55 +3158,6 @@ def _depth_terms_config(who, valid_min, berhu_weight, silog_weight, silog_lambda
     return bw, sw, lam, gw, (0 if grad_weight is None else int(grad_scales)), pmin
 
 
-class _DepthCriterion(torch.autograd.Function):
-    """nasseg_berhu_masked_fwd + nasseg_depth_terms_fwd / nasseg_depth_terms_bwd; with ``rows`` their row-indexed
-    twins on the cache ``target``.  Outputs: the total (a scalar of its own) and - not differentiable - berHu, D,
-    L_gm and n_valid (0-dim, fp32).  ``terms``: _depth_terms_config's tuple"""
-
-    @staticmethod
-    def forward(ctx, pred, target, valid_min, valid_max, terms, rows=None):
-        n_rows = None if rows is None else _cache_rows("depth_criterion", pred, target, rows)
-        require_device(pred, target)
-        if pred.dtype not in (torch.float32, torch.bfloat16) or pred.dim() != 4 or pred.shape[1] != 1:
-            raise NassegError("depth_criterion: the prediction must be fp32 or bf16 of shape (B, 1, h, w) (got {} {})"
-                              .format(pred.dtype, tuple(pred.shape)))
-        if target.dtype != torch.float32 or target.dim() != 3 or (rows is None and target.shape[0] != pred.shape[0]):
-            raise NassegError("depth_criterion: the target must be fp32 of shape (B, H, W) (got {} {})".format(
-                target.dtype, tuple(target.shape)))
-        p, t = pred.contiguous(), target.contiguous()  # (one channel: NCHW and NHWC are the same memory)
-        B, _, h, w = p.shape
-        geom = (B, h, w, int(t.shape[1]), int(t.shape[2]), float(valid_min), float(valid_max))
-        bw, sw, lam, gw, scales, pmin = terms
-        berhu, out = _vec(p, 3), _vec(p, 16)
-        resid = torch.empty((B, h, w), device=p.device, dtype=torch.float32)
-        ws_b = _ws(p, lib.query("nasseg_berhu_masked_workspace"))
-        ws_t = _ws(p, lib.query("nasseg_depth_terms_workspace"))
-        table = () if rows is None else (ptr(rows), n_rows)
-        mid = "_rows" if rows is not None else ""
-        stream = current_stream()
-        lib.call(_k("nasseg_berhu_masked{}_fwd".format(mid), p), ptr(p), ptr(t), *table, *geom, ptr(berhu), ptr(ws_b),
-                 stream)
-        lib.call(_k("nasseg_depth_terms{}_fwd".format(mid), p), ptr(p), ptr(t), *table, *geom, pmin, lam, scales,
-                 ptr(berhu), bw, sw, gw, ptr(resid), ptr(out), ptr(ws_t), stream)
-        ctx.save_for_backward(*((p, t, resid, berhu, out) + (() if rows is None else (rows,))))
-        ctx.n_rows, ctx.mid = n_rows, mid
-        ctx.cfg = geom + (pmin, lam, scales, bw, sw, gw)
-        # (the total under a tensor of its own, as _BerHuMasked.forward returns its loss: it may be updated in place)
-        parts = (_own_scalar(berhu, 0), _own_scalar(out, 1), _own_scalar(out, 2), _own_scalar(out, 3))
-        ctx.mark_non_differentiable(*parts)
-        return (_own_scalar(out, 0),) + parts
-
-    @staticmethod
-    def backward(ctx, g, *unused):
-        p, t, resid, berhu, out = ctx.saved_tensors[:5]
-        g = g.to(torch.float32).contiguous().view(1)
-        d = torch.empty_like(p)
-        table = () if ctx.n_rows is None else (ptr(ctx.saved_tensors[5]), ctx.n_rows)
-        lib.call(_k("nasseg_depth_terms{}_bwd".format(ctx.mid), p), ptr(p), ptr(t), *table, ptr(resid), ptr(berhu),
-                 ptr(out), ptr(g), *ctx.cfg, ptr(d), current_stream())
-        return (d, None, None, None, None) + (() if ctx.n_rows is None else (None,))
-
-
 def depth_criterion(pred, target, valid_min=0.0, valid_max=float("inf"), berhu_weight=1.0, silog_weight=None,
                     silog_lambda=0.5, grad_weight=None, grad_scales=4, pred_min=1e-3, rows=None, return_parts=False):
     """The depth criterion that matches the depth score: ``berhu_weight * berHu + silog_weight * D + grad_weight *
@@ -3240,11 +3181,8 @@ def depth_criterion(pred, target, valid_min=0.0, valid_max=float("inf"), berhu_w
     inputs give the same bits.  ``rows``: as in ``berhu_loss_masked``."""
     terms = _depth_terms_config("depth_criterion", valid_min, berhu_weight, silog_weight, silog_lambda, grad_weight,
                                 grad_scales, pred_min)
-    if rows is None:
-        out = _DepthCriterion.apply(pred, target, valid_min, valid_max, terms)
-    else:
-        out = _DepthCriterion.apply(pred, target, valid_min, valid_max, terms, rows)
-    return out if return_parts else out[0]
+    out = _depth_criterion(pred, target, valid_min, valid_max, terms=terms, rows=rows)
+    return (out.loss, out.berhu, out.silog, out.grad_match, out.n_valid) if return_parts else out.loss
 
 
 def depth_metrics(pred, gt, min_depth=1e-3, max_depth=10.0, acc=None):

@@ -72,15 +72,8 @@ def run(family, pred, target, rows=None, group=0, scale=2.5):
     """-> (loss, c, n_valid, dpred) of one forward + backward, ``scale`` applied upstream"""
     F = Fn()
     p = pred.clone().requires_grad_(True)
-    extra = () if rows is None else (rows,)
-    if family == "up":
-        loss, c, n = F._BerHuUpsampled.apply(p, target, 0.0, VMAX, group, *extra)
-    else:
-        loss = F.berhu_loss_masked(p, target, 0.0, VMAX) if rows is None else F.berhu_loss_masked(
-            p, target, 0.0, VMAX, rows=rows)
-        stats = loss.grad_fn.saved_tensors[2].clone()  # (out = {loss, c, n_valid})
-        assert float(stats[0]) == float(loss)
-        c, n = stats[1], stats[2]
+    parts = F._depth_criterion(p, target, 0.0, VMAX, family, group, rows=rows)
+    loss, c, n = parts.loss, parts.c, parts.n_valid
     (scale * loss).backward()
     return loss.detach().clone(), c.detach().clone(), n.detach().clone(), p.grad
 

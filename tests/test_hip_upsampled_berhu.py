@@ -34,7 +34,8 @@ def run_gpu(pred, gt, valid_max=INF, scale=U.GRAD_SCALE, group=None):
     if group is None:
         out, c, n = F().berhu_loss_upsampled(pg, gt.to(DEV), 0.0, valid_max, return_parts=True)
     else:
-        out, c, n = F()._BerHuUpsampled.apply(pg, gt.to(DEV), 0.0, valid_max, group)
+        parts = F()._depth_criterion(pg, gt.to(DEV), 0.0, valid_max, "up", group)
+        out, c, n = parts.loss, parts.c, parts.n_valid
     assert out.dim() == 0 and out.dtype == torch.float32 and not c.requires_grad and not n.requires_grad
     (out * scale).backward()
     return float(out.detach()), pg.grad.cpu(), float(c), float(n)
@@ -166,7 +167,7 @@ def test_upsampled_berhu_edge_cases_and_in_place_use():
     with pytest.raises(RuntimeError):  # (a NaN bound)
         Fn.berhu_loss_upsampled(pred.to(DEV), gt.to(DEV), valid_max=float("nan"))
     with pytest.raises(RuntimeError):  # (a group size the backward does not have)
-        Fn._BerHuUpsampled.apply(pred.clone().to(DEV).requires_grad_(True), gt.to(DEV), 0.0, INF, 8)[0].backward()
+        Fn._depth_criterion(pred.clone().to(DEV).requires_grad_(True), gt.to(DEV), 0.0, INF, "up", 8).loss.backward()
 
 
 @pytest.mark.parametrize("case", [(1, 3, 4, 96, 128), (2, 33, 47, 130, 187)], ids=str)
