@@ -545,6 +545,26 @@ int nasseg_ce_up_bwd(const float* logits, const void* target, int elem_size, con
                      const float* pixel_loss, const float* lse, const float* stats, const float* gscale, int B, int h,
                      int w, int C, int H, int W, int ignore, float* dlogits, void* stream);
 
+/* Row-indexed twins of the two entry points above, for labels that live in a cache (the task0 cache's full-size
+ * labels, engine/trainer.py: populate_task0(full_size_labels=True)): target is the WHOLE cache, uint8 / int64
+ * [n_rows][H][W], and rows a DEVICE array of B cache rows - the index nasseg_gather_rows takes; image b of the logits
+ * meets target[clamp(rows[b], 0, n_rows - 1)] (the clamp is a memory-safety net only: the host checks the range).
+ * Repeated and unordered rows are legal.  pixel_loss and lse stay the batch's, [B][H][W]; the workspace is
+ * nasseg_ce_up_workspace(B, h, w, C, H, W).  Everything else - validity, selection, loss, stats, counts, the NaN rule,
+ * the backward - is as above, and so is every bit: the result is that of the un-indexed entry point on a gathered copy
+ * target[rows] (the same kernels, launch geometry, order of sums and finalize; only the address of an image's labels
+ * differs - in the forward, in the weighted sum pass and in the backward's gather), which is never written.  The
+ * limits above bound the BATCH; the cache may be larger (rows[b]*H*W is 64-bit).  Neither the cache nor the table is
+ * written. */
+int nasseg_ce_up_rows_fwd(const float* logits, const void* target, int elem_size, const int64_t* rows, int64_t n_rows,
+                          const float* weight, int B, int h, int w, int C, int H, int W, int ignore, int select,
+                          float t_loss, int64_t min_kept, double keep_fraction, float* loss, float* stats,
+                          int64_t* counts, float* pixel_loss, float* lse, float* ws, void* stream);
+int nasseg_ce_up_rows_bwd(const float* logits, const void* target, int elem_size, const int64_t* rows, int64_t n_rows,
+                          const float* weight, const float* pixel_loss, const float* lse, const float* stats,
+                          const float* gscale, int B, int h, int w, int C, int H, int W, int ignore, float* dlogits,
+                          void* stream);
+
 /* Lovasz-Softmax term (Berman, Triggs, Blaschko, CVPR 2018; absent from the reference): the convex extension of the
  * Jaccard loss, the surrogate of the mean IoU the reward is built from.  Logits [P][C], labels [P]; pixel p is valid
  * iff its label t != ignore and 0 <= t < C; n = valid pixels, y_pc = [t_p == c], N_c = sum_p y_pc.
@@ -1056,6 +1076,15 @@ int nasseg_bf16_ce_up_fwd(const nasseg_bf16_t* logits, const void* target, int e
 int nasseg_bf16_ce_up_bwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* weight,
                           const float* pixel_loss, const float* lse, const float* stats, const float* gscale, int B,
                           int h, int w, int C, int H, int W, int ignore, nasseg_bf16_t* dlogits, void* stream);
+int nasseg_bf16_ce_up_rows_fwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const int64_t* rows,
+                               int64_t n_rows, const float* weight, int B, int h, int w, int C, int H, int W,
+                               int ignore, int select, float t_loss, int64_t min_kept, double keep_fraction,
+                               float* loss, float* stats, int64_t* counts, float* pixel_loss, float* lse, float* ws,
+                               void* stream);
+int nasseg_bf16_ce_up_rows_bwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const int64_t* rows,
+                               int64_t n_rows, const float* weight, const float* pixel_loss, const float* lse,
+                               const float* stats, const float* gscale, int B, int h, int w, int C, int H, int W,
+                               int ignore, nasseg_bf16_t* dlogits, void* stream);
 int nasseg_bf16_lovasz_fwd(const nasseg_bf16_t* logits, const void* target, int elem_size, int64_t P, int C,
                            int ignore, int all_classes, double lovasz_weight, const float* base_loss, float* loss,
                            float* loss_lovasz, float* errors, float* coef, int* rank, int64_t* ncls, float* ws,

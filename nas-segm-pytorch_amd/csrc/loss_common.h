@@ -26,6 +26,51 @@ __device__ __forceinline__ bool label_valid(int64_t t, int C, int ignore) {
   return !NASSEG_LABEL_SKIPPED(t, C, ignore);
 }
 
+// A ROW TABLE over the labels (nasseg_ce_up_rows_*; as RowTable of csrc/depth.hip): the labels are a cache
+// [n_rows][hw] and image b of the batch is its row rows[b], clamped to the cache as nasseg_gather_rows clamps it (a
+// memory-safety net: the host checks).  The kernels that read labels take it as a trailing parameter pack `Rows... lr`
+// that is empty or one LabelRows: empty, image b of the labels is image b and the kernel - the one the un-indexed
+// entry points launch - has neither an argument nor an instruction for it.
+struct LabelRows {
+  const int64_t* rows;
+  int64_t n_rows;
+  uint32_t hw;  // label pixels per image (the batch holds fewer than 2^32)
+};
+
+template <typename TL>
+__device__ __forceinline__ const TL* label_image(const TL* __restrict__ target, int64_t b, const LabelRows& lr) {
+  int64_t r = lr.rows[b];
+  r = r < 0 ? 0 : (r >= lr.n_rows ? lr.n_rows - 1 : r);
+  return target + r * (int64_t)lr.hw;  // (64-bit: the cache may hold more than 2^32 pixels)
+}
+
+// the base from which pixel p of the BATCH (its flat index, image b's among them) has its label at base[p]: the cache
+// image's start less b images.  Formed as an integer - the base itself may lie outside the cache, base[p] never does.
+template <typename TL>
+__device__ __forceinline__ const TL* label_base(const TL* __restrict__ target, int64_t b, const LabelRows& lr) {
+  const uintptr_t image = reinterpret_cast<uintptr_t>(label_image(target, b, lr));
+  return reinterpret_cast<const TL*>(image - (uintptr_t)(b * (int64_t)lr.hw) * sizeof(TL));
+}
+
+// pixel p of the batch (p < 2^32 with a table) -> its image b, and returned its offset within the image
+__device__ __forceinline__ uint32_t label_decode(uint32_t p, int& b, const LabelRows& lr) {
+  const uint32_t i = p / lr.hw;
+  b = (int)i;
+  return p - i * lr.hw;
+}
+
+// label of pixel p of the batch: the batch's own, or - with a table - that of the cache image its image selects
+template <typename TL>
+__device__ __forceinline__ int64_t label_at(const TL* __restrict__ target, int64_t p) {
+  return (int64_t)target[p];
+}
+template <typename TL>
+__device__ __forceinline__ int64_t label_at(const TL* __restrict__ target, int64_t p, const LabelRows& lr) {
+  int b;
+  const uint32_t off = label_decode((uint32_t)p, b, lr);
+  return (int64_t)label_image(target, (int64_t)b, lr)[off];
+}
+
 constexpr int kCeGridCap = 1024;  // workgroups of a pass over the pixels = rows of its partials
 constexpr int kCeTileMaxC = 63;   // classes up to which a tile of 256 pixels is staged through LDS
 
@@ -33,12 +78,13 @@ constexpr int kCeTileMaxC = 63;   // classes up to which a tile of 256 pixels is
 // Sum pass over pixel_loss + labels: partial[b] = {sum w l, sum w, count} over the kept pixels of workgroup b, with
 // the pixel -> (workgroup, thread) mapping, the accumulation order and the tree of ce_fwd_kernel: with unit weights
 // and everything kept, the very sums of nasseg_ce_fwd.  tau == nullptr: no selection, every valid pixel is kept.
-template <typename TL>
+// lr: the labels behind a row table (P < 2^32) - only the address of a pixel's label differs.
+template <typename TL, typename... Rows>
 __global__ __launch_bounds__(256) void ce_sel_sum_kernel(const float* __restrict__ pixel_loss,
                                                          const TL* __restrict__ target,
                                                          const float* __restrict__ weight, int64_t P,
                                                          const float* __restrict__ tau,
-                                                         float* __restrict__ partial) {
+                                                         float* __restrict__ partial, Rows... lr) {
   __shared__ float red_l[256];
   __shared__ float red_w[256];
   __shared__ float red_n[256];
@@ -47,7 +93,7 @@ __global__ __launch_bounds__(256) void ce_sel_sum_kernel(const float* __restrict
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
     const float l = pixel_loss[p];
     if (!sel_kept(l, t)) continue;
-    const float w = weight ? weight[(int64_t)target[p]] : 1.f;  // (l >= 0: the label is in [0, C))
+    const float w = weight ? weight[label_at(target, p, lr...)] : 1.f;  // (l >= 0: the label is in [0, C))
     loss += w * l;
     sw += w;
     cnt += 1.f;
@@ -180,17 +226,18 @@ inline int check_selection(const char* who, int select, int64_t min_kept, double
 #ifndef NASSEG_LOSS_NO_SUM_PASS
 // What follows the pass that wrote pixel_loss: the selection (`selection(tau, counts)`, when `select`), the sum pass
 // into ws = [kCeGridCap][3] partials and - unless the caller's own finalizer reads them (fin_name == nullptr) - the
-// fp64 finalize.
-template <typename Sel>
+// fp64 finalize.  lr: the row table the labels are read through (none: `target` is the batch's own labels).
+template <typename Sel, typename... Rows>
 inline int ce_sel_reduce(const char* sum_name, const char* fin_name, Sel&& selection, const float* pixel_loss,
                          const void* target, int elem_size, const float* weight, int64_t P, int select,
-                         float* loss, float* stats, int64_t* counts, float* ws, hipStream_t s) {
+                         float* loss, float* stats, int64_t* counts, float* ws, hipStream_t s, Rows... lr) {
+  static_assert(sizeof...(Rows) <= 1, "no table, or one LabelRows");
   const int grid = ce_grid(P);
   if (select) NASSEG_TRY(selection(stats + 1, counts));
   const float* tau = select ? stats + 1 : nullptr;
   with_labels(target, elem_size, [&](auto labels) {
-    hipLaunchKernelGGL(ce_sel_sum_kernel<label_of<decltype(labels)>>, dim3(grid), dim3(256), 0, s, pixel_loss, labels,
-                       weight, P, tau, ws);
+    hipLaunchKernelGGL((ce_sel_sum_kernel<label_of<decltype(labels)>, Rows...>), dim3(grid), dim3(256), 0, s,
+                       pixel_loss, labels, weight, P, tau, ws, lr...);
   });
   NASSEG_LAUNCH_CHECK(sum_name);
   if (fin_name) {

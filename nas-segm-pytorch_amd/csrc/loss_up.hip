@@ -14,6 +14,10 @@
 //             of <= kUpChunk channels, stages tile + halo of the logits in LDS (row stride cn | 1 floats: odd), and every
 //             thread walks the label pixels of ITS (pixel, channel) in a fixed order: re-interpolates its channel,
 //             exp(v - lse) - onehot, times the pixel's factor and Wy Wx.  dlogits is written once; no atomics.
+// Every pass exists once, as a template on an optional ROW TABLE (nasseg_ce_up_rows_*; `Rows... lr`: LabelRows,
+// csrc/loss_common.h): image b of the logits then meets image rows[b] of a label cache - the task0 cache - instead of
+// image b of the labels; only the address of an image's labels differs, so both forms give the same bits and the
+// batch's labels are never gathered into a copy.
 #include <math.h>
 
 #include "loss_common.h"
@@ -25,23 +29,34 @@ constexpr int kUpTile = 8;        // backward: logits pixels per tile side
 constexpr int kUpPatch = kUpTile + 2;
 constexpr int kUpChunk = 64;      // backward: channels per workgroup
 
-template <typename TL>
+template <typename TL, typename... Rows>
 __global__ __launch_bounds__(256) void ce_up_fwd_kernel(const act_t* __restrict__ logits, const TL* __restrict__ target,
                                                         int B, int h, int w, int C, int H, int W, float sh, float sw,
                                                         int ignore, float* __restrict__ pixel_loss,
-                                                        float* __restrict__ lse_out) {
+                                                        float* __restrict__ lse_out, Rows... lr) {
   const int64_t P = (int64_t)B * H * W;
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
-    const int64_t t = (int64_t)target[p];
+    int X, Y, b;
+    int64_t t;
+    if constexpr (sizeof...(Rows) != 0) {  // (the label's address needs b: decoded first - in 32 bits, p < 2^32)
+      const uint32_t off = label_decode((uint32_t)p, b, lr...);
+      Y = (int)(off / (uint32_t)W);
+      X = (int)(off - (uint32_t)Y * (uint32_t)W);
+      t = (int64_t)label_image(target, (int64_t)b, lr...)[off];
+    } else {
+      t = (int64_t)target[p];
+    }
     if (NASSEG_LABEL_SKIPPED(t, C, ignore)) {
       pixel_loss[p] = -1.f;
       lse_out[p] = 0.f;
       continue;
     }
-    const int X = (int)(p % W);
-    const int64_t q = p / W;
-    const int Y = (int)(q % H);
-    const int b = (int)(q / H);
+    if constexpr (sizeof...(Rows) == 0) {
+      X = (int)(p % W);
+      const int64_t q = p / W;
+      Y = (int)(q % H);
+      b = (int)(q / H);
+    }
     const Lin ly = lin_coeff(Y, sh, h, H);
     const Lin lx = lin_coeff(X, sw, w, W);
     const act_t* lb = logits + (int64_t)b * h * w * C;
@@ -65,14 +80,15 @@ __global__ __launch_bounds__(256) void ce_up_fwd_kernel(const act_t* __restrict_
 // grid: (channel chunk, tile x, tile y, image), flattened, chunk fastest.  VEC: the patch is staged with 16-byte
 // (bf16: 8-byte) loads - one chunk (C <= kUpChunk) and 16-byte aligned logits; else element by element.
 // LDS: patch[kUpPatch][kUpPatch][cn | 1] floats.
-template <typename TL, bool VEC>
+template <typename TL, bool VEC, typename... Rows>
 __global__ __launch_bounds__(256) void ce_up_bwd_kernel(const act_t* __restrict__ logits, const TL* __restrict__ target,
                                                         const float* __restrict__ weight,
                                                         const float* __restrict__ pixel_loss,
                                                         const float* __restrict__ lse, const float* __restrict__ stats,
                                                         const float* __restrict__ gscale, int B, int h, int w, int C,
                                                         int H, int W, float sh, float sw, int tiles_y, int tiles_x,
-                                                        int nchunk, act_t* __restrict__ dlogits) {
+                                                        int nchunk, act_t* __restrict__ dlogits, Rows... lr) {
+  constexpr bool kRows = sizeof...(Rows) != 0;
   extern __shared__ float patch[];
   const int tid = threadIdx.x;
   int wi = blockIdx.x;
@@ -134,6 +150,10 @@ __global__ __launch_bounds__(256) void ce_up_bwd_kernel(const act_t* __restrict_
   __syncthreads();
   const float g = gscale ? gscale[0] : 1.f;
   const float sumw = stats[0], tau = stats[1];
+  // (with a table: pixel p of the batch has its label (rows[b] - b) images further on in the cache - one scalar load
+  //  of the table per workgroup, and every visit reads the address it read without one, from another base)
+  const TL* tbase = target;
+  if constexpr (kRows) tbase = label_base(target, (int64_t)b, lr...);
   for (int item = tid; item < ny * nx * cn; item += 256) {
     const int pix = item / cn, c = item - pix * cn;
     const int iy = pix / nx, jx = pix - iy * nx;
@@ -155,7 +175,7 @@ __global__ __launch_bounds__(256) void ce_up_bwd_kernel(const act_t* __restrict_
         if (wx == 0.f) continue;
         const int64_t p = prow + X;
         if (!sel_kept(pixel_loss[p], tau)) continue;  // (-1 on pixels that are not valid)
-        const int64_t t = (int64_t)target[p];
+        const int64_t t = (int64_t)tbase[p];
         const float gp = (g * (weight ? weight[t] : 1.f)) / sumw;
         const int a0 = (lx.i0 - ox) * CS, a1 = (lx.i1 - ox) * CS;
         const float v = up_interp(r0[a0], r0[a1], r1[a0], r1[a1], ly, lx);
@@ -176,6 +196,78 @@ inline bool up_shape_ok(int B, int h, int w, int C, int H, int W) {
   return true;
 }
 
+#define UP_SHAPE_CHECK(who)                          \
+  NASSEG_REQUIRE(up_shape_ok(B, h, w, C, H, W),      \
+                 "%s: bad shape (C >= 2, B*H*W < 2^32, B*h*w*C < 2^31, fewer than 2^24 backward tiles)", who)
+
+// Launches: one body per entry-point pair.  lr empty: target is the batch's own [B][H][W] labels; one LabelRows: the
+// cache [n_rows][H][W] and the device table of B rows.  Same geometry, same order of sums, same finalize.
+inline bool rows_ok() { return true; }
+inline bool rows_ok(const LabelRows& lr) { return lr.rows && lr.n_rows > 0; }
+#define ROWS_CHECK(who) \
+  NASSEG_REQUIRE(rows_ok(lr...), "%s: a row table of B entries and n_rows > 0 are expected", who)
+// (H*W < 2^32: up_shape_ok, which every launch body checks first)
+inline LabelRows label_rows(const int64_t* rows, int64_t n_rows, int H, int W) {
+  return {rows, n_rows, (uint32_t)((int64_t)H * W)};
+}
+
+template <typename... Rows>
+int up_fwd(const char* who, const act_t* logits, const void* target, int elem_size, const float* weight, int B, int h,
+           int w, int C, int H, int W, int ignore, int select, float t_loss, int64_t min_kept, double keep_fraction,
+           float* loss, float* stats, int64_t* counts, float* pixel_loss, float* lse, float* ws, void* stream,
+           Rows... lr) {
+  static_assert(sizeof...(Rows) <= 1, "no table, or one LabelRows");
+  UP_SHAPE_CHECK(who);
+  NASSEG_TRY(check_elem_size(who, elem_size));
+  NASSEG_REQUIRE(logits && target && loss && stats && counts && pixel_loss && lse && ws, "%s: null pointer", who);
+  ROWS_CHECK(who);
+  NASSEG_TRY(check_selection(who, select, min_kept, keep_fraction));
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t P = (int64_t)B * H * W;
+  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
+  with_labels(target, elem_size, [&](auto labels) {
+    hipLaunchKernelGGL((ce_up_fwd_kernel<label_of<decltype(labels)>, Rows...>), dim3(ce_grid(P)), dim3(256), 0, s,
+                       logits, labels, B, h, w, C, H, W, sh, sw, ignore, pixel_loss, lse, lr...);
+  });
+  NASSEG_LAUNCH_CHECK("ce_up_fwd");
+  const auto selection = [&](float* tau, int64_t* cnt) {  // (the stand-alone one: include/nasseg.h)
+    return nasseg_ohem_threshold(pixel_loss, P, t_loss, min_kept, keep_fraction, tau, cnt, ws + 3 * kCeGridCap, stream);
+  };
+  return ce_sel_reduce("ce_up_sum", "ce_up_finalize", selection, pixel_loss, target, elem_size, weight, P, select, loss,
+                       stats, counts, ws, s, lr...);
+}
+
+template <typename... Rows>
+int up_bwd(const char* who, const act_t* logits, const void* target, int elem_size, const float* weight,
+           const float* pixel_loss, const float* lse, const float* stats, const float* gscale, int B, int h, int w,
+           int C, int H, int W, act_t* dlogits, void* stream, Rows... lr) {
+  static_assert(sizeof...(Rows) <= 1, "no table, or one LabelRows");
+  UP_SHAPE_CHECK(who);
+  NASSEG_TRY(check_elem_size(who, elem_size));
+  NASSEG_REQUIRE(logits && target && pixel_loss && lse && stats && dlogits, "%s: null pointer", who);
+  ROWS_CHECK(who);
+  hipStream_t s = (hipStream_t)stream;
+  const int tiles_y = cdiv(h, kUpTile), tiles_x = cdiv(w, kUpTile), nchunk = cdiv(C, kUpChunk);
+  const int64_t nwg = (int64_t)B * tiles_y * tiles_x * nchunk;  // (< 2^24: up_shape_ok)
+  const int cmax = C < kUpChunk ? C : kUpChunk;
+  const size_t lds = (size_t)kUpPatch * kUpPatch * (cmax | 1) * sizeof(float);
+  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
+  const bool vec = nchunk == 1 && ((uintptr_t)logits & 15) == 0;
+  with_labels(target, elem_size, [&](auto labels) {
+    using TL = label_of<decltype(labels)>;
+    const auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(256), lds, s, logits, labels, weight, pixel_loss, lse, stats,
+                         gscale, B, h, w, C, H, W, sh, sw, tiles_y, tiles_x, nchunk, dlogits, lr...);
+    };
+    if (vec)
+      launch(ce_up_bwd_kernel<TL, true, Rows...>);
+    else
+      launch(ce_up_bwd_kernel<TL, false, Rows...>);
+  });
+  NASSEG_LAUNCH_CHECK("ce_up_bwd");
+  return NASSEG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -188,60 +280,42 @@ int64_t nasseg_ce_up_workspace(int B, int h, int w, int C, int H, int W) {
 }
 #endif
 
-#define UP_SHAPE_CHECK(who)                          \
-  NASSEG_REQUIRE(up_shape_ok(B, h, w, C, H, W), who \
-                 ": bad shape (C >= 2, B*H*W < 2^32, B*h*w*C < 2^31, fewer than 2^24 backward tiles)")
-
 int NASSEG_FN(ce_up_fwd)(const act_t* logits, const void* target, int elem_size, const float* weight, int B, int h,
                          int w, int C, int H, int W, int ignore, int select, float t_loss, int64_t min_kept,
                          double keep_fraction, float* loss, float* stats, int64_t* counts, float* pixel_loss,
                          float* lse, float* ws, void* stream) {
-  UP_SHAPE_CHECK("ce_up_fwd");
-  NASSEG_TRY(check_elem_size("ce_up_fwd", elem_size));
-  NASSEG_REQUIRE(logits && target && loss && stats && counts && pixel_loss && lse && ws, "ce_up_fwd: null pointer");
-  NASSEG_TRY(check_selection("ce_up_fwd", select, min_kept, keep_fraction));
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t P = (int64_t)B * H * W;
-  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
-  with_labels(target, elem_size, [&](auto labels) {
-    hipLaunchKernelGGL(ce_up_fwd_kernel<label_of<decltype(labels)>>, dim3(ce_grid(P)), dim3(256), 0, s, logits, labels,
-                       B, h, w, C, H, W, sh, sw, ignore, pixel_loss, lse);
-  });
-  NASSEG_LAUNCH_CHECK("ce_up_fwd");
-  const auto selection = [&](float* tau, int64_t* cnt) {  // (the stand-alone one: include/nasseg.h)
-    return nasseg_ohem_threshold(pixel_loss, P, t_loss, min_kept, keep_fraction, tau, cnt, ws + 3 * kCeGridCap, stream);
-  };
-  return ce_sel_reduce("ce_up_sum", "ce_up_finalize", selection, pixel_loss, target, elem_size, weight, P, select, loss,
-                       stats, counts, ws, s);
+  return up_fwd("ce_up_fwd", logits, target, elem_size, weight, B, h, w, C, H, W, ignore, select, t_loss, min_kept,
+                keep_fraction, loss, stats, counts, pixel_loss, lse, ws, stream);
 }
 
 int NASSEG_FN(ce_up_bwd)(const act_t* logits, const void* target, int elem_size, const float* weight,
                          const float* pixel_loss, const float* lse, const float* stats, const float* gscale, int B,
                          int h, int w, int C, int H, int W, int ignore, act_t* dlogits, void* stream) {
   (void)ignore;  // (validity is pixel_loss >= 0: the forward decided it)
-  UP_SHAPE_CHECK("ce_up_bwd");
-  NASSEG_TRY(check_elem_size("ce_up_bwd", elem_size));
-  NASSEG_REQUIRE(logits && target && pixel_loss && lse && stats && dlogits, "ce_up_bwd: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const int tiles_y = cdiv(h, kUpTile), tiles_x = cdiv(w, kUpTile), nchunk = cdiv(C, kUpChunk);
-  const int64_t nwg = (int64_t)B * tiles_y * tiles_x * nchunk;  // (< 2^24: up_shape_ok)
-  const int cmax = C < kUpChunk ? C : kUpChunk;
-  const size_t lds = (size_t)kUpPatch * kUpPatch * (cmax | 1) * sizeof(float);
-  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
-  const bool vec = nchunk == 1 && ((uintptr_t)logits & 15) == 0;
-  with_labels(target, elem_size, [&](auto labels) {
-    using TL = label_of<decltype(labels)>;
-    const auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(256), lds, s, logits, labels, weight, pixel_loss, lse, stats,
-                         gscale, B, h, w, C, H, W, sh, sw, tiles_y, tiles_x, nchunk, dlogits);
-    };
-    if (vec)
-      launch(ce_up_bwd_kernel<TL, true>);
-    else
-      launch(ce_up_bwd_kernel<TL, false>);
-  });
-  NASSEG_LAUNCH_CHECK("ce_up_bwd");
-  return NASSEG_OK;
+  return up_bwd("ce_up_bwd", logits, target, elem_size, weight, pixel_loss, lse, stats, gscale, B, h, w, C, H, W,
+                dlogits, stream);
+}
+
+// The row-indexed twins: target is the whole label cache [n_rows][H][W], rows a device array of B cache rows; image b
+// of the logits meets target[clamp(rows[b], 0, n_rows - 1)].  Everything else - and every bit - as above on
+// target[rows]; the limits of up_shape_ok are the BATCH's, the cache may be larger.
+int NASSEG_FN(ce_up_rows_fwd)(const act_t* logits, const void* target, int elem_size, const int64_t* rows,
+                              int64_t n_rows, const float* weight, int B, int h, int w, int C, int H, int W,
+                              int ignore, int select, float t_loss, int64_t min_kept, double keep_fraction,
+                              float* loss, float* stats, int64_t* counts, float* pixel_loss, float* lse, float* ws,
+                              void* stream) {
+  return up_fwd("ce_up_rows_fwd", logits, target, elem_size, weight, B, h, w, C, H, W, ignore, select, t_loss,
+                min_kept, keep_fraction, loss, stats, counts, pixel_loss, lse, ws, stream,
+                label_rows(rows, n_rows, H, W));
+}
+
+int NASSEG_FN(ce_up_rows_bwd)(const act_t* logits, const void* target, int elem_size, const int64_t* rows,
+                              int64_t n_rows, const float* weight, const float* pixel_loss, const float* lse,
+                              const float* stats, const float* gscale, int B, int h, int w, int C, int H, int W,
+                              int ignore, act_t* dlogits, void* stream) {
+  (void)ignore;
+  return up_bwd("ce_up_rows_bwd", logits, target, elem_size, weight, pixel_loss, lse, stats, gscale, B, h, w, C, H, W,
+                dlogits, stream, label_rows(rows, n_rows, H, W));
 }
 
 }  // extern "C"

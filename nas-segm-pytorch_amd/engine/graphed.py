@@ -37,8 +37,8 @@ from torch import nn
 
 from .. import functional as F
 from . import graph_dag
-from .trainer_common import (check_cache_rows, clip_and_step, inner, task0_depth_loss, task0_loss, task1_depth_loss,
-                             task1_loss)
+from .trainer_common import (check_cache_rows, clip_and_step, inner, require_full_size_labels, task0_depth_loss,
+                             task0_loss, task1_depth_loss, task1_loss)
 
 logger = logging.getLogger(__name__)
 
@@ -401,18 +401,19 @@ class GraphedTask0Step(_GraphedStep):
     ``depth_crit`` (an nn.BerHuLoss; the cache has a 'depth' entry, populate_task0(task="depth")): the depth step -
     ``task0_depth_loss``: the criterion's kernels read the full-size maps of the cache in place through the step's
     static index tensor, so the graph holds no gather of the targets; its bounds are recorded by value.
+    A full-size ``segm_crit`` (nn.SegmCrossEntropy(full_size=True); the cache has a 'y_full' entry,
+    populate_task0(full_size_labels=True)): likewise - ``task0_full_size_loss`` reads the full-size labels of the
+    cache in place through the index tensor; no head is resized and no labels are gathered.
     """
 
     def __init__(self, Xy_train, segmenter, optim_dec, batch_size, ignore_index=255, dec_grad_clip=0.0,
                  aux_weight=0, capture_optimisers=False, warmup=2, kd_coeff=None, segm_crit=None, depth_crit=None):
+        require_full_size_labels("GraphedTask0Step", Xy_train, segm_crit)
         if depth_crit is not None and (kd_coeff is not None or segm_crit is not None or "depth" not in Xy_train):
             raise ValueError("GraphedTask0Step: depth_crit needs a depth cache (populate_task0(task=\"depth\")) and "
                              "goes with neither distillation nor a segmentation criterion")
         if kd_coeff is not None and segm_crit is not None:
             raise ValueError("GraphedTask0Step: the fused distillation term exists for the plain softmax/NLL only")
-        if getattr(segm_crit, "full_size", False):
-            raise ValueError("GraphedTask0Step: a full-size criterion (SegmCrossEntropy(full_size=True)) is for the "
-                             "end-to-end step only - the task0 cache holds labels at the logits' size")
         model = inner(segmenter)
         self.cache = Xy_train
         self.optim_dec = optim_dec

@@ -60,8 +60,8 @@ def evaluate_candidate(config, train_batches, val_batches, ctrl_version="wacv", 
     hard-example mining or a region-overlap (soft Jaccard / Dice) term; None: LogSoftmax + NLL with ignore index 255.
     ``task0_epochs`` > 0: the search protocol's first stage before the ``epochs`` end-to-end ones - the encoder's
     features of every sample of ``train_batches`` are cached once (``populate_task0``; task="depth": with the
-    full-size depth maps) and the decoder alone is trained on the cache for that many epochs (``train_task0``, at the
-    batches' size, with the same criterion).  0: no such stage, exactly as before."""
+    full-size depth maps, a full-size ``segm_crit``: with the full-size labels) and the decoder alone is trained on
+    the cache for that many epochs (``train_task0``, at the batches' size, with the same criterion).  0: no such stage, exactly as before."""
     if depth_crit is not None and not isinstance(depth_crit, BerHuLoss):
         raise ValueError("evaluate_candidate: depth_crit must be an nn.BerHuLoss (got {!r})".format(depth_crit))
     if not isinstance(task0_epochs, int) or isinstance(task0_epochs, bool) or task0_epochs < 0:
@@ -118,7 +118,9 @@ def _task0_stage(segmenter, train_batches, optim_dec, crit, task0_epochs, aux, t
     epochs of ``train_task0`` at the batches' size (clip norm 3, as the end-to-end stage).  False: a RuntimeError
     inside (``try_except``) - the candidate scores 0.  The module is left in training mode, as it was built."""
     n_train = sum(int(b["image"].shape[0]) for b in train_batches)
-    cache = populate_task0(segmenter, train_batches, None, n_train, task=task)
+    # (a full-size segmentation criterion trains on the labels as they are: the cache keeps them too)
+    full = {"full_size_labels": True} if task == "segm" and getattr(crit, "full_size", False) else {}
+    cache = populate_task0(segmenter, train_batches, None, n_train, task=task, **full)
     ok = not isinstance(cache, int)  # (try_except: 0)
     for epoch in range(task0_epochs if ok else 0):
         if train_task0(cache, segmenter, optim_dec, epoch, crit, None, int(train_batches[0]["image"].shape[0]), False,

@@ -24,8 +24,8 @@ from ..helpers.utils import AverageMeter, try_except
 from ..nn.losses import BerHuLoss, SegmCrossEntropy
 from ..nn.modules import TREE_VERSION
 from . import graphed
-from .trainer_common import (cache_feature_keys, check_cache_rows, task0_depth_loss, task0_loss, task1_depth_loss,
-                             task1_loss)
+from .trainer_common import (cache_feature_keys, check_cache_rows, require_full_size_labels, task0_depth_loss,
+                             task0_loss, task1_depth_loss, task1_loss)
 from .trainer_common import clip_and_step as _clip_and_step
 from .trainer_common import inner as _inner
 
@@ -329,7 +329,7 @@ def _segmenter_stepper(segmenter, image, target, optim_enc, optim_dec, ignore, e
 
 
 @try_except
-def populate_task0(segmenter, train_loader, kd_net, n_train, do_kd=False, task="segm"):
+def populate_task0(segmenter, train_loader, kd_net, n_train, do_kd=False, task="segm", full_size_labels=False):
     """Run the encoder (eval, no grad, one image at a time) over ``n_train``
     samples and keep its feature maps, the nearest-resized labels and optionally
     the teacher's logits on the device.  Returns the cache dict
@@ -345,9 +345,18 @@ def populate_task0(segmenter, train_loader, kd_net, n_train, do_kd=False, task="
     as they arrive - full size, holes (0 / NaN / inf) included, bit for bit, nothing resized: the berHu kernels of
     the decoder-only depth step read them in place through the batch's row index (``train_task0`` with an
     nn.BerHuLoss).  All maps must share one (H, W) - the cache is one tensor - and there is no distillation term for
-    depth: otherwise ValueError."""
+    depth: otherwise ValueError.
+
+    full_size_labels=True (task="segm"): beside 'y' the cache gets 'y_full': (N, H, W), the loader's masks as they go
+    to the device - uint8 or int64, full size, bit for bit, nothing resized: the full-size cross-entropy of the
+    decoder-only step reads them in place through the batch's row index (``train_task0`` with an
+    nn.SegmCrossEntropy(full_size=True)).  All masks must share one (H, W), else ValueError; every other entry is what
+    it is without the flag.  With task="depth" (whose cache is full-size as it is) a ValueError."""
     if task not in ("segm", "depth"):
         raise ValueError("populate_task0: task must be 'segm' or 'depth' (got {!r})".format(task))
+    if full_size_labels and task == "depth":
+        raise ValueError("populate_task0: full_size_labels belongs to task=\"segm\" (the depth cache holds full-size "
+                         "maps as it is)")
     if task == "depth" and do_kd:
         raise ValueError("populate_task0: there is no distillation term for depth (do_kd with task=\"depth\")")
     cache = {}
@@ -391,6 +400,16 @@ def populate_task0(segmenter, train_loader, kd_net, n_train, do_kd=False, task="
                 labels = _labels(sample["mask"], device)
                 F.nearest_label_resize(labels, size, out=slot(
                     "y", torch.empty((1,) + tuple(size), dtype=torch.int64), seen, b))
+                if full_size_labels:
+                    if labels.dim() != 3 or labels.shape[0] != b or (
+                            "y_full" in cache and (tuple(labels.shape[1:]) != tuple(cache["y_full"].shape[1:])
+                                                   or labels.dtype != cache["y_full"].dtype)):
+                        raise ValueError("populate_task0: full-size labels of one size (b, H, W) and one dtype "
+                                         "expected - the cache is one tensor (got {} {}{})".format(
+                                             labels.dtype, tuple(labels.shape), ", cached {} {}".format(
+                                                 cache["y_full"].dtype, tuple(cache["y_full"].shape[1:]))
+                                             if "y_full" in cache else ""))
+                    slot("y_full", labels, seen, b).copy_(labels)  # (a plain device copy: every bit)
             if do_kd:
                 # (the teacher runs in fp32 whatever the candidate's activation storage)
                 store("kd_y", F.bilinear_resize(kd_net(image if image.dtype == torch.float32 else image.float()),
@@ -405,6 +424,11 @@ def populate_task0(segmenter, train_loader, kd_net, n_train, do_kd=False, task="
                     d = cache["depth"]
                     logger.info(" Depth cache: {} maps of {} x {}, fp32, {:.1f} MiB".format(
                         d.shape[0], d.shape[1], d.shape[2], d.numel() * d.element_size() / 2.0 ** 20))
+                if full_size_labels:
+                    d = cache["y_full"]
+                    logger.info(" Full-size label cache: {} maps of {} x {}, {}, {:.1f} MiB".format(
+                        d.shape[0], d.shape[1], d.shape[2], str(d.dtype).replace("torch.", ""),
+                        d.numel() * d.element_size() / 2.0 ** 20))
                 break
         else:
             for k in list(cache):  # (loader exhausted first - as in the reference, no 'out_size' then)
@@ -428,7 +452,12 @@ def make_task0_step(Xy_train, segmenter, optim_dec, batch_size, ignore_index=255
     ``depth_crit`` (an nn.BerHuLoss, on a cache with a 'depth' entry - populate_task0(task="depth")): the depth step
     instead - gather the feature rows, decoder, the criterion of every head against the full-size maps of the cache,
     read in place through the batch's rows (trainer_common.task0_depth_loss): nothing is resized, no target batch is
-    gathered; replayed or launched from the host by the same rule."""
+    gathered; replayed or launched from the host by the same rule.
+    A full-size ``segm_crit`` (nn.SegmCrossEntropy(full_size=True), on a cache with a 'y_full' entry -
+    populate_task0(full_size_labels=True); without one a ValueError): likewise, every head at its own size against
+    the full-size labels of the cache, read in place through the batch's rows (trainer_common.task0_full_size_loss);
+    with distillation the step is launched from the host and ``kd_crit`` meets the main head resized to ``out_size``."""
+    require_full_size_labels("make_task0_step", Xy_train, segm_crit)
     decoder = _inner(segmenter).decoder
     feat = Xy_train[cache_feature_keys(Xy_train)[0]]
     out_size = tuple(Xy_train["out_size"])
@@ -478,7 +507,9 @@ def train_task0(Xy_train, segmenter, optim_dec, epoch, segm_crit, kd_crit, batch
                 do_kd, kd_coeff, dec_grad_clip, do_polyak, avg_param=None, polyak_decay=0.9,
                 aux_weight=0):
     """Decoder-only epoch over the cached encoder features (trainer.py:78-175).
-    An nn.BerHuLoss on a cache with a 'depth' entry (populate_task0(task="depth")): the decoder-only DEPTH epoch."""
+    An nn.BerHuLoss on a cache with a 'depth' entry (populate_task0(task="depth")): the decoder-only DEPTH epoch.
+    An nn.SegmCrossEntropy(full_size=True) on a cache with a 'y_full' entry (populate_task0(full_size_labels=True)):
+    the loss of every head is taken at the labels' full size, where ``validate`` scores."""
     depth_crit = _depth_crit(segm_crit)
     depth_cache = "depth" in Xy_train
     if depth_crit is not None and not depth_cache:
@@ -490,9 +521,8 @@ def train_task0(Xy_train, segmenter, optim_dec, epoch, segm_crit, kd_crit, batch
                          "segm_crit (got {!r})".format(segm_crit))
     if depth_cache and do_kd:
         raise ValueError("train_task0: there is no distillation term for depth (do_kd with a depth cache)")
-    if depth_crit is None and getattr(segm_crit, "full_size", False):
-        raise ValueError("train_task0: a full-size criterion (SegmCrossEntropy(full_size=True)) is for the end-to-end "
-                         "step only (train_segmenter) - the task0 cache holds labels at the logits' size")
+    if depth_crit is None:
+        require_full_size_labels("train_task0", Xy_train, segm_crit)
     decoder = _inner(segmenter).decoder
     # (data parallel the cache is sharded: every rank must issue the same number of gradient
     #  all-reduces, so the shards agree on the smallest of their sizes first)

@@ -94,7 +94,16 @@ def task1_depth_loss(segmenter, image, target, crit, aux_weight):
 
 def cache_feature_keys(cache):
     """the encoder-feature entries of the task0 cache (engine/trainer.py: populate_task0)"""
-    return [k for k in cache.keys() if k not in ("y", "depth", "kd_y", "out_size")]
+    return [k for k in cache.keys() if k not in ("y", "y_full", "depth", "kd_y", "out_size")]
+
+
+def require_full_size_labels(caller, cache, segm_crit):
+    """a full-size criterion trains on the cache's full-size labels: without them, a ValueError - raised by the task0
+    steps before they touch anything else of their arguments"""
+    if _full_size(segm_crit) and "y_full" not in cache:
+        raise ValueError("{}: a full-size criterion (SegmCrossEntropy(full_size=True)) needs the cache's full-size "
+                         "labels, and this cache holds labels at the logits' size only - make it with "
+                         "populate_task0(..., full_size_labels=True)".format(caller))
 
 
 def check_cache_rows(idx, cache, caller):
@@ -112,7 +121,10 @@ def task0_loss(cache, index, decoder, ignore_index, aux_weight, kd_coeff=None, k
     ``fuse_kd``: the teacher rows are gathered after the resize and kd_coeff * MSE runs fused with the softmax/NLL
     (F.log_softmax_nll_mse refuses a teacher of another shape) - given a ``kd_crit``, only when the rows have the
     logits' shape.  Otherwise kd_coeff * kd_crit(output, teacher rows) runs from the host - always with a
-    ``segm_crit`` (class weights / hard-example selection: there is no fused distillation term for it)."""
+    ``segm_crit`` (class weights / hard-example selection: there is no fused distillation term for it).
+    A full-size ``segm_crit`` (``_full_size``): ``task0_full_size_loss`` instead."""
+    if _full_size(segm_crit):
+        return task0_full_size_loss(cache, index, decoder, segm_crit, aux_weight, kd_coeff, kd_crit)
     feats = [F.gather_rows(cache[k], index) for k in cache_feature_keys(cache)]
     target = F.gather_rows(cache["y"], index)
     output, aux_outs = _heads(decoder(feats))
@@ -128,6 +140,26 @@ def task0_loss(cache, index, decoder, ignore_index, aux_weight, kd_coeff=None, k
             kd_y = kd_y if kd_y is not None else F.gather_rows(cache["kd_y"], index)
             loss = loss + kd_coeff * kd_crit(output, kd_y)
     return segmentation_loss(output, aux_outs, target, ignore_index, aux_weight, loss, segm_crit)
+
+
+def task0_full_size_loss(cache, index, decoder, segm_crit, aux_weight, kd_coeff=None, kd_crit=None):
+    """forward + loss of the decoder-only step with a full-size criterion (nn.SegmCrossEntropy(full_size=True)) on the
+    cache rows ``index``: gather the feature rows, decoder, ``segm_crit`` of the main head + aux_weight * that of
+    every auxiliary head when aux_weight > 0 - as ``task0_depth_loss``, the labels left where they are: the kernels
+    read image b's full-size labels from ``cache["y_full"]`` through ``index``, so no head is resized and no labels
+    are gathered.  kd_coeff not None: + kd_coeff * kd_crit(the main head resized to ``out_size``, teacher rows),
+    launched from the host as written (the fused CE + MSE kernel is for the plain softmax/NLL at the logits' size)."""
+    feats = [F.gather_rows(cache[k], index) for k in cache_feature_keys(cache)]
+    output, aux_outs = _heads(decoder(feats))
+    labels = cache["y_full"]
+    loss = segm_crit(output, labels, rows=index)
+    if kd_coeff is not None:
+        kd_y = F.gather_rows(cache["kd_y"], index)
+        loss = loss + kd_coeff * kd_crit(F.bilinear_resize(output, cache["out_size"]), kd_y)
+    if aux_weight > 0:
+        for aux_out in aux_outs:
+            loss = loss + segm_crit(aux_out, labels, rows=index) * aux_weight
+    return loss
 
 
 def task0_depth_loss(cache, index, decoder, crit, aux_weight):

@@ -2463,18 +2463,43 @@ def _label_tensor(target, who=None):
                                                                         target.dtype))
 
 
-def _segm_inputs(who, logits, target, weight, same_size=True):
+def _label_rows(who, logits, target, rows):
+    """the checks of a label cache (N, H, W) read in place through ``rows``, as ``_depth_inputs`` makes them for a
+    depth cache -> N.  An index that can be read without a synchronisation (a host tensor) is checked against [0, N)
+    before it is refused for being on the host; on the device the kernels clamp (a memory-safety net)."""
+    if not torch.is_tensor(rows) or rows.dtype != torch.int64 or rows.dim() != 1 or not rows.is_contiguous():
+        raise NassegError("{}: rows must be a contiguous 1-D int64 tensor".format(who))
+    if (not torch.is_tensor(target) or target.dtype not in (torch.uint8, torch.int64) or target.dim() != 3
+            or target.numel() == 0):
+        raise NassegError("{}: with rows, the target must be a uint8 or int64 cache of shape (N, H, W) (got {} "
+                          "{})".format(who, getattr(target, "dtype", None), tuple(getattr(target, "shape", ()))))
+    n_rows = int(target.shape[0])
+    if not torch.is_tensor(logits) or logits.dim() != 4 or rows.shape[0] != logits.shape[0]:
+        raise NassegError("{}: one cache row per image expected ({} rows for logits {})".format(
+            who, rows.shape[0], tuple(getattr(logits, "shape", ()))))
+    if not rows.is_cuda and rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n_rows):
+        raise IndexError("{}: cache row index out of range [0, {})".format(who, n_rows))
+    require_device(logits, target, rows)
+    if not target.is_contiguous():
+        raise NassegError("{}: with rows, the label cache must be contiguous (it is read in place)".format(who))
+    return n_rows
+
+
+def _segm_inputs(who, logits, target, weight, same_size=True, rows=None):
     """(logits, target, esz, weight) as the segmentation losses' kernels read them: NHWC logits (B, C, h, w),
-    contiguous labels of ``esz`` bytes and the logits' size (``same_size=False``: (B, H, W) of any size), fp32 class
-    weights (C,) or None.  ``who``: the public function the user called, named by every NassegError."""
+    contiguous labels of ``esz`` bytes and the logits' size (``same_size=False``: (B, H, W) of any size; with
+    ``rows`` a cache (N, H, W) as it stands - _label_rows), fp32 class weights (C,) or None.  ``who``: the public
+    function the user called, named by every NassegError."""
+    if rows is not None:  # (the cache's dtype and shape, the table's length: before anything else)
+        _label_rows(who, logits, target, rows)
     logits = _cl(logits)
     B, C, H, W = logits.shape
     target, esz = _label_tensor(target, who)
-    if same_size:
+    if rows is None and same_size:
         if tuple(target.shape) != (B, H, W):
             raise NassegError("{}: target {} does not match logits {}".format(who, tuple(target.shape),
                                                                              tuple(logits.shape)))
-    elif target.dim() != 3 or target.shape[0] != B or target.numel() == 0:
+    elif rows is None and (target.dim() != 3 or target.shape[0] != B or target.numel() == 0):
         raise NassegError("{}: the target must be uint8 or int64 of shape ({}, H, W) (got {})".format(
             who, B, tuple(target.shape)))
     if weight is not None:
@@ -2869,11 +2894,13 @@ def cross_entropy_select(logits, target, weight=None, ignore_index=255, thresh=N
 
 class _CrossEntropyUpsampled(torch.autograd.Function):
     """nasseg_ce_up_fwd / _bwd.  Outputs: the loss (a scalar of its own), and - not differentiable - pixel_loss at the
-    labels' size (B, H, W), tau (0-dim) and counts = {k, n_valid, n_kept} (int64)."""
+    labels' size (B, H, W), tau (0-dim) and counts = {k, n_valid, n_kept} (int64).  ``rows`` (or None): the
+    row-indexed twins nasseg_ce_up_rows_fwd / _bwd on the label cache ``target`` (_ce_up_entry)."""
 
     @staticmethod
-    def forward(ctx, logits, target, weight, ignore_index, cfg):
-        logits, target, esz, weight = _segm_inputs("cross_entropy_upsampled", logits, target, weight, same_size=False)
+    def forward(ctx, logits, target, weight, ignore_index, cfg, rows):
+        logits, target, esz, weight = _segm_inputs("cross_entropy_upsampled", logits, target, weight, same_size=False,
+                                                   rows=rows)
         B, C, h, w = logits.shape
         if C < 2:
             raise NassegError("cross_entropy_upsampled: at least two classes are expected (got logits {})".format(
@@ -2889,28 +2916,39 @@ class _CrossEntropyUpsampled(torch.autograd.Function):
         stats, counts, pixel_loss = _ce_outputs(logits, B, H, W)
         lse = torch.empty((B, H, W), device=logits.device, dtype=torch.float32)
         ws = _ws(logits, n_ws)
-        lib.call(_k("nasseg_ce_up_fwd", logits), ptr(logits), ptr(target), esz, ptr(weight), *dims,
-                 int(ignore_index), *cfg, ptr(loss), ptr(stats), ptr(counts), ptr(pixel_loss), ptr(lse), ptr(ws),
-                 current_stream())
-        ctx.save_for_backward(logits, target, weight, pixel_loss, lse, stats)
-        ctx.cfg = (esz, int(ignore_index), dims)
+        n_rows = None if rows is None else int(target.shape[0])
+        name, table = _ce_up_entry("_fwd", logits, rows, n_rows)
+        lib.call(name, ptr(logits), ptr(target), esz, *table, ptr(weight), *dims, int(ignore_index), *cfg, ptr(loss),
+                 ptr(stats), ptr(counts), ptr(pixel_loss), ptr(lse), ptr(ws), current_stream())
+        ctx.save_for_backward(logits, target, weight, pixel_loss, lse, stats, rows)
+        ctx.cfg = (esz, int(ignore_index), dims, n_rows)
         tau = _own_scalar(stats, 1)
         ctx.mark_non_differentiable(pixel_loss, tau, counts)
         return loss, pixel_loss, tau, counts
 
     @staticmethod
     def backward(ctx, g, *unused):
-        logits, target, weight, pixel_loss, lse, stats = ctx.saved_tensors
-        esz, ignore, dims = ctx.cfg
+        logits, target, weight, pixel_loss, lse, stats, rows = ctx.saved_tensors
+        esz, ignore, dims, n_rows = ctx.cfg
         g = _upstream(g)
         d = torch.empty_like(logits)
-        lib.call(_k("nasseg_ce_up_bwd", logits), ptr(logits), ptr(target), esz, ptr(weight), ptr(pixel_loss),
-                 ptr(lse), ptr(stats), ptr(g), *dims, ignore, ptr(d), current_stream())
-        return d, None, None, None, None
+        name, table = _ce_up_entry("_bwd", logits, rows, n_rows)
+        lib.call(name, ptr(logits), ptr(target), esz, *table, ptr(weight), ptr(pixel_loss), ptr(lse), ptr(stats),
+                 ptr(g), *dims, ignore, ptr(d), current_stream())
+        return d, None, None, None, None, None
+
+
+def _ce_up_entry(end, logits, rows, n_rows):
+    """(entry point, the arguments that follow elem_size) of the full-size cross-entropy's ``end`` ("_fwd" | "_bwd")
+    for logits stored like ``logits``: with ``rows`` the row-indexed twin and its table (rows, N), without them the
+    plain entry point and nothing (as _depth_entry)"""
+    if rows is None:
+        return _k("nasseg_ce_up" + end, logits), ()
+    return _k("nasseg_ce_up_rows" + end, logits), (ptr(rows), n_rows)
 
 
 def cross_entropy_upsampled(logits, target, weight=None, ignore_index=255, thresh=None, min_kept=0,
-                            keep_fraction=0.0, return_parts=False):
+                            keep_fraction=0.0, return_parts=False, rows=None):
     """``cross_entropy_select`` taken at the LABELS' size: the cross-entropy of (B, C, h, w) logits, up-sampled
     bilinearly (align_corners=False) to the (B, H, W) labels inside the kernels -> 0-dim loss of its own storage
     (INTEGRATION.md, "Losses").
@@ -2923,9 +2961,13 @@ def cross_entropy_upsampled(logits, target, weight=None, ignore_index=255, thres
     loss and the log-sum-exp are kept, the gradient is gathered straight into the logits' shape (exact zeros where
     no kept label pixel reaches a logit).
     ``return_parts``: (loss, pixel_loss (B, H, W) with -1 on invalid pixels, tau, counts = [k, n_valid, n_kept]).
-    No host synchronisation: capturable."""
+    No host synchronisation: capturable.
+    ``rows`` (a contiguous 1-D int64 device tensor of B entries): ``target`` is a label cache (N, H, W), uint8 or
+    int64 and contiguous, and image b meets ``target[rows[b]]`` - read in place by the kernels, bit for bit the call
+    on the gathered ``target[rows]``, which is never made (the task0 cache's ``'y_full'``, engine/trainer.py).
+    Repeated and unordered rows are legal; B*H*W < 2^32 bounds the batch, the cache may be larger."""
     cfg = _select_config("cross_entropy_upsampled", thresh, min_kept, keep_fraction)
-    out = _CrossEntropyUpsampled.apply(logits, target, weight, ignore_index, cfg)
+    out = _CrossEntropyUpsampled.apply(logits, target, weight, ignore_index, cfg, rows)
     return out if return_parts else out[0]
 
 

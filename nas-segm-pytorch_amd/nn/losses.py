@@ -110,8 +110,9 @@ class SegmCrossEntropy(nn.Module):
     map), the logits are up-sampled bilinearly to it inside the kernels and the loss, class weights and selection
     included, is taken over the label pixels: the resolution ``validate`` scores at.  The training steps then hand
     every head, at its own size, the labels as they are (nothing is resized).  Such a criterion is the loss of every
-    head even without weights or selection; it has no region or Lovasz term, and ``train_task0`` refuses it (its
-    cache holds labels at the logits' size)."""
+    head even without weights or selection; it has no region or Lovasz term.  ``train_task0`` takes it on a cache
+    made with ``populate_task0(..., full_size_labels=True)``: ``forward(logits, cache, rows=index)`` reads image b's
+    labels at ``cache[rows[b]]`` in place (``F.cross_entropy_upsampled(rows=)``)."""
 
     def __init__(self, weight=None, ignore_index=255, thresh=None, min_kept=0, keep_fraction=0.0, region=None,
                  region_weight=1.0, region_smooth=1.0, region_classes="present", lovasz_weight=None,
@@ -175,11 +176,19 @@ class SegmCrossEntropy(nn.Module):
             self.weight = w.to(device=device, dtype=torch.float32)
         return self
 
-    def forward(self, logits, target):
+    def forward(self, logits, target, rows=None):
+        """``rows`` (an int64 device tensor, one entry per image; ``full_size=True`` only): ``target`` is a label
+        cache (N, H, W) and image b meets ``target[rows[b]]``, read in place (the task0 cache's ``'y_full'``)"""
+        if rows is not None and not self.full_size:
+            raise ValueError("SegmCrossEntropy: rows= reads a full-size label cache in place and needs "
+                             "full_size=True (at the logits' size the step gathers its labels)")
         self.prepare(logits.device)
         loss = F.cross_entropy_upsampled if self.full_size else F.cross_entropy_select
+        if rows is None:
+            return loss(logits, target, self.weight, self.ignore_index, self.thresh, self.min_kept,
+                        self.keep_fraction, **self._terms())
         return loss(logits, target, self.weight, self.ignore_index, self.thresh, self.min_kept, self.keep_fraction,
-                    **self._terms())
+                    rows=rows)
 
     def extra_repr(self):
         s = "classes={}, ignore_index={}, thresh={}, min_kept={}, keep_fraction={}".format(
