@@ -565,6 +565,67 @@ int nasseg_ce_up_rows_bwd(const float* logits, const void* target, int elem_size
                           const float* gscale, int B, int h, int w, int C, int H, int W, int ignore, float* dlogits,
                           void* stream);
 
+/* Full-size cross-entropy plus the region-overlap term (soft Jaccard / Dice / Tversky), both taken at the LABELS'
+ * size with the bilinear up-sampling of the logits fused in: the differentiable form of the mean IoU where
+ * validate() (src/engine/inference.py:55-66) measures it - on the logits resized up to the labels - instead of on the
+ * labels resized down to the logits (src/engine/trainer.py:141-146,236-250).  Notation: "Full-size cross-entropy" and
+ * the region-overlap term above; nothing about either changes.
+ * logits [B][h][w][C], labels [B][H][W] (uint8 / int64) at any size per axis.  For label pixel p = (b, Y, X) the row
+ * v_p is the interpolated row of nasseg_ce_up_fwd, bit for bit (the same lin_coeff, top / bot / v, every product and
+ * sum rounded on its own); p is valid iff t_p != ignore and 0 <= t_p < C; lse_p = logsumexp(v_p) and pixel_loss[p]
+ * are exactly what nasseg_ce_up_fwd writes (pixel_loss and lse are written - and needed by the backward - also with
+ * with_ce == 0).
+ * Forward: q_pc = expf(v_pc - lse_p) in fp32 - the value the full-size backward uses, and the one definition of q in
+ * every pass here.  Over ALL valid label pixels (selection does not thin the term, class weights do not enter it):
+ *   I_c = sum_p q_pc [t_p == c],  S_c = sum_p q_pc,  N_c = sum_p [t_p == c]
+ * and D_c, T_c, K, loss_region, coef, sums and ncls are literally those of nasseg_ce_region_fwd (alpha, beta, smooth,
+ * all_classes, "K empty: exactly 0 and an exactly zero gradient", the mean-removed coef[C + c]): the same finalize
+ * kernel runs on this path's partial rows.  loss = loss_ce + region_weight * loss_region; with_ce == 0: region_weight *
+ * loss_region, select must be 0, and weight, stats and counts may be null.  loss_ce, stats, counts, pixel_loss and lse
+ * are bit-identical to nasseg_ce_up_fwd's on the same input, selection included.  Class sums: fp32 within a tile of
+ * 256 label pixels, fp64 across a workgroup's tiles, one fp64 row per workgroup (at most 1024), the rows added in a
+ * fixed order by the finalize launch.  One more launch after the finalize interpolates every valid pixel's row once
+ * more and writes
+ *   gdot[p] = sum_c G_pc q_pc,  G_pc = coef[C + c] + [t_p == c] coef[c]   (fp32 [B][H][W]; 0 where p is not valid)
+ * so that per label pixel three fp32 values are kept - pixel_loss, lse, gdot - and nothing of B*H*W*C elements exists
+ * in either direction.
+ * Backward:
+ *   dlogits[b][i][j][c] = sum_{Y, X} Wy(Y, i) Wx(X, j) ( [p kept] gscale w[t_p] (q_pc - [c == t_p]) / stats[0]
+ *                                                        + gscale region_weight q_pc (G_pc - gdot_p) )
+ * over the valid label pixels in the gather order of nasseg_ce_up_bwd (Y, then X, ascending), in fp32: a valid pixel
+ * the selection did not keep still contributes its region part.  A logit no valid label pixel reaches gets an exact
+ * zero; written once, in the logits' type; at region_weight = 0 (with_ce != 0) bit-identical to nasseg_ce_up_bwd's -
+ * the launch is then that entry point's own.
+ * No float atomics, no host synchronisation, no allocation, a launch geometry that depends on the shapes alone:
+ * capturable and bit-reproducible.  Shape limits: those of nasseg_ce_up_fwd.  ws: nasseg_ce_up_region_workspace
+ * floats, 8-byte aligned (0: bad shape) - a function of the grid and of C, not of the pixel count.
+ * The _rows_ twins read a label cache [n_rows][H][W] through a device table of B rows exactly as
+ * nasseg_ce_up_rows_fwd / _bwd do: the result is that of the un-indexed call on target[rows], bit for bit; neither the
+ * cache nor the table is written. */
+int64_t nasseg_ce_up_region_workspace(int B, int h, int w, int C, int H, int W);
+int nasseg_ce_up_region_fwd(const float* logits, const void* target, int elem_size, const float* weight, int B, int h,
+                            int w, int C, int H, int W, int ignore, int with_ce, int select, float t_loss,
+                            int64_t min_kept, double keep_fraction, double alpha, double beta, double smooth,
+                            int all_classes, double region_weight, float* loss, float* loss_ce, float* loss_region,
+                            float* stats, int64_t* counts, float* pixel_loss, float* lse, float* coef, float* sums,
+                            int64_t* ncls, float* gdot, float* ws, void* stream);
+int nasseg_ce_up_region_bwd(const float* logits, const void* target, int elem_size, const float* weight,
+                            const float* pixel_loss, const float* lse, const float* stats, const float* coef,
+                            const float* gdot, const float* gscale, int with_ce, double region_weight, int B, int h,
+                            int w, int C, int H, int W, int ignore, float* dlogits, void* stream);
+int nasseg_ce_up_region_rows_fwd(const float* logits, const void* target, int elem_size, const int64_t* rows,
+                                 int64_t n_rows, const float* weight, int B, int h, int w, int C, int H, int W,
+                                 int ignore, int with_ce, int select, float t_loss, int64_t min_kept,
+                                 double keep_fraction, double alpha, double beta, double smooth, int all_classes,
+                                 double region_weight, float* loss, float* loss_ce, float* loss_region, float* stats,
+                                 int64_t* counts, float* pixel_loss, float* lse, float* coef, float* sums,
+                                 int64_t* ncls, float* gdot, float* ws, void* stream);
+int nasseg_ce_up_region_rows_bwd(const float* logits, const void* target, int elem_size, const int64_t* rows,
+                                 int64_t n_rows, const float* weight, const float* pixel_loss, const float* lse,
+                                 const float* stats, const float* coef, const float* gdot, const float* gscale,
+                                 int with_ce, double region_weight, int B, int h, int w, int C, int H, int W,
+                                 int ignore, float* dlogits, void* stream);
+
 /* Lovasz-Softmax term (Berman, Triggs, Blaschko, CVPR 2018; absent from the reference): the convex extension of the
  * Jaccard loss, the surrogate of the mean IoU the reward is built from.  Logits [P][C], labels [P]; pixel p is valid
  * iff its label t != ignore and 0 <= t < C; n = valid pixels, y_pc = [t_p == c], N_c = sum_p y_pc.
@@ -1085,6 +1146,29 @@ int nasseg_bf16_ce_up_rows_bwd(const nasseg_bf16_t* logits, const void* target, 
                                int64_t n_rows, const float* weight, const float* pixel_loss, const float* lse,
                                const float* stats, const float* gscale, int B, int h, int w, int C, int H, int W,
                                int ignore, nasseg_bf16_t* dlogits, void* stream);
+int nasseg_bf16_ce_up_region_fwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* weight,
+                                 int B, int h, int w, int C, int H, int W, int ignore, int with_ce, int select,
+                                 float t_loss, int64_t min_kept, double keep_fraction, double alpha, double beta,
+                                 double smooth, int all_classes, double region_weight, float* loss, float* loss_ce,
+                                 float* loss_region, float* stats, int64_t* counts, float* pixel_loss, float* lse,
+                                 float* coef, float* sums, int64_t* ncls, float* gdot, float* ws, void* stream);
+int nasseg_bf16_ce_up_region_bwd(const nasseg_bf16_t* logits, const void* target, int elem_size, const float* weight,
+                                 const float* pixel_loss, const float* lse, const float* stats, const float* coef,
+                                 const float* gdot, const float* gscale, int with_ce, double region_weight, int B,
+                                 int h, int w, int C, int H, int W, int ignore, nasseg_bf16_t* dlogits, void* stream);
+int nasseg_bf16_ce_up_region_rows_fwd(const nasseg_bf16_t* logits, const void* target, int elem_size,
+                                      const int64_t* rows, int64_t n_rows, const float* weight, int B, int h, int w,
+                                      int C, int H, int W, int ignore, int with_ce, int select, float t_loss,
+                                      int64_t min_kept, double keep_fraction, double alpha, double beta, double smooth,
+                                      int all_classes, double region_weight, float* loss, float* loss_ce,
+                                      float* loss_region, float* stats, int64_t* counts, float* pixel_loss, float* lse,
+                                      float* coef, float* sums, int64_t* ncls, float* gdot, float* ws, void* stream);
+int nasseg_bf16_ce_up_region_rows_bwd(const nasseg_bf16_t* logits, const void* target, int elem_size,
+                                      const int64_t* rows, int64_t n_rows, const float* weight,
+                                      const float* pixel_loss, const float* lse, const float* stats, const float* coef,
+                                      const float* gdot, const float* gscale, int with_ce, double region_weight, int B,
+                                      int h, int w, int C, int H, int W, int ignore, nasseg_bf16_t* dlogits,
+                                      void* stream);
 int nasseg_bf16_lovasz_fwd(const nasseg_bf16_t* logits, const void* target, int elem_size, int64_t P, int C,
                            int ignore, int all_classes, double lovasz_weight, const float* base_loss, float* loss,
                            float* loss_lovasz, float* errors, float* coef, int* rank, int64_t* ncls, float* ws,

@@ -155,6 +155,140 @@ __global__ __launch_bounds__(256) void ce_sel_finalize_kernel(const float* __res
   }
 }
 
+// The region-overlap term (nasseg_ce_region_*: csrc/loss.hip; nasseg_ce_up_region_*: csrc/loss_up.hip): the forward
+// kernels of both write per-workgroup fp64 rows part[3][C][kRegionRows] = I | S | N, and one finalize adds them.
+constexpr int kRegionRows = kCeGridCap;  // (a row per workgroup of the forward)
+
+__device__ __forceinline__ float wave_allsum(float v) {  // (a fixed butterfly: the same pairing every time)
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ double wave_allsum(double v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// One workgroup of 1024 threads.  1. with_ce: the statements of ce_sel_finalize_kernel, by the first 256 threads, on
+// the sum pass's partials (lce, stats, counts: bit-identical to nasseg_ce_sel_fwd's).  2. wave w of 16 adds rows
+// 0 .. nblk-1 of part for the elements w, w + 16, ...: each lane its <= 16 rows, all loads in flight at once, added
+// in row order, then the butterfly -> tot[3][C].  3. per class T_c and the members of K; sum T and |K| by a tree;
+// lreg = 1 - sum T / |K| (0 when K is empty), loss = [lce +] rweight * lreg, and for backward
+// coef = {-a_c / |K|} | {-b_c / |K| - their mean over the C classes} (outside K: a_c = b_c = 0).  All in fp64.
+__global__ __launch_bounds__(1024) void region_finalize_kernel(const float* __restrict__ partial,
+                                                               const double* __restrict__ part, int nblk, int C,
+                                                               int with_ce, int selected, double alpha, double beta,
+                                                               double smooth, int all_classes, double rweight,
+                                                               float* __restrict__ loss, float* __restrict__ lce,
+                                                               float* __restrict__ lreg, float* __restrict__ stats,
+                                                               int64_t* __restrict__ counts, float* __restrict__ coef,
+                                                               float* __restrict__ sums, int64_t* __restrict__ ncls,
+                                                               double* tot) {
+  __shared__ double red_l[256];
+  __shared__ double red_w[256];
+  __shared__ double red_n[256];
+  const int tid = threadIdx.x;
+  const bool head = tid < 256;
+  if (with_ce) {
+    if (head) {
+      double l = 0.0, w = 0.0, n = 0.0;
+      for (int b = tid; b < nblk; b += 256) {
+        l += (double)partial[b * 3];
+        w += (double)partial[b * 3 + 1];
+        n += (double)partial[b * 3 + 2];
+      }
+      red_l[tid] = l;
+      red_w[tid] = w;
+      red_n[tid] = n;
+    }
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (tid < s) {
+        red_l[tid] += red_l[tid + s];
+        red_w[tid] += red_w[tid + s];
+        red_n[tid] += red_n[tid + s];
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      lce[0] = (float)(red_l[0] / red_w[0]);
+      stats[0] = (float)red_w[0];
+      counts[2] = (int64_t)red_n[0];
+      if (!selected) {
+        stats[1] = -__builtin_inff();
+        counts[0] = counts[1] = (int64_t)red_n[0];
+      }
+    }
+    __syncthreads();
+  } else if (tid == 0) {
+    lce[0] = 0.f;
+  }
+  const int lane = tid & 63, wave = tid >> 6;
+  for (int e = wave; e < 3 * C; e += 16) {
+    const double* src = part + (int64_t)e * kRegionRows;
+    double r[kRegionRows / 64];
+#pragma unroll
+    for (int i = 0; i < kRegionRows / 64; ++i) r[i] = lane + 64 * i < nblk ? src[lane + 64 * i] : 0.0;
+    double v = 0.0;
+#pragma unroll
+    for (int i = 0; i < kRegionRows / 64; ++i) v += r[i];
+    v = wave_allsum(v);
+    if (lane == 0) tot[e] = v;
+  }
+  __syncthreads();
+  const double gamma = 1.0 - alpha - beta;
+  double tsum = 0.0, bsum = 0.0, kcnt = 0.0;
+  if (head) {
+    for (int c = tid; c < C; c += 256) {
+      const double I = tot[c], S = tot[C + c], N = tot[2 * C + c];
+      if (all_classes || N > 0.0) {
+        const double D = gamma * I + alpha * S + beta * N + smooth;
+        tsum += (I + smooth) / D;
+        bsum += (I + smooth) * alpha / (D * D);
+        kcnt += 1.0;
+      }
+    }
+    red_l[tid] = tsum;
+    red_w[tid] = bsum;
+    red_n[tid] = kcnt;
+  }
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) {
+      red_l[tid] += red_l[tid + s];
+      red_w[tid] += red_w[tid + s];
+      red_n[tid] += red_n[tid + s];
+    }
+    __syncthreads();
+  }
+  const double K = red_n[0];
+  // The gradient q_j (G_j - sum_c G_c q_c) does not change when a constant is added to every G_c (sum_c q_c = 1):
+  // the -b_c / |K| are stored minus their mean over the C classes, so that fp32 does not have to cancel it.
+  const double bmean = K > 0.0 ? red_w[0] / K / (double)C : 0.0;
+  if (head) {
+    for (int c = tid; c < C; c += 256) {
+      const double I = tot[c], S = tot[C + c], N = tot[2 * C + c];
+      float ca = 0.f;
+      double cb = 0.0;
+      if (all_classes || N > 0.0) {
+        const double D = gamma * I + alpha * S + beta * N + smooth;
+        ca = (float)(-((D - (I + smooth) * gamma) / (D * D)) / K);
+        cb = ((I + smooth) * alpha / (D * D)) / K;
+      }
+      coef[c] = ca;
+      coef[C + c] = (float)(cb - bmean);
+      sums[c] = (float)I;
+      sums[C + c] = (float)S;
+      ncls[c] = (int64_t)N;
+    }
+  }
+  if (tid == 0) {
+    const float lr = K > 0.0 ? (float)(1.0 - red_l[0] / K) : 0.f;
+    lreg[0] = lr;
+    ncls[C] = (int64_t)K;
+    loss[0] = (float)((with_ce ? (double)lce[0] : 0.0) + rweight * (double)lr);
+  }
+}
+
 #endif  // NASSEG_LOSS_NO_SUM_PASS
 
 // ---------------------------------------------------------------------------

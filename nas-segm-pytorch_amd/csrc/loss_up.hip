@@ -18,7 +18,13 @@
 // csrc/loss_common.h): image b of the logits then meets image rows[b] of a label cache - the task0 cache - instead of
 // image b of the labels; only the address of an image's labels differs, so both forms give the same bits and the
 // batch's labels are never gathered into a copy.
+// The region-overlap term at the labels' size (nasseg_ce_up_region_*): after the forward above, a pass that adds the
+// class sums of q = expf(v - lse) into per-workgroup fp64 rows, the finalize of nasseg_ce_region_fwd
+// (csrc/loss_common.h) on them, one more pass for gdot[p] = sum_c G_pc q_pc, and the backward gather above with the
+// region part inside its per-visit expression (a compile-time flag: without it, the kernel nasseg_ce_up_bwd launches).
 #include <math.h>
+
+#include <type_traits>
 
 #include "loss_common.h"
 #include "resize_index.h"
@@ -76,19 +82,160 @@ __global__ __launch_bounds__(256) void ce_up_fwd_kernel(const act_t* __restrict_
   }
 }
 
+// ---------------------------------------------------------------------------
+// The region-overlap term at the labels' size (nasseg_ce_up_region_*; definition: include/nasseg.h).
+// ---------------------------------------------------------------------------
+// Label pixel p of the batch -> its label (returned), image and coordinates: the decoding of ce_up_fwd_kernel.
+template <typename TL, typename... Rows>
+__device__ __forceinline__ int64_t up_label(const TL* __restrict__ target, int64_t p, int H, int W, int& b, int& Y,
+                                            int& X, Rows... lr) {
+  if constexpr (sizeof...(Rows) != 0) {
+    const uint32_t off = label_decode((uint32_t)p, b, lr...);
+    Y = (int)(off / (uint32_t)W);
+    X = (int)(off - (uint32_t)Y * (uint32_t)W);
+    return (int64_t)label_image(target, (int64_t)b, lr...)[off];
+  } else {
+    X = (int)(p % W);
+    const int64_t q = p / W;
+    Y = (int)(q % H);
+    b = (int)(q / H);
+    return (int64_t)target[p];
+  }
+}
+
+// The four neighbour rows of a label pixel and its two coefficient pairs.
+struct UpRow {
+  const act_t *p00, *p01, *p10, *p11;
+  Lin ly, lx;
+  __device__ __forceinline__ float at(int64_t c) const {
+    return up_interp(lda1(p00 + c), lda1(p01 + c), lda1(p10 + c), lda1(p11 + c), ly, lx);
+  }
+};
+__device__ __forceinline__ UpRow up_row(const act_t* __restrict__ logits, int b, int Y, int X, int h, int w, int C,
+                                        int H, int W, float sh, float sw) {
+  UpRow r;
+  r.ly = lin_coeff(Y, sh, h, H);
+  r.lx = lin_coeff(X, sw, w, W);
+  const act_t* lb = logits + (int64_t)b * h * w * C;
+  r.p00 = lb + ((int64_t)r.ly.i0 * w + r.lx.i0) * C;
+  r.p01 = lb + ((int64_t)r.ly.i0 * w + r.lx.i1) * C;
+  r.p10 = lb + ((int64_t)r.ly.i1 * w + r.lx.i0) * C;
+  r.p11 = lb + ((int64_t)r.ly.i1 * w + r.lx.i1) * C;
+  return r;
+}
+
+// After ce_up_fwd_kernel (which stays the one writer of pixel_loss and lse: their bits are nasseg_ce_up_fwd's because
+// the kernel is): the class sums of q_pc = expf(v_pc - lse_p) over the valid pixels (pixel_loss >= 0), the row
+// interpolated once more, by the route of region_fwd_kernel (csrc/loss.hip): per class a butterfly over the wave (fp32
+// within the tile of 256 label pixels), the four waves' sums through 3 KB of LDS in chunks of 64 classes, and the
+// workgroup's row of part[3][C][kRegionRows] accumulated in place in fp64, each element by the one thread that owns
+// it, in tile order.  Every workgroup of ce_grid(P) owns at least one tile, so every row below the grid's size is
+// written.
+template <typename TL, typename... Rows>
+__global__ __launch_bounds__(256) void ce_up_region_sums_kernel(const act_t* __restrict__ logits,
+                                                                const TL* __restrict__ target, int B, int h, int w,
+                                                                int C, int H, int W, float sh, float sw,
+                                                                const float* __restrict__ pixel_loss,
+                                                                const float* __restrict__ lse_in,
+                                                                double* __restrict__ part, Rows... lr) {
+  __shared__ float red[4][3][64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t P = (int64_t)B * H * W;
+  const int64_t ntiles = (P + 255) / 256;
+  bool first = true;
+  for (int64_t tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
+    const int64_t p = tl * 256 + tid;
+    int64_t t = -1;
+    bool valid = false;
+    float lse = 0.f;
+    UpRow r = {};
+    if (p < P && pixel_loss[p] >= 0.f) {
+      int X, Y, b;
+      t = up_label(target, p, H, W, b, Y, X, lr...);  // (valid: in [0, C))
+      valid = true;
+      r = up_row(logits, b, Y, X, h, w, C, H, W, sh, sw);
+      lse = lse_in[p];
+    }
+    for (int c0 = 0; c0 < C; c0 += 64) {
+      const int nc = C - c0 < 64 ? C - c0 : 64;
+      for (int j = 0; j < nc; ++j) {
+        const int c = c0 + j;
+        const float q = valid ? expf(r.at(c) - lse) : 0.f;
+        const bool hit = valid && t == (int64_t)c;
+        const float vS = wave_allsum(q);
+        const float vI = wave_allsum(hit ? q : 0.f);
+        const float vN = (float)__popcll(__ballot(hit));
+        if (lane == 0) {
+          red[wave][0][j] = vI;
+          red[wave][1][j] = vS;
+          red[wave][2][j] = vN;
+        }
+      }
+      __syncthreads();
+      if (tid < 3 * nc) {
+        const int k = tid / nc, j = tid - k * nc;
+        const float v = ((red[0][k][j] + red[1][k][j]) + red[2][k][j]) + red[3][k][j];
+        double* dst = part + ((int64_t)k * C + c0 + j) * kRegionRows + blockIdx.x;
+        *dst = first ? (double)v : *dst + (double)v;
+      }
+      __syncthreads();
+    }
+    first = false;
+  }
+}
+
+// After the finalize: gdot[p] = sum_c G_pc q_pc with G_pc = coef[C + c] + [t_p == c] coef[c] and q the forward's
+// (expf(v - lse), the row interpolated once more), 0 on pixels that are not valid (pixel_loss < 0).  One lane per label
+// pixel; the sum runs over c ascending, the label's own term last.
+template <typename TL, typename... Rows>
+__global__ __launch_bounds__(256) void ce_up_gdot_kernel(const act_t* __restrict__ logits,
+                                                         const TL* __restrict__ target, int B, int h, int w, int C,
+                                                         int H, int W, float sh, float sw,
+                                                         const float* __restrict__ pixel_loss,
+                                                         const float* __restrict__ lse, const float* __restrict__ coef,
+                                                         float* __restrict__ gdot, Rows... lr) {
+  const int64_t P = (int64_t)B * H * W;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
+    if (pixel_loss[p] < 0.f) {
+      gdot[p] = 0.f;
+      continue;
+    }
+    int X, Y, b;
+    const int64_t t = up_label(target, p, H, W, b, Y, X, lr...);  // (valid: in [0, C))
+    const UpRow r = up_row(logits, b, Y, X, h, w, C, H, W, sh, sw);
+    const float l = lse[p];
+    float dot = 0.f;
+    for (int c = 0; c < C; ++c) dot = fmaf(coef[C + c], expf(r.at(c) - l), dot);
+    gdot[p] = fmaf(coef[t], expf(r.at(t) - l), dot);
+  }
+}
+
 // (up_interp, up_dst_range, up_weight: csrc/resize_index.h)
 // grid: (channel chunk, tile x, tile y, image), flattened, chunk fastest.  VEC: the patch is staged with 16-byte
 // (bf16: 8-byte) loads - one chunk (C <= kUpChunk) and 16-byte aligned logits; else element by element.
 // LDS: patch[kUpPatch][kUpPatch][cn | 1] floats.
-template <typename TL, bool VEC, typename... Rows>
+// RG = NoRegion: the cross-entropy alone (nasseg_ce_up_bwd: the `else` branches below are its code).  RG = RegionBwd
+// (nasseg_ce_up_region_bwd): every VALID label pixel is visited and adds region_weight * q (G - gdot) to the
+// cross-entropy part, which only a kept pixel has; the thread's channel is fixed, so its two coefficients are
+// registers.
+struct NoRegion {};
+struct RegionBwd {
+  const float* coef;  // [2C]: region_finalize_kernel's
+  const float* gdot;  // [B][H][W]: sum_c G_pc q_pc (ce_up_gdot_kernel)
+  float rweight;
+  int with_ce;
+};
+
+template <typename TL, bool VEC, typename RG, typename... Rows>
 __global__ __launch_bounds__(256) void ce_up_bwd_kernel(const act_t* __restrict__ logits, const TL* __restrict__ target,
                                                         const float* __restrict__ weight,
                                                         const float* __restrict__ pixel_loss,
                                                         const float* __restrict__ lse, const float* __restrict__ stats,
                                                         const float* __restrict__ gscale, int B, int h, int w, int C,
                                                         int H, int W, float sh, float sw, int tiles_y, int tiles_x,
-                                                        int nchunk, act_t* __restrict__ dlogits, Rows... lr) {
+                                                        int nchunk, act_t* __restrict__ dlogits, RG rg, Rows... lr) {
   constexpr bool kRows = sizeof...(Rows) != 0;
+  constexpr bool kRegion = std::is_same<RG, RegionBwd>::value;
   extern __shared__ float patch[];
   const int tid = threadIdx.x;
   int wi = blockIdx.x;
@@ -149,7 +296,17 @@ __global__ __launch_bounds__(256) void ce_up_bwd_kernel(const act_t* __restrict_
   }
   __syncthreads();
   const float g = gscale ? gscale[0] : 1.f;
-  const float sumw = stats[0], tau = stats[1];
+  float sumw, tau, gr = 0.f;
+  bool with_ce = true;
+  if constexpr (kRegion) {  // (the term alone: stats may be null)
+    with_ce = rg.with_ce != 0;
+    sumw = with_ce ? stats[0] : 1.f;
+    tau = with_ce ? stats[1] : 0.f;
+    gr = g * rg.rweight;
+  } else {
+    sumw = stats[0];
+    tau = stats[1];
+  }
   // (with a table: pixel p of the batch has its label (rows[b] - b) images further on in the cache - one scalar load
   //  of the table per workgroup, and every visit reads the address it read without one, from another base)
   const TL* tbase = target;
@@ -162,6 +319,11 @@ __global__ __launch_bounds__(256) void ce_up_bwd_kernel(const act_t* __restrict_
     up_dst_range(i, sh, h, H, ylo, yhi);
     up_dst_range(j, sw, w, W, xlo, xhi);
     float acc = 0.f;
+    float ca = 0.f, cb = 0.f;
+    if constexpr (kRegion) {
+      ca = rg.coef[c0 + c];
+      cb = rg.coef[C + c0 + c];
+    }
     for (int Y = ylo; Y <= yhi; ++Y) {
       const Lin ly = lin_coeff(Y, sh, h, H);
       const float wy = up_weight(ly, i);
@@ -174,13 +336,28 @@ __global__ __launch_bounds__(256) void ce_up_bwd_kernel(const act_t* __restrict_
         const float wx = up_weight(lx, j);
         if (wx == 0.f) continue;
         const int64_t p = prow + X;
-        if (!sel_kept(pixel_loss[p], tau)) continue;  // (-1 on pixels that are not valid)
-        const int64_t t = (int64_t)tbase[p];
-        const float gp = (g * (weight ? weight[t] : 1.f)) / sumw;
-        const int a0 = (lx.i0 - ox) * CS, a1 = (lx.i1 - ox) * CS;
-        const float v = up_interp(r0[a0], r0[a1], r1[a0], r1[a1], ly, lx);
-        const float d = gp * (expf(v - lse[p]) - ((int64_t)(c0 + c) == t ? 1.f : 0.f));
-        acc = fmaf(wy * wx, d, acc);
+        if constexpr (kRegion) {
+          const float pl = pixel_loss[p];
+          if (pl < 0.f) continue;  // (-1 on pixels that are not valid)
+          const bool kept = with_ce && sel_kept(pl, tau);
+          const int64_t t = (int64_t)tbase[p];
+          const bool y = (int64_t)(c0 + c) == t;
+          const int a0 = (lx.i0 - ox) * CS, a1 = (lx.i1 - ox) * CS;
+          const float v = up_interp(r0[a0], r0[a1], r1[a0], r1[a1], ly, lx);
+          const float q = expf(v - lse[p]);
+          float ce = 0.f;
+          if (kept) ce = ((g * (weight ? weight[t] : 1.f)) / sumw) * (q - (y ? 1.f : 0.f));  // (the line below)
+          const float G = cb + (y ? ca : 0.f);
+          acc = fmaf(wy * wx, fmaf(gr, q * (G - rg.gdot[p]), ce), acc);
+        } else {
+          if (!sel_kept(pixel_loss[p], tau)) continue;  // (-1 on pixels that are not valid)
+          const int64_t t = (int64_t)tbase[p];
+          const float gp = (g * (weight ? weight[t] : 1.f)) / sumw;
+          const int a0 = (lx.i0 - ox) * CS, a1 = (lx.i1 - ox) * CS;
+          const float v = up_interp(r0[a0], r0[a1], r1[a0], r1[a1], ly, lx);
+          const float d = gp * (expf(v - lse[p]) - ((int64_t)(c0 + c) == t ? 1.f : 0.f));
+          acc = fmaf(wy * wx, d, acc);
+        }
       }
     }
     sta1(dlogits + (((int64_t)b * h + i) * w + j) * C + c0 + c, acc);
@@ -237,14 +414,19 @@ int up_fwd(const char* who, const act_t* logits, const void* target, int elem_si
                        stats, counts, ws, s, lr...);
 }
 
-template <typename... Rows>
+// rg: NoRegion (the cross-entropy alone) or RegionBwd.
+template <typename RG, typename... Rows>
 int up_bwd(const char* who, const act_t* logits, const void* target, int elem_size, const float* weight,
            const float* pixel_loss, const float* lse, const float* stats, const float* gscale, int B, int h, int w,
-           int C, int H, int W, act_t* dlogits, void* stream, Rows... lr) {
+           int C, int H, int W, act_t* dlogits, void* stream, RG rg, Rows... lr) {
   static_assert(sizeof...(Rows) <= 1, "no table, or one LabelRows");
   UP_SHAPE_CHECK(who);
   NASSEG_TRY(check_elem_size(who, elem_size));
-  NASSEG_REQUIRE(logits && target && pixel_loss && lse && stats && dlogits, "%s: null pointer", who);
+  NASSEG_REQUIRE(logits && target && pixel_loss && lse && dlogits, "%s: null pointer", who);
+  if constexpr (std::is_same<RG, RegionBwd>::value)
+    NASSEG_REQUIRE(rg.coef && rg.gdot && (!rg.with_ce || stats), "%s: null pointer", who);
+  else
+    NASSEG_REQUIRE(stats, "%s: null pointer", who);
   ROWS_CHECK(who);
   hipStream_t s = (hipStream_t)stream;
   const int tiles_y = cdiv(h, kUpTile), tiles_x = cdiv(w, kUpTile), nchunk = cdiv(C, kUpChunk);
@@ -257,14 +439,102 @@ int up_bwd(const char* who, const act_t* logits, const void* target, int elem_si
     using TL = label_of<decltype(labels)>;
     const auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(256), lds, s, logits, labels, weight, pixel_loss, lse, stats,
-                         gscale, B, h, w, C, H, W, sh, sw, tiles_y, tiles_x, nchunk, dlogits, lr...);
+                         gscale, B, h, w, C, H, W, sh, sw, tiles_y, tiles_x, nchunk, dlogits, rg, lr...);
     };
     if (vec)
-      launch(ce_up_bwd_kernel<TL, true, Rows...>);
+      launch(ce_up_bwd_kernel<TL, true, RG, Rows...>);
     else
-      launch(ce_up_bwd_kernel<TL, false, Rows...>);
+      launch(ce_up_bwd_kernel<TL, false, RG, Rows...>);
   });
   NASSEG_LAUNCH_CHECK("ce_up_bwd");
+  return NASSEG_OK;
+}
+
+// The backward with the region term.  region_weight == 0 beside the cross-entropy: the term adds nothing, and the launch
+// is nasseg_ce_up_bwd's own - the kernel without the region part - so that the gradient has its bits.  (The region
+// instantiation computes the same cross-entropy expression, but the compiler fuses the multiply-adds of the
+// interpolation differently in the two instantiations, so their last bits differ.)
+template <typename... Rows>
+int up_region_bwd(const char* who, const act_t* logits, const void* target, int elem_size, const float* weight,
+                  const float* pixel_loss, const float* lse, const float* stats, const float* coef, const float* gdot,
+                  const float* gscale, int with_ce, double region_weight, int B, int h, int w, int C, int H, int W,
+                  act_t* dlogits, void* stream, Rows... lr) {
+  const float rw = (float)region_weight;
+  if (with_ce && rw == 0.f)
+    return up_bwd(who, logits, target, elem_size, weight, pixel_loss, lse, stats, gscale, B, h, w, C, H, W, dlogits,
+                  stream, NoRegion{}, lr...);
+  return up_bwd(who, logits, target, elem_size, weight, pixel_loss, lse, stats, gscale, B, h, w, C, H, W, dlogits,
+                stream, RegionBwd{coef, gdot, rw, with_ce}, lr...);
+}
+
+// floats of the workspace before its fp64 part: the sum pass's partials | the selection's words, to an even count
+inline int64_t up_region_head() { return (3 * kCeGridCap + nasseg_ohem_workspace() + 1) & ~(int64_t)1; }
+
+struct RegionFwd {
+  int with_ce;
+  double alpha, beta, smooth;
+  int all_classes;
+  double rweight;
+  float *loss_ce, *loss_region, *coef, *sums;
+  int64_t* ncls;
+  float* gdot;
+};
+
+// ce_up_fwd_kernel, ce_up_region_sums_kernel, [the selection and the sum pass of up_fwd,] region_finalize_kernel on
+// this path's rows, ce_up_gdot_kernel.  ws: partials | selection | fp64 part[3][C][kRegionRows] | fp64 tot[3][C].
+template <typename... Rows>
+int up_region_fwd(const char* who, const act_t* logits, const void* target, int elem_size, const float* weight, int B,
+                  int h, int w, int C, int H, int W, int ignore, int select, float t_loss, int64_t min_kept,
+                  double keep_fraction, const RegionFwd& rf, float* loss, float* stats, int64_t* counts,
+                  float* pixel_loss, float* lse, float* ws, void* stream, Rows... lr) {
+  static_assert(sizeof...(Rows) <= 1, "no table, or one LabelRows");
+  UP_SHAPE_CHECK(who);
+  NASSEG_TRY(check_elem_size(who, elem_size));
+  NASSEG_REQUIRE(logits && target && loss && rf.loss_ce && rf.loss_region && rf.coef && rf.sums && rf.ncls &&
+                     rf.gdot && pixel_loss && lse && ws,
+                 "%s: null pointer", who);
+  NASSEG_REQUIRE(!rf.with_ce || (stats && counts), "%s: null pointer", who);
+  ROWS_CHECK(who);
+  NASSEG_REQUIRE(rf.with_ce || !select, "%s: selection without the cross-entropy", who);
+  NASSEG_TRY(check_selection(who, select, min_kept, keep_fraction));
+  NASSEG_REQUIRE(rf.alpha >= 0.0 && rf.beta >= 0.0 && rf.alpha + rf.beta > 0.0 && rf.smooth >= 0.0,
+                 "%s: alpha, beta, smooth >= 0 and alpha + beta > 0 expected", who);
+  NASSEG_REQUIRE(!rf.all_classes || rf.smooth > 0.0, "%s: all classes need smooth > 0", who);
+  NASSEG_REQUIRE(((uintptr_t)ws & 7) == 0, "%s: the workspace must be 8-byte aligned", who);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t P = (int64_t)B * H * W;
+  const int grid = ce_grid(P);  // (<= kRegionRows)
+  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
+  double* part = (double*)(ws + up_region_head());
+  double* tot = part + (int64_t)3 * C * kRegionRows;
+  with_labels(target, elem_size, [&](auto labels) {
+    using TL = label_of<decltype(labels)>;
+    hipLaunchKernelGGL((ce_up_fwd_kernel<TL, Rows...>), dim3(grid), dim3(256), 0, s, logits, labels, B, h, w, C, H, W,
+                       sh, sw, ignore, pixel_loss, lse, lr...);
+    hipLaunchKernelGGL((ce_up_region_sums_kernel<TL, Rows...>), dim3(grid), dim3(256), 0, s, logits, labels, B, h, w, C,
+                       H, W, sh, sw, pixel_loss, lse, part, lr...);
+  });
+  NASSEG_LAUNCH_CHECK("ce_up_region_fwd");
+  if (rf.with_ce) {  // (the finalizer below reads the partials)
+    const auto selection = [&](float* tau, int64_t* cnt) {
+      return nasseg_ohem_threshold(pixel_loss, P, t_loss, min_kept, keep_fraction, tau, cnt, ws + 3 * kCeGridCap,
+                                   stream);
+    };
+    NASSEG_TRY(ce_sel_reduce("ce_up_region_sum", nullptr, selection, pixel_loss, target, elem_size, weight, P, select,
+                             nullptr, stats, counts, ws, s, lr...));
+  }
+  hipLaunchKernelGGL(region_finalize_kernel, dim3(1), dim3(1024), 0, s, ws, part, grid, C, rf.with_ce, select,
+                     rf.alpha, rf.beta, rf.smooth, rf.all_classes, rf.rweight, loss, rf.loss_ce, rf.loss_region, stats,
+                     counts, rf.coef, rf.sums, rf.ncls, tot);
+  NASSEG_LAUNCH_CHECK("ce_up_region_finalize");
+  // (nothing is summed here, so no cap of 1024 workgroups: a workgroup per 256 label pixels, fewer than 2^24 - with four
+  //  waves per SIMD the pass waits on its loads, measured: DESIGN.md 3.6)
+  const unsigned gdot_grid = (unsigned)((P + 255) / 256);
+  with_labels(target, elem_size, [&](auto labels) {
+    hipLaunchKernelGGL((ce_up_gdot_kernel<label_of<decltype(labels)>, Rows...>), dim3(gdot_grid), dim3(256), 0, s,
+                       logits, labels, B, h, w, C, H, W, sh, sw, pixel_loss, lse, rf.coef, rf.gdot, lr...);
+  });
+  NASSEG_LAUNCH_CHECK("ce_up_gdot");
   return NASSEG_OK;
 }
 
@@ -293,7 +563,7 @@ int NASSEG_FN(ce_up_bwd)(const act_t* logits, const void* target, int elem_size,
                          int h, int w, int C, int H, int W, int ignore, act_t* dlogits, void* stream) {
   (void)ignore;  // (validity is pixel_loss >= 0: the forward decided it)
   return up_bwd("ce_up_bwd", logits, target, elem_size, weight, pixel_loss, lse, stats, gscale, B, h, w, C, H, W,
-                dlogits, stream);
+                dlogits, stream, NoRegion{});
 }
 
 // The row-indexed twins: target is the whole label cache [n_rows][H][W], rows a device array of B cache rows; image b
@@ -315,7 +585,62 @@ int NASSEG_FN(ce_up_rows_bwd)(const act_t* logits, const void* target, int elem_
                               int ignore, act_t* dlogits, void* stream) {
   (void)ignore;
   return up_bwd("ce_up_rows_bwd", logits, target, elem_size, weight, pixel_loss, lse, stats, gscale, B, h, w, C, H, W,
-                dlogits, stream, label_rows(rows, n_rows, H, W));
+                dlogits, stream, NoRegion{}, label_rows(rows, n_rows, H, W));
+}
+
+#if NASSEG_FP32_ONLY
+// floats: nasseg_ce_up_workspace's (to an even count) | fp64 part[3][C][kRegionRows] | fp64 tot[3][C]
+int64_t nasseg_ce_up_region_workspace(int B, int h, int w, int C, int H, int W) {
+  if (!up_shape_ok(B, h, w, C, H, W)) return 0;
+  return up_region_head() + 2 * ((int64_t)3 * C * kRegionRows + (int64_t)3 * C);
+}
+#endif
+
+// The cross-entropy above plus the region-overlap term over the label pixels (include/nasseg.h).
+int NASSEG_FN(ce_up_region_fwd)(const act_t* logits, const void* target, int elem_size, const float* weight, int B,
+                                int h, int w, int C, int H, int W, int ignore, int with_ce, int select, float t_loss,
+                                int64_t min_kept, double keep_fraction, double alpha, double beta, double smooth,
+                                int all_classes, double region_weight, float* loss, float* loss_ce, float* loss_region,
+                                float* stats, int64_t* counts, float* pixel_loss, float* lse, float* coef, float* sums,
+                                int64_t* ncls, float* gdot, float* ws, void* stream) {
+  const RegionFwd rf = {with_ce, alpha, beta, smooth, all_classes, region_weight, loss_ce, loss_region, coef, sums,
+                        ncls,    gdot};
+  return up_region_fwd("ce_up_region_fwd", logits, target, elem_size, weight, B, h, w, C, H, W, ignore, select, t_loss,
+                       min_kept, keep_fraction, rf, loss, stats, counts, pixel_loss, lse, ws, stream);
+}
+
+int NASSEG_FN(ce_up_region_bwd)(const act_t* logits, const void* target, int elem_size, const float* weight,
+                                const float* pixel_loss, const float* lse, const float* stats, const float* coef,
+                                const float* gdot, const float* gscale, int with_ce, double region_weight, int B, int h,
+                                int w, int C, int H, int W, int ignore, act_t* dlogits, void* stream) {
+  (void)ignore;
+  return up_region_bwd("ce_up_region_bwd", logits, target, elem_size, weight, pixel_loss, lse, stats, coef, gdot, gscale,
+                       with_ce, region_weight, B, h, w, C, H, W, dlogits, stream);
+}
+
+int NASSEG_FN(ce_up_region_rows_fwd)(const act_t* logits, const void* target, int elem_size, const int64_t* rows,
+                                     int64_t n_rows, const float* weight, int B, int h, int w, int C, int H, int W,
+                                     int ignore, int with_ce, int select, float t_loss, int64_t min_kept,
+                                     double keep_fraction, double alpha, double beta, double smooth, int all_classes,
+                                     double region_weight, float* loss, float* loss_ce, float* loss_region,
+                                     float* stats, int64_t* counts, float* pixel_loss, float* lse, float* coef,
+                                     float* sums, int64_t* ncls, float* gdot, float* ws, void* stream) {
+  const RegionFwd rf = {with_ce, alpha, beta, smooth, all_classes, region_weight, loss_ce, loss_region, coef, sums,
+                        ncls,    gdot};
+  return up_region_fwd("ce_up_region_rows_fwd", logits, target, elem_size, weight, B, h, w, C, H, W, ignore, select,
+                       t_loss, min_kept, keep_fraction, rf, loss, stats, counts, pixel_loss, lse, ws, stream,
+                       label_rows(rows, n_rows, H, W));
+}
+
+int NASSEG_FN(ce_up_region_rows_bwd)(const act_t* logits, const void* target, int elem_size, const int64_t* rows,
+                                     int64_t n_rows, const float* weight, const float* pixel_loss, const float* lse,
+                                     const float* stats, const float* coef, const float* gdot, const float* gscale,
+                                     int with_ce, double region_weight, int B, int h, int w, int C, int H, int W,
+                                     int ignore, act_t* dlogits, void* stream) {
+  (void)ignore;
+  return up_region_bwd("ce_up_region_rows_bwd", logits, target, elem_size, weight, pixel_loss, lse, stats, coef, gdot,
+                       gscale, with_ce, region_weight, B, h, w, C, H, W, dlogits, stream,
+                       label_rows(rows, n_rows, H, W));
 }
 
 }  // extern "C"

@@ -2895,60 +2895,111 @@ def cross_entropy_select(logits, target, weight=None, ignore_index=255, thresh=N
 class _CrossEntropyUpsampled(torch.autograd.Function):
     """nasseg_ce_up_fwd / _bwd.  Outputs: the loss (a scalar of its own), and - not differentiable - pixel_loss at the
     labels' size (B, H, W), tau (0-dim) and counts = {k, n_valid, n_kept} (int64).  ``rows`` (or None): the
-    row-indexed twins nasseg_ce_up_rows_fwd / _bwd on the label cache ``target`` (_ce_up_entry)."""
+    row-indexed twins nasseg_ce_up_rows_fwd / _bwd on the label cache ``target`` (_ce_up_entry).
+    ``rcfg`` (_region_config's tuple, or None): nasseg_ce_up_region_fwd / _bwd instead - the region-overlap term over
+    the label pixels on top (``cfg`` None: alone) - and four more outputs, not differentiable: loss_ce, loss_region,
+    sums = I | S (2C,), ncls = N | |K| (C + 1,) int64; tau and counts are then None without the cross-entropy.  Kept
+    for backward beyond the plain node's: 2C coefficients and gdot (B, H, W)."""
 
     @staticmethod
-    def forward(ctx, logits, target, weight, ignore_index, cfg, rows):
-        logits, target, esz, weight = _segm_inputs("cross_entropy_upsampled", logits, target, weight, same_size=False,
-                                                   rows=rows)
+    def forward(ctx, logits, target, weight, ignore_index, cfg, rows, rcfg=None):
+        with_ce = cfg is not None
+        who = "cross_entropy_upsampled" if with_ce else "region_overlap_loss_upsampled"
+        logits, target, esz, weight = _segm_inputs(who, logits, target, weight, same_size=False, rows=rows)
         B, C, h, w = logits.shape
         if C < 2:
-            raise NassegError("cross_entropy_upsampled: at least two classes are expected (got logits {})".format(
-                tuple(logits.shape)))
+            raise NassegError("{}: at least two classes are expected (got logits {})".format(who, tuple(logits.shape)))
         H, W = int(target.shape[1]), int(target.shape[2])
         dims = (B, h, w, C, H, W)
-        n_ws = lib.query("nasseg_ce_up_workspace", *dims)
+        n_ws = lib.query("nasseg_ce_up_workspace" if rcfg is None else "nasseg_ce_up_region_workspace", *dims)
         if n_ws <= 0:
-            raise NassegError("cross_entropy_upsampled: logits {} against labels {} exceed B*H*W < 2^32, "
+            raise NassegError("{}: logits {} against labels {} exceed B*H*W < 2^32, "
                               "B*h*w*C < 2^31 or 2^24 tiles of 8 x 8 logits and 64 channels".format(
-                                  tuple(logits.shape), tuple(target.shape)))
+                                  who, tuple(logits.shape), tuple(target.shape)))
         loss = _scalar(logits)
         stats, counts, pixel_loss = _ce_outputs(logits, B, H, W)
         lse = torch.empty((B, H, W), device=logits.device, dtype=torch.float32)
         ws = _ws(logits, n_ws)
         n_rows = None if rows is None else int(target.shape[0])
-        name, table = _ce_up_entry("_fwd", logits, rows, n_rows)
-        lib.call(name, ptr(logits), ptr(target), esz, *table, ptr(weight), *dims, int(ignore_index), *cfg, ptr(loss),
-                 ptr(stats), ptr(counts), ptr(pixel_loss), ptr(lse), ptr(ws), current_stream())
-        ctx.save_for_backward(logits, target, weight, pixel_loss, lse, stats, rows)
-        ctx.cfg = (esz, int(ignore_index), dims, n_rows)
-        tau = _own_scalar(stats, 1)
-        ctx.mark_non_differentiable(pixel_loss, tau, counts)
-        return loss, pixel_loss, tau, counts
+        ctx.cfg = (esz, int(ignore_index), dims, n_rows, with_ce, None if rcfg is None else rcfg[4])
+        if rcfg is None:
+            name, table = _ce_up_entry("_fwd", logits, rows, n_rows)
+            lib.call(name, ptr(logits), ptr(target), esz, *table, ptr(weight), *dims, int(ignore_index), *cfg,
+                     ptr(loss), ptr(stats), ptr(counts), ptr(pixel_loss), ptr(lse), ptr(ws), current_stream())
+            ctx.save_for_backward(logits, target, weight, pixel_loss, lse, stats, rows)
+            tau = _own_scalar(stats, 1)
+            ctx.mark_non_differentiable(pixel_loss, tau, counts)
+            return loss, pixel_loss, tau, counts
+        alpha, beta, smooth, all_classes, region_weight = rcfg
+        loss_ce, loss_region = _scalar(logits), _scalar(logits)
+        rcoef, sums = _vec(logits, 2 * C), _vec(logits, 2 * C)
+        ncls = torch.empty((C + 1,), device=logits.device, dtype=torch.int64)
+        gdot = torch.empty((B, H, W), device=logits.device, dtype=torch.float32)
+        if not with_ce:
+            stats = counts = None
+        name, table = _ce_up_entry("_fwd", logits, rows, n_rows, region=True)
+        lib.call(name, ptr(logits), ptr(target), esz, *table, ptr(weight), *dims, int(ignore_index), int(with_ce),
+                 *(cfg if with_ce else (0, float("inf"), 0, 0.0)), alpha, beta, smooth, all_classes, region_weight,
+                 ptr(loss), ptr(loss_ce), ptr(loss_region), ptr(stats), ptr(counts), ptr(pixel_loss), ptr(lse),
+                 ptr(rcoef), ptr(sums), ptr(ncls), ptr(gdot), ptr(ws), current_stream())
+        ctx.save_for_backward(logits, target, weight, pixel_loss, lse, stats, rows, rcoef, gdot)
+        tau = _own_scalar(stats, 1) if with_ce else None
+        outs = (loss, pixel_loss, tau, counts, loss_ce, loss_region, sums, ncls)
+        ctx.mark_non_differentiable(*[o for o in outs[1:] if o is not None])
+        return outs
 
     @staticmethod
     def backward(ctx, g, *unused):
-        logits, target, weight, pixel_loss, lse, stats, rows = ctx.saved_tensors
-        esz, ignore, dims, n_rows = ctx.cfg
+        esz, ignore, dims, n_rows, with_ce, region_weight = ctx.cfg
         g = _upstream(g)
-        d = torch.empty_like(logits)
-        name, table = _ce_up_entry("_bwd", logits, rows, n_rows)
-        lib.call(name, ptr(logits), ptr(target), esz, *table, ptr(weight), ptr(pixel_loss), ptr(lse), ptr(stats),
-                 ptr(g), *dims, ignore, ptr(d), current_stream())
-        return d, None, None, None, None, None
+        if region_weight is None:
+            logits, target, weight, pixel_loss, lse, stats, rows = ctx.saved_tensors
+            d = torch.empty_like(logits)
+            name, table = _ce_up_entry("_bwd", logits, rows, n_rows)
+            lib.call(name, ptr(logits), ptr(target), esz, *table, ptr(weight), ptr(pixel_loss), ptr(lse), ptr(stats),
+                     ptr(g), *dims, ignore, ptr(d), current_stream())
+        else:
+            logits, target, weight, pixel_loss, lse, stats, rows, rcoef, gdot = ctx.saved_tensors
+            d = torch.empty_like(logits)
+            name, table = _ce_up_entry("_bwd", logits, rows, n_rows, region=True)
+            lib.call(name, ptr(logits), ptr(target), esz, *table, ptr(weight), ptr(pixel_loss), ptr(lse), ptr(stats),
+                     ptr(rcoef), ptr(gdot), ptr(g), int(with_ce), region_weight, *dims, ignore, ptr(d),
+                     current_stream())
+        return d, None, None, None, None, None, None
 
 
-def _ce_up_entry(end, logits, rows, n_rows):
+def _ce_up_entry(end, logits, rows, n_rows, region=False):
     """(entry point, the arguments that follow elem_size) of the full-size cross-entropy's ``end`` ("_fwd" | "_bwd")
     for logits stored like ``logits``: with ``rows`` the row-indexed twin and its table (rows, N), without them the
-    plain entry point and nothing (as _depth_entry)"""
+    plain entry point and nothing (as _depth_entry).  ``region``: the entry points with the region-overlap term."""
+    base = "nasseg_ce_up_region" if region else "nasseg_ce_up"
     if rows is None:
-        return _k("nasseg_ce_up" + end, logits), ()
-    return _k("nasseg_ce_up_rows" + end, logits), (ptr(rows), n_rows)
+        return _k(base + end, logits), ()
+    return _k(base + "_rows" + end, logits), (ptr(rows), n_rows)
+
+
+def region_overlap_loss_upsampled(logits, target, region="jaccard", smooth=1.0, classes="present", ignore_index=255,
+                                  return_parts=False, rows=None):
+    """``region_overlap_loss`` taken at the LABELS' size: the soft Jaccard / Dice / Tversky loss of (B, C, h, w)
+    logits up-sampled bilinearly (align_corners=False) to the (B, H, W) labels inside the kernels -> 0-dim loss of its
+    own storage ("Losses"): the region term of ``cross_entropy_upsampled(region=...)`` alone.
+
+    ``region``, ``smooth``, ``classes`` and the ``ValueError``s are ``region_overlap_loss``'s; the sums run over the
+    valid label pixels with q = exp(v - logsumexp(v)) of the interpolated row v.  Nothing of B*H*W*C elements is
+    allocated in either direction.  ``return_parts``: (loss, I (C,) fp32, S (C,) fp32, N (C,) int64, |K| 0-dim int64).
+    ``rows``: as ``cross_entropy_upsampled``'s.  Deterministic, no host synchronisation: capturable."""
+    rcfg = _region_config("region_overlap_loss_upsampled", region, smooth, classes)
+    out = _CrossEntropyUpsampled.apply(logits, target, None, ignore_index, None, rows, rcfg)
+    if not return_parts:
+        return out[0]
+    sums, ncls = out[6], out[7]
+    C = sums.numel() // 2
+    return out[0], sums[:C], sums[C:], ncls[:C], ncls[C]
 
 
 def cross_entropy_upsampled(logits, target, weight=None, ignore_index=255, thresh=None, min_kept=0,
-                            keep_fraction=0.0, return_parts=False, rows=None):
+                            keep_fraction=0.0, return_parts=False, rows=None, region=None, region_weight=1.0,
+                            region_smooth=1.0, region_classes="present"):
     """``cross_entropy_select`` taken at the LABELS' size: the cross-entropy of (B, C, h, w) logits, up-sampled
     bilinearly (align_corners=False) to the (B, H, W) labels inside the kernels -> 0-dim loss of its own storage
     (INTEGRATION.md, "Losses").
@@ -2965,10 +3016,21 @@ def cross_entropy_upsampled(logits, target, weight=None, ignore_index=255, thres
     ``rows`` (a contiguous 1-D int64 device tensor of B entries): ``target`` is a label cache (N, H, W), uint8 or
     int64 and contiguous, and image b meets ``target[rows[b]]`` - read in place by the kernels, bit for bit the call
     on the gathered ``target[rows]``, which is never made (the task0 cache's ``'y_full'``, engine/trainer.py).
-    Repeated and unordered rows are legal; B*H*W < 2^32 bounds the batch, the cache may be larger."""
+    Repeated and unordered rows are legal; B*H*W < 2^32 bounds the batch, the cache may be larger.
+    ``region`` ("jaccard" | "dice" | ("tversky", a, b); ``region_smooth``, ``region_classes``: the ``smooth`` and
+    ``classes`` of ``region_overlap_loss``; None: no such term, and nothing here changes): loss = the above +
+    ``region_weight`` * that region term over ALL valid label pixels (selection does not thin it, the weights do not
+    enter it), with q = exp(v - logsumexp(v)) of the interpolated row - the differentiable form of the mean IoU at the
+    size ``validate`` measures it.  Still nothing of B*H*W*C elements: one more fp32 value per label pixel is kept.
+    ``return_parts`` then also returns the two component losses: (loss, pixel_loss, tau, counts, loss_ce,
+    loss_region).  With ``rows`` as well."""
     cfg = _select_config("cross_entropy_upsampled", thresh, min_kept, keep_fraction)
-    out = _CrossEntropyUpsampled.apply(logits, target, weight, ignore_index, cfg, rows)
-    return out if return_parts else out[0]
+    if region is None:
+        out = _CrossEntropyUpsampled.apply(logits, target, weight, ignore_index, cfg, rows, None)
+        return out if return_parts else out[0]
+    rcfg = _region_config("cross_entropy_upsampled", region, region_smooth, region_classes, region_weight)
+    out = _CrossEntropyUpsampled.apply(logits, target, weight, ignore_index, cfg, rows, rcfg)
+    return out[:6] if return_parts else out[0]
 
 
 def ohem_threshold(pixel_loss, thresh=None, min_kept=1, keep_fraction=0.0, t_loss=None):

@@ -110,13 +110,19 @@ class SegmCrossEntropy(nn.Module):
     map), the logits are up-sampled bilinearly to it inside the kernels and the loss, class weights and selection
     included, is taken over the label pixels: the resolution ``validate`` scores at.  The training steps then hand
     every head, at its own size, the labels as they are (nothing is resized).  Such a criterion is the loss of every
-    head even without weights or selection; it has no region or Lovasz term.  ``train_task0`` takes it on a cache
+    head even without weights or selection; it has no Lovasz term, and a region term only with
+    ``region_at="labels"``.  ``train_task0`` takes it on a cache
     made with ``populate_task0(..., full_size_labels=True)``: ``forward(logits, cache, rows=index)`` reads image b's
-    labels at ``cache[rows[b]]`` in place (``F.cross_entropy_upsampled(rows=)``)."""
+    labels at ``cache[rows[b]]`` in place (``F.cross_entropy_upsampled(rows=)``).
+    ``region_at`` ("logits" | "labels"; needs ``full_size=True`` and a ``region``): where the region term's sums are
+    taken.  "labels": over the label pixels, on the up-sampled rows, fused like the cross-entropy
+    (``F.cross_entropy_upsampled(region=...)``) - ``CE + lambda * Dice`` where the score is taken, with ``rows=`` as
+    well.  "logits" (the default) is the term of ``F.cross_entropy_select``, which a full-size criterion cannot
+    have: a ValueError, as before."""
 
     def __init__(self, weight=None, ignore_index=255, thresh=None, min_kept=0, keep_fraction=0.0, region=None,
                  region_weight=1.0, region_smooth=1.0, region_classes="present", lovasz_weight=None,
-                 lovasz_classes="present", full_size=False):
+                 lovasz_classes="present", full_size=False, region_at="logits"):
         super(SegmCrossEntropy, self).__init__()
         if weight is not None:
             weight = torch.as_tensor(weight)
@@ -138,10 +144,17 @@ class SegmCrossEntropy(nn.Module):
         if lovasz_weight is None and lovasz_classes not in ("present", "all"):
             raise ValueError("SegmCrossEntropy: lovasz_classes must be \"present\" or \"all\" (got {!r})".format(
                 lovasz_classes))
-        if full_size and (region is not None or lovasz_weight is not None):
+        if region_at not in ("logits", "labels"):
+            raise ValueError("SegmCrossEntropy: region_at must be \"logits\" or \"labels\" (got {!r})".format(region_at))
+        if region_at == "labels" and not (full_size and region is not None):
+            raise ValueError("SegmCrossEntropy: region_at=\"labels\" takes the region term over the full-size labels "
+                             "and needs full_size=True and a region")
+        if full_size and (lovasz_weight is not None or (region is not None and region_at != "labels")):
             raise ValueError("SegmCrossEntropy: full_size=True has no region or Lovasz term (those terms are defined "
-                             "at the logits' size only)")
+                             "at the logits' size only; region_at=\"labels\" takes the region term at the labels' "
+                             "size)")
         self.full_size = bool(full_size)
+        self.region_at = region_at
 
     def _terms(self):
         """the keyword arguments of ``F.cross_entropy_select`` for the terms this criterion has"""
@@ -166,6 +179,8 @@ class SegmCrossEntropy(nn.Module):
             cfg = cfg + (("lovasz", self.lovasz_weight, self.lovasz_classes),)
         if self.full_size:  # (another loss kind: other launches, labels at another size)
             cfg = cfg + (("full_size",),)
+        if self.region_at == "labels":  # (and another again: the region term's own launches)
+            cfg = cfg + (("region_at", "labels"),)
         return cfg
 
     def prepare(self, device):
@@ -188,7 +203,7 @@ class SegmCrossEntropy(nn.Module):
             return loss(logits, target, self.weight, self.ignore_index, self.thresh, self.min_kept,
                         self.keep_fraction, **self._terms())
         return loss(logits, target, self.weight, self.ignore_index, self.thresh, self.min_kept, self.keep_fraction,
-                    rows=rows)
+                    rows=rows, **self._terms())
 
     def extra_repr(self):
         s = "classes={}, ignore_index={}, thresh={}, min_kept={}, keep_fraction={}".format(
@@ -201,4 +216,6 @@ class SegmCrossEntropy(nn.Module):
             s += ", lovasz_weight={}, lovasz_classes={!r}".format(self.lovasz_weight, self.lovasz_classes)
         if self.full_size:
             s += ", full_size=True"
+        if self.region_at == "labels":
+            s += ", region_at='labels'"
         return s
