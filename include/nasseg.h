@@ -960,6 +960,25 @@ int nasseg_augment(const uint8_t* src, int64_t src_bytes, const int64_t* desc, c
 int nasseg_augment_depth(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
                          const float* lut, const float* params, float depth_scale, float* image, float* target,
                          int B, int Ho, int Wo, void* stream);
+/* The two launches above with a photometric jitter between the resampling and lut (data/datasets.py: ColourJitter;
+ * data/device.py plans it).  Everything else - arguments, grid, the mask / target half, fills - is the sibling's.
+ * colour int32 [B][12] = {q[0][0..2], q[1][0..2], q[2][0..2], apply, 0, 0}: the sample's colour matrix in 12-bit fixed
+ * point (4096 = 1.0) and whether to apply it; ctab uint8 [B][3][256], 4-byte aligned: the sample's point table per
+ * channel.  A live pixel's resampled uint8 triple v becomes
+ *   m[c] = apply ? clip((q[c][0] v[0] + q[c][1] v[1] + q[c][2] v[2] + 2048) >> 12, 0, 255) : v[c]   (arithmetic shift)
+ *   image value of channel c = lut[c][ctab[b][c][m[c]]].
+ * A fill pixel (an index -1, or a window that does not lie inside src) is lut[c][fill byte c]: neither the matrix nor
+ * ctab touches it - the host passes the fill its pipeline ends with.  The sum is int32 with every coefficient clamped
+ * to |q| <= 2^15 as it is read (|sum| < 2^25; data/device.py refuses larger coefficients, ColourJitter's stay below
+ * 2^14.1), and every table index is a value clipped to 0..255: all loads stay in bounds whatever colour and ctab hold.
+ * With apply = 0 and ctab the identity ramp the image is the sibling's, bit for bit.  Both tables sit in LDS; the 12
+ * words are uniform per workgroup. */
+int nasseg_augment_colour(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
+                          const int32_t* colour, const uint8_t* ctab, const float* lut, float* image, uint8_t* mask,
+                          int B, int Ho, int Wo, void* stream);
+int nasseg_augment_depth_colour(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
+                                const int32_t* colour, const uint8_t* ctab, const float* lut, const float* params,
+                                float depth_scale, float* image, float* target, int B, int Ho, int Wo, void* stream);
 
 /* ---- prediction post-processing: cv2.resize(logits, dsize, interpolation=INTER_CUBIC) (float branch) of the
  * reference's inference notebooks, then argmax for segmentation (engine/predict.py) ------------------------------
@@ -1285,6 +1304,13 @@ int nasseg_bf16_augment(const uint8_t* src, int64_t src_bytes, const int64_t* de
 int nasseg_bf16_augment_depth(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
                               const nasseg_bf16_t* lut, const float* params, float depth_scale, nasseg_bf16_t* image,
                               float* target, int B, int Ho, int Wo, void* stream);
+int nasseg_bf16_augment_colour(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
+                               const int32_t* colour, const uint8_t* ctab, const nasseg_bf16_t* lut,
+                               nasseg_bf16_t* image, uint8_t* mask, int B, int Ho, int Wo, void* stream);
+int nasseg_bf16_augment_depth_colour(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
+                                     const int32_t* colour, const uint8_t* ctab, const nasseg_bf16_t* lut,
+                                     const float* params, float depth_scale, nasseg_bf16_t* image, float* target,
+                                     int B, int Ho, int Wo, void* stream);
 int nasseg_bf16_resize_cubic(const nasseg_bf16_t* x, int B, int h, int w, int C, const int* taps, const float* coef,
                              float* y, int H, int W, void* stream);
 int nasseg_bf16_resize_cubic_argmax(const nasseg_bf16_t* x, int B, int h, int w, int C, const int* taps,

@@ -13,6 +13,15 @@
 // window may start at any byte (an image of odd 3 h w bytes precedes it), so a count is read as TWO BYTE LOADS and
 // put together in a register: the target half issues no 16-bit load, aligned or not, and the host packs without
 // padding.
+//
+// The colour launches (nasseg_augment_colour, nasseg_augment_depth_colour: data/datasets.py's ColourJitter) are the
+// same two kernels with augment_image's compile-time switch on: a live pixel's resampled uint8 triple v goes through
+// the sample's 12-bit colour matrix, m[c] = clip((sum_k q[c][k] v[k] + 2048) >> 12, 0, 255) (arithmetic shift, skipped
+// unless the sample's word 9 is set), then through the sample's byte table ctab[c][m[c]], then through lut as before.
+// A fill pixel goes from the descriptor's fill straight to lut: the host has jittered that fill where its pipeline does.
+// The sum is int32: each coefficient is clamped to |q| <= 2^15 as it is read (the planner refuses larger ones), so
+// |sum| <= 3 * 2^15 * 255 + 2^11 < 2^25 whatever `colour` holds, and every table index is a value clipped to 0..255.
+// The sample's 12 words are uniform per workgroup (blockIdx.y); its 768 table bytes sit in LDS beside lut.
 #include "common.h"
 
 namespace {
@@ -22,10 +31,14 @@ enum { AUG_IMG_OFF, AUG_MSK_OFF, AUG_H, AUG_W, AUG_IMG_LD, AUG_MSK_LD, AUG_IMG_F
 
 // The image half of one output pixel (oy, ox) of a sample (its image window: the descriptor's img_off, h, w, img_ld
 // and img_fill; its tables t): OpenCV's fixed-point bicubic of the four by four taps (or the fill), through the table
-// in LDS, to the pixel's three values at o.  Every kernel of this file calls it.
+// in LDS, to the pixel's three values at o.  Every kernel of this file calls it.  COLOUR: the live pixel's colour
+// matrix cq (the sample's 12 words, wave-uniform) and byte table stab (LDS, [3][256]) in between; without it
+// neither is touched.
+template <bool COLOUR>
 __device__ __forceinline__ void augment_image(const uint8_t* __restrict__ src, int64_t src_bytes, int64_t img_off,
                                               int h, int w, int64_t img_ld, int img_fill, const int* __restrict__ t,
-                                              const act_t* slut, act_t* __restrict__ o, int oy, int ox, int Ho) {
+                                              const act_t* slut, act_t* __restrict__ o, int oy, int ox, int Ho,
+                                              const int32_t* __restrict__ cq, const uint8_t* stab) {
   // a window that does not lie inside the buffer is read as fill (the host checks before it launches; this
   // keeps every load in bounds whatever it is handed)
   const bool img_ok = h > 0 && w > 0 && img_off >= 0 && img_ld >= 3 * (int64_t)w &&
@@ -67,6 +80,22 @@ __device__ __forceinline__ void augment_image(const uint8_t* __restrict__ src, i
       const int64_t r = (acc[c] + (1 << 21)) >> 22;  // arithmetic shift, as numpy's >> on int64
       v[c] = (int)(r < 0 ? 0 : (r > 255 ? 255 : r));
     }
+    if (COLOUR) {
+      if (cq[9] != 0) {
+        int m[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          int sum = 1 << 11;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) sum += min(max(cq[3 * c + k], -(1 << 15)), 1 << 15) * v[k];
+          m[c] = min(max(sum >> 12, 0), 255);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = m[c];
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c] = stab[256 * c + v[c]];
+    }
   }
   o[0] = slut[v[0]];
   o[1] = slut[256 + v[1]];
@@ -76,16 +105,22 @@ __device__ __forceinline__ void augment_image(const uint8_t* __restrict__ src, i
 // one thread per output pixel of one sample (blockIdx.y), the pixels of a sample in row-major order: a wave writes
 // 64 consecutive pixels (768 contiguous bytes of fp32 image, 64 of mask), and the few output rows a workgroup
 // covers read the same four source rows, which stay in L1 / L2 between the lanes that share them.
+// COLOUR: colour int32 [B][12] and ctab uint8 [B][3][256] (4-byte aligned: copied as 192 words) are read, else ignored.
+template <bool COLOUR>
 __global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
                                                       const int64_t* __restrict__ desc,
                                                       const int* __restrict__ taps,
+                                                      const int32_t* __restrict__ colour,
+                                                      const uint8_t* __restrict__ ctab,
                                                       const act_t* __restrict__ lut, act_t* __restrict__ image,
                                                       uint8_t* __restrict__ mask, int Ho, int Wo) {
+  const int b = blockIdx.y;
   __shared__ act_t slut[3 * 256];
+  __shared__ uint32_t stab[COLOUR ? 3 * 64 : 1];
   for (int i = threadIdx.x; i < 3 * 256; i += 256) slut[i] = lut[i];
+  if (COLOUR && threadIdx.x < 3 * 64) stab[threadIdx.x] = ((const uint32_t*)ctab)[(int64_t)b * (3 * 64) + threadIdx.x];
   __syncthreads();
 
-  const int b = blockIdx.y;
   const int64_t npix = (int64_t)Ho * Wo;
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= npix) return;
@@ -103,8 +138,8 @@ __global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict_
   const int* t = taps + (int64_t)b * (9 * (Ho + Wo));
   const int my = t[8 * (Ho + Wo) + oy], mx = t[8 * (Ho + Wo) + Ho + ox];
 
-  augment_image(src, src_bytes, img_off, h, w, img_ld, img_fill, t, slut, image + ((int64_t)b * npix + p) * 3, oy, ox,
-                Ho);
+  augment_image<COLOUR>(src, src_bytes, img_off, h, w, img_ld, img_fill, t, slut, image + ((int64_t)b * npix + p) * 3,
+                        oy, ox, Ho, COLOUR ? colour + (int64_t)b * 12 : nullptr, (const uint8_t*)stab);
 
   if (!mask) return;  // (an image without a mask: F.prepare_image)
   int m = msk_fill & 255;
@@ -115,19 +150,24 @@ __global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict_
 // The same launch for a depth target (see the head of the file): the target window of sample b holds h rows of w
 // little-endian 16-bit counts, msk_ld BYTES apart (>= 2 w); params [B][2] = {zoom, fill} in fp32.  A wave writes 64
 // consecutive floats of the target (256 contiguous bytes) next to its 768 bytes of fp32 image.  The descriptor's
-// mask fill is not read.
+// mask fill is not read.  COLOUR: as augment_kernel's.
+template <bool COLOUR>
 __global__ __launch_bounds__(256) void augment_depth_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
                                                             const int64_t* __restrict__ desc,
                                                             const int* __restrict__ taps,
+                                                            const int32_t* __restrict__ colour,
+                                                            const uint8_t* __restrict__ ctab,
                                                             const act_t* __restrict__ lut,
                                                             const float* __restrict__ params, float depth_scale,
                                                             act_t* __restrict__ image, float* __restrict__ target,
                                                             int Ho, int Wo) {
+  const int b = blockIdx.y;
   __shared__ act_t slut[3 * 256];
+  __shared__ uint32_t stab[COLOUR ? 3 * 64 : 1];
   for (int i = threadIdx.x; i < 3 * 256; i += 256) slut[i] = lut[i];
+  if (COLOUR && threadIdx.x < 3 * 64) stab[threadIdx.x] = ((const uint32_t*)ctab)[(int64_t)b * (3 * 64) + threadIdx.x];
   __syncthreads();
 
-  const int b = blockIdx.y;
   const int64_t npix = (int64_t)Ho * Wo;
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= npix) return;
@@ -144,8 +184,8 @@ __global__ __launch_bounds__(256) void augment_depth_kernel(const uint8_t* __res
   const int* t = taps + (int64_t)b * (9 * (Ho + Wo));
   const int my = t[8 * (Ho + Wo) + oy], mx = t[8 * (Ho + Wo) + Ho + ox];
 
-  augment_image(src, src_bytes, img_off, h, w, img_ld, img_fill, t, slut, image + ((int64_t)b * npix + p) * 3, oy, ox,
-                Ho);
+  augment_image<COLOUR>(src, src_bytes, img_off, h, w, img_ld, img_fill, t, slut, image + ((int64_t)b * npix + p) * 3,
+                        oy, ox, Ho, COLOUR ? colour + (int64_t)b * 12 : nullptr, (const uint8_t*)stab);
 
   float v = params[2 * b + 1];  // the fill: a pad comes after the resize on the host, so it is not divided
   if (my >= 0 && mx >= 0 && msk_ok) {
@@ -160,34 +200,71 @@ __global__ __launch_bounds__(256) void augment_depth_kernel(const uint8_t* __res
   target[(int64_t)b * npix + p] = v;
 }
 
+// the launches of the four entry points: one check, one grid (one thread per output pixel, blockIdx.y = sample)
+template <bool COLOUR>
+int launch_augment(const char* what, const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
+                   const int32_t* colour, const uint8_t* ctab, const act_t* lut, act_t* image, uint8_t* mask, int B,
+                   int Ho, int Wo, void* stream) {
+  NASSEG_REQUIRE(B > 0 && B <= 65535 && Ho > 0 && Wo > 0 && src_bytes > 0, "%s: bad shape", what);
+  NASSEG_REQUIRE(!COLOUR || (colour != nullptr && ctab != nullptr && ((uintptr_t)ctab & 3) == 0),
+                 "%s: colour and a 4-byte aligned ctab are required", what);
+  NASSEG_REQUIRE((int64_t)9 * (Ho + Wo) < ((int64_t)1 << 31), "%s: output too large", what);
+  const int64_t npix = (int64_t)Ho * Wo;
+  NASSEG_REQUIRE(cdiv64(npix, 256) < ((int64_t)1 << 31), "%s: output too large", what);
+  hipLaunchKernelGGL(augment_kernel<COLOUR>, dim3((unsigned)cdiv64(npix, 256), B), dim3(256), 0, (hipStream_t)stream,
+                     src, src_bytes, desc, taps, colour, ctab, lut, image, mask, Ho, Wo);
+  NASSEG_LAUNCH_CHECK(what);
+  return NASSEG_OK;
+}
+
+template <bool COLOUR>
+int launch_augment_depth(const char* what, const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
+                         const int32_t* colour, const uint8_t* ctab, const act_t* lut, const float* params,
+                         float depth_scale, act_t* image, float* target, int B, int Ho, int Wo, void* stream) {
+  NASSEG_REQUIRE(B > 0 && B <= 65535 && Ho > 0 && Wo > 0 && src_bytes > 0, "%s: bad shape", what);
+  NASSEG_REQUIRE(params != nullptr && target != nullptr, "%s: params and target are required", what);
+  NASSEG_REQUIRE(!COLOUR || (colour != nullptr && ctab != nullptr && ((uintptr_t)ctab & 3) == 0),
+                 "%s: colour and a 4-byte aligned ctab are required", what);
+  NASSEG_REQUIRE((int64_t)9 * (Ho + Wo) < ((int64_t)1 << 31), "%s: output too large", what);
+  const int64_t npix = (int64_t)Ho * Wo;
+  NASSEG_REQUIRE(cdiv64(npix, 256) < ((int64_t)1 << 31), "%s: output too large", what);
+  hipLaunchKernelGGL(augment_depth_kernel<COLOUR>, dim3((unsigned)cdiv64(npix, 256), B), dim3(256), 0,
+                     (hipStream_t)stream, src, src_bytes, desc, taps, colour, ctab, lut, params, depth_scale, image,
+                     target, Ho, Wo);
+  NASSEG_LAUNCH_CHECK(what);
+  return NASSEG_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int NASSEG_FN(augment)(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
                        const act_t* lut, act_t* image, uint8_t* mask, int B, int Ho, int Wo, void* stream) {
-  NASSEG_REQUIRE(B > 0 && B <= 65535 && Ho > 0 && Wo > 0 && src_bytes > 0, "augment: bad shape");
-  NASSEG_REQUIRE((int64_t)9 * (Ho + Wo) < ((int64_t)1 << 31), "augment: output too large");
-  const int64_t npix = (int64_t)Ho * Wo;
-  NASSEG_REQUIRE(cdiv64(npix, 256) < ((int64_t)1 << 31), "augment: output too large");
-  hipLaunchKernelGGL(augment_kernel, dim3((unsigned)cdiv64(npix, 256), B), dim3(256), 0, (hipStream_t)stream, src,
-                     src_bytes, desc, taps, lut, image, mask, Ho, Wo);
-  NASSEG_LAUNCH_CHECK("augment");
-  return NASSEG_OK;
+  return launch_augment<false>("augment", src, src_bytes, desc, taps, nullptr, nullptr, lut, image, mask, B, Ho, Wo,
+                               stream);
+}
+
+int NASSEG_FN(augment_colour)(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
+                              const int32_t* colour, const uint8_t* ctab, const act_t* lut, act_t* image,
+                              uint8_t* mask, int B, int Ho, int Wo, void* stream) {
+  return launch_augment<true>("augment_colour", src, src_bytes, desc, taps, colour, ctab, lut, image, mask, B, Ho, Wo,
+                              stream);
 }
 
 int NASSEG_FN(augment_depth)(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
                              const act_t* lut, const float* params, float depth_scale, act_t* image, float* target,
                              int B, int Ho, int Wo, void* stream) {
-  NASSEG_REQUIRE(B > 0 && B <= 65535 && Ho > 0 && Wo > 0 && src_bytes > 0, "augment_depth: bad shape");
-  NASSEG_REQUIRE(params != nullptr && target != nullptr, "augment_depth: params and target are required");
-  NASSEG_REQUIRE((int64_t)9 * (Ho + Wo) < ((int64_t)1 << 31), "augment_depth: output too large");
-  const int64_t npix = (int64_t)Ho * Wo;
-  NASSEG_REQUIRE(cdiv64(npix, 256) < ((int64_t)1 << 31), "augment_depth: output too large");
-  hipLaunchKernelGGL(augment_depth_kernel, dim3((unsigned)cdiv64(npix, 256), B), dim3(256), 0, (hipStream_t)stream,
-                     src, src_bytes, desc, taps, lut, params, depth_scale, image, target, Ho, Wo);
-  NASSEG_LAUNCH_CHECK("augment_depth");
-  return NASSEG_OK;
+  return launch_augment_depth<false>("augment_depth", src, src_bytes, desc, taps, nullptr, nullptr, lut, params,
+                                     depth_scale, image, target, B, Ho, Wo, stream);
+}
+
+int NASSEG_FN(augment_depth_colour)(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps,
+                                    const int32_t* colour, const uint8_t* ctab, const act_t* lut, const float* params,
+                                    float depth_scale, act_t* image, float* target, int B, int Ho, int Wo,
+                                    void* stream) {
+  return launch_augment_depth<true>("augment_depth_colour", src, src_bytes, desc, taps, colour, ctab, lut, params,
+                                    depth_scale, image, target, B, Ho, Wo, stream);
 }
 
 }  // extern "C"

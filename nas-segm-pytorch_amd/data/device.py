@@ -13,7 +13,8 @@ opt-in twin.
 
 Pipelines the kernel cannot reproduce are refused (ValueError) when the dataset is built: more than one resize,
 a resize after a window operation (crop, mirror, pad), more than one pad, ``Normalise`` and ``ToTensor`` not the
-last two operations, an operation this module does not know.  Samples it cannot reproduce are refused when they
+last two operations, more than one ``ColourJitter``, one before a resize or after ``Normalise``, an operation this
+module does not know.  Samples it cannot reproduce are refused when they
 arrive: images that are not 3-channel uint8 (the float branch of resize_cubic; RGBA), masks that are not 2-D uint8
 of the image's size.
 
@@ -22,6 +23,12 @@ counts, shipped as little-endian bytes; ``functional.augment_depth`` gathers it 
 writes fp32 metres - count * depth_scale, divided by the fp32 zoom factor where the resize is a DepthResizeScale -
 with the two correctly rounded fp32 operations the host pipeline makes, so the targets are the host's bit for bit
 too.  ``plan_sample`` keeps refusing every mask that is not uint8; depth samples go through ``plan_depth_sample``.
+
+Colour (``datasets.ColourJitter``): its planner makes the operation's draws through the operation's own ``draw()`` and
+the sample carries the integer colour matrix and the byte table (``colour_tables``); ``functional.augment_colour`` /
+``augment_depth_colour`` apply them to every live pixel between the resampling and the Normalise table, in integers, so
+these batches are the host's bit for bit too.  Batches of pipelines without the operation are packed and launched as
+before.
 """
 import numpy as np
 import torch
@@ -51,6 +58,7 @@ class _Plan(object):
         self.zoom = np.float32(1.0)  # what a depth target is divided by (a DepthResizeScale's factor, in fp32)
         self.depth_fill = np.float32(0.0)  # a pad's fill of a depth target
         self.lut = None
+        self.colour = None  # (Mq, Tab) of a ColourJitter's draw, once one ran
 
     @property
     def shape(self):
@@ -148,6 +156,32 @@ def _plan_to_tensor(op, plan):
     pass
 
 
+def _plan_colour(op, plan):
+    """the op's own draws (``draw``: the method ``apply`` calls).  The kernel jitters live pixels only, so a fill
+    that is already there - a Pad BEFORE the op: the host jitters its border too - goes through the same integer
+    function here; a Pad after the op sets its fill afterwards and leaves it as it is."""
+    Mq, Tab = op.draw()
+    if Mq is not None and np.abs(Mq).max() > D.COLOUR_COEF_MAX:
+        raise ValueError("device pipeline: colour coefficients beyond 2^15 ({})".format(Mq.tolist()))
+    plan.colour = (Mq, Tab)
+    plan.img_fill = D.colour_apply(plan.img_fill, Mq, Tab)
+
+
+_CTAB_IDENTITY = np.repeat(np.arange(256, dtype=np.uint8)[None, :], 3, axis=0)
+
+
+def colour_tables(p):
+    """{"colour": int32 [12] = the 9 coefficients row-major, 1 / 0: apply the matrix, 0, 0; "ctab": uint8 [3][256],
+    the identity ramp when the draw made no table} of a plan whose pipeline has a ColourJitter, else {}"""
+    if p.colour is None:
+        return {}
+    Mq, Tab = p.colour
+    words = np.zeros(12, np.int32)
+    words[:9] = ((1 << 12) * np.eye(3, dtype=np.int64) if Mq is None else Mq).ravel()
+    words[9] = Mq is not None
+    return {"colour": words, "ctab": np.ascontiguousarray(_CTAB_IDENTITY if Tab is None else Tab, dtype=np.uint8)}
+
+
 _PLANNERS = {
     D.ResizeScale: _plan_resize_scale,
     D.DepthResizeScale: _plan_depth_resize_scale,
@@ -158,6 +192,7 @@ _PLANNERS = {
     D.Pad: _plan_pad,
     D.Normalise: _plan_normalise,
     D.ToTensor: _plan_to_tensor,
+    D.ColourJitter: _plan_colour,
 }
 _RESIZES = (D.ResizeScale, D.DepthResizeScale, D.ResizeShorter)
 _WINDOWS = (D.RandomMirror, D.RandomCrop, D.CentralCrop, D.Pad)
@@ -170,6 +205,14 @@ def check_pipeline(pipeline):
         if type(op) not in _PLANNERS:
             raise ValueError("device pipeline: no device plan for {}".format(type(op).__name__))
     kinds = [type(op) for op in ops]
+    jitters = [i for i, k in enumerate(kinds) if k is D.ColourJitter]
+    if len(jitters) > 1:
+        raise ValueError("device pipeline: at most one ColourJitter")
+    if jitters and any(k in _RESIZES for k in kinds[jitters[0]:]):
+        raise ValueError("device pipeline: a ColourJitter before a resize (the kernel applies colour after "
+                         "resampling, and the two do not commute)")
+    if jitters and D.Normalise in kinds[:jitters[0]]:
+        raise ValueError("device pipeline: a ColourJitter after Normalise")
     if len(ops) < 2 or kinds[-2] is not D.Normalise or kinds[-1] is not D.ToTensor:
         raise ValueError("device pipeline: Normalise and ToTensor must be the last two operations")
     if kinds.count(D.Normalise) != 1 or kinds.count(D.ToTensor) != 1:
@@ -298,7 +341,7 @@ def plan_sample(pipeline, image, mask):
     return {"image": np.ascontiguousarray(image[r0:r1, c0:c1]), "mask": np.ascontiguousarray(mask[r0:r1, c0:c1]),
             "taps": taps, "fill": (int(p.img_fill[0]) | int(p.img_fill[1]) << 8 | int(p.img_fill[2]) << 16,
                                    p.msk_fill),
-            "lut": p.lut, "size": p.shape}
+            "lut": p.lut, "size": p.shape, **colour_tables(p)}
 
 
 def plan_depth_sample(pipeline, image, counts):
@@ -317,12 +360,14 @@ def plan_depth_sample(pipeline, image, counts):
     return {"image": np.ascontiguousarray(image[r0:r1, c0:c1]),
             "mask": np.ascontiguousarray(counts[r0:r1, c0:c1], dtype="<u2"), "taps": taps,
             "fill": (int(p.img_fill[0]) | int(p.img_fill[1]) << 8 | int(p.img_fill[2]) << 16, 0),
-            "params": np.array([p.zoom, p.depth_fill], np.float32), "lut": p.lut, "size": p.shape}
+            "params": np.array([p.zoom, p.depth_fill], np.float32), "lut": p.lut, "size": p.shape,
+            **colour_tables(p)}
 
 
 def collate(samples):
     """a list of device samples -> {"src": uint8 [bytes], "desc": int64 [B][8], "taps": int32 [B][9 (Ho + Wo)],
-    "lut": float64 [3][256], "size": int64 [2]} (tensors the DataLoader can pin)"""
+    "lut": float64 [3][256], "size": int64 [2]} (tensors the DataLoader can pin); samples of a pipeline with a
+    ColourJitter add "colour": int32 [B][12] and "ctab": uint8 [B][3][256]"""
     size = tuple(samples[0]["size"])
     if any(tuple(s["size"]) != size for s in samples):
         raise RuntimeError("device pipeline: samples of one batch differ in size: {}".format(
@@ -341,9 +386,16 @@ def collate(samples):
         desc[i] = (off, off + img.nbytes, h, w, 3 * w, msk.itemsize * w, s["fill"][0], s["fill"][1])
         chunks += [img.reshape(-1), msk.reshape(-1).view(np.uint8)]
         off += img.nbytes + msk.nbytes
-    return {"src": torch.from_numpy(np.concatenate(chunks)), "desc": torch.from_numpy(desc),
-            "taps": torch.from_numpy(np.stack([s["taps"] for s in samples])), "lut": torch.from_numpy(lut),
-            "size": torch.tensor(size, dtype=torch.int64)}
+    batch = {"src": torch.from_numpy(np.concatenate(chunks)), "desc": torch.from_numpy(desc),
+             "taps": torch.from_numpy(np.stack([s["taps"] for s in samples])), "lut": torch.from_numpy(lut),
+             "size": torch.tensor(size, dtype=torch.int64)}
+    jittered = ["colour" in s for s in samples]
+    if any(jittered):
+        if not all(jittered):
+            raise RuntimeError("device pipeline: samples with and without a ColourJitter in one batch")
+        batch["colour"] = torch.from_numpy(np.stack([s["colour"] for s in samples]).astype(np.int32))
+        batch["ctab"] = torch.from_numpy(np.stack([s["ctab"] for s in samples]).astype(np.uint8))
+    return batch
 
 
 def collate_depth(samples):
@@ -356,13 +408,18 @@ def collate_depth(samples):
 
 def run_batch(batch, device, dtype):
     """one packed batch -> {"image": B x 3 x Ho x Wo channels_last ``dtype``, "mask": B x Ho x Wo uint8} on
-    ``device`` (uploads on the current stream, one augment launch)"""
+    ``device`` (uploads on the current stream, one augment launch: augment_colour for the batches of a pipeline with
+    a ColourJitter)"""
     from .. import functional as F
 
     Ho, Wo = (int(v) for v in batch["size"])
     lut = batch["lut"].to(dtype)  # (on the host: the cast of torch.from_numpy(host image).to(dtype))
-    up = {k: batch[k].to(device, non_blocking=True) for k in ("src", "desc", "taps")}
-    image, mask = F.augment(up["src"], up["desc"], up["taps"], lut.to(device, non_blocking=True), Ho, Wo)
+    up = {k: batch[k].to(device, non_blocking=True) for k in ("src", "desc", "taps", "colour", "ctab") if k in batch}
+    if "colour" in up:
+        image, mask = F.augment_colour(up["src"], up["desc"], up["taps"], up["colour"], up["ctab"],
+                                       lut.to(device, non_blocking=True), Ho, Wo)
+    else:
+        image, mask = F.augment(up["src"], up["desc"], up["taps"], lut.to(device, non_blocking=True), Ho, Wo)
     return {"image": image, "mask": mask}
 
 
@@ -373,9 +430,14 @@ def run_depth_batch(batch, device, dtype, depth_scale):
 
     Ho, Wo = (int(v) for v in batch["size"])
     lut = batch["lut"].to(dtype)
-    up = {k: batch[k].to(device, non_blocking=True) for k in ("src", "desc", "taps", "params")}
-    image, target = F.augment_depth(up["src"], up["desc"], up["taps"], lut.to(device, non_blocking=True),
-                                    up["params"], depth_scale, Ho, Wo)
+    up = {k: batch[k].to(device, non_blocking=True) for k in ("src", "desc", "taps", "params", "colour", "ctab")
+          if k in batch}
+    if "colour" in up:
+        image, target = F.augment_depth_colour(up["src"], up["desc"], up["taps"], up["colour"], up["ctab"],
+                                               lut.to(device, non_blocking=True), up["params"], depth_scale, Ho, Wo)
+    else:
+        image, target = F.augment_depth(up["src"], up["desc"], up["taps"], lut.to(device, non_blocking=True),
+                                        up["params"], depth_scale, Ho, Wo)
     return {"image": image, "mask": target}
 
 
@@ -432,7 +494,7 @@ def create_device_loaders(args, device=None, dtype=torch.float32):
     split, shuffling and drop_last, the same batches (``image`` as ``dtype`` on ``device``, channels_last)
     -> (train_loader, val_loader, do_search)."""
     val_ops = L._pipeline(L._VAL_OPS, args)
-    full = DevicePascalDataset(args.train_list, args.train_dir, L._pipeline(L._TRAIN_OPS, args), val_ops)
+    full = DevicePascalDataset(args.train_list, args.train_dir, L._train_pipeline(args), val_ops)
     do_search = args.train_list == args.val_list
     if do_search:
         n_train = int(len(full) * args.meta_train_prct / 100.0)

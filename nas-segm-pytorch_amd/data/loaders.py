@@ -30,6 +30,16 @@ def _pipeline(table, args):
     return D.Compose([op(*getter(args)) for op, getter in table])
 
 
+def _train_pipeline(args):
+    """the training pipeline; with ``args.colour_jitter`` (a dict of ColourJitter's keywords; optional) that
+    operation at position 3 - after RandomCrop, before Normalise: positions 0 and 2 stay what set_config rewrites"""
+    pipeline = _pipeline(_TRAIN_OPS, args)
+    jitter = getattr(args, "colour_jitter", None)
+    if jitter is not None:
+        pipeline.transforms.insert(3, D.ColourJitter(**jitter))
+    return pipeline
+
+
 def _loader(dataset, batch_size, shuffle, args):
     return DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, num_workers=args.num_workers,
                       pin_memory=True, drop_last=True)
@@ -38,13 +48,14 @@ def _loader(dataset, batch_size, shuffle, args):
 def create_loaders(args):
     """-> (train_loader, val_loader, do_search).  ``args``: train_dir, val_dir, train_list, val_list,
     meta_train_prct, resize_side[0], low_scale, high_scale, resize_longer_side, crop_size[0], val_resize_side,
-    val_crop_size, normalise_params = (scale, mean, std), batch_size[0], val_batch_size, num_workers.
+    val_crop_size, normalise_params = (scale, mean, std), batch_size[0], val_batch_size, num_workers; optionally
+    colour_jitter (ColourJitter's keywords as a dict: that operation in the training pipeline, never in validation).
     Search mode (``do_search``) is train_list == val_list: ``meta_train_prct`` percent of that one list train the
     candidates and the rest scores them (one ``random_split`` draw from torch's global generator); both halves
     share the dataset object, whose stage the engine switches.  Otherwise the validation list is its own dataset.
     Both loaders drop the last incomplete batch; only the training loader shuffles."""
     val_ops = _pipeline(_VAL_OPS, args)
-    full = D.PascalCustomDataset(args.train_list, args.train_dir, _pipeline(_TRAIN_OPS, args), val_ops)
+    full = D.PascalCustomDataset(args.train_list, args.train_dir, _train_pipeline(args), val_ops)
     do_search = args.train_list == args.val_list
     if do_search:
         n_train = int(len(full) * args.meta_train_prct / 100.0)
@@ -61,7 +72,7 @@ def create_loaders(args):
 
 def _depth_train_pipeline(args, zoom_depth):
     """the training pipeline with a DepthResizeScale at position 0 (``zoom_depth``), else as it is"""
-    pipeline = _pipeline(_TRAIN_OPS, args)
+    pipeline = _train_pipeline(args)
     if zoom_depth:
         op = pipeline.transforms[0]
         pipeline.transforms[0] = D.DepthResizeScale(op.resize_side, op.low_scale, op.high_scale, op.longer)

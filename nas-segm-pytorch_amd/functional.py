@@ -3370,18 +3370,26 @@ def gather_rows(src, idx, out=None):
     return out
 
 
+def _packed_batch(what, src, desc, taps, lut, Ho, Wo, params=None):
+    """B of a packed batch of data/device.py (``params``: a depth batch's), or NassegError"""
+    B = desc.shape[0] if desc.dim() == 2 else 0
+    if (src.dtype != torch.uint8 or desc.dtype != torch.int64 or taps.dtype != torch.int32
+            or lut.dtype not in (torch.float32, torch.bfloat16) or src.dim() != 1 or B == 0
+            or tuple(desc.shape) != (B, 8) or tuple(taps.shape) != (B, 9 * (Ho + Wo)) or tuple(lut.shape) != (3, 256)
+            or not all(t.is_contiguous() for t in (src, desc, taps, lut))
+            or (params is not None and (params.dtype != torch.float32 or tuple(params.shape) != (B, 2)
+                                        or not params.is_contiguous()))):
+        raise NassegError("{}: bad packed batch".format(what))
+    return B
+
+
 def augment(src, desc, taps, lut, Ho, Wo):
     """The sample pipelines of data/datasets.py for one packed batch (data/device.py plans and packs it): uint8
     ``src`` (the source windows), int64 ``desc`` [B][8], int32 ``taps`` [B][9 (Ho + Wo)] and the Normalise table
     ``lut`` [3][256] of the output dtype (fp32 or bf16) -> (image B x 3 x Ho x Wo channels_last, mask uint8
     B x Ho x Wo); one nasseg_augment launch (include/nasseg.h)."""
     require_device(src, desc, taps, lut)
-    B = desc.shape[0] if desc.dim() == 2 else 0
-    if (src.dtype != torch.uint8 or desc.dtype != torch.int64 or taps.dtype != torch.int32
-            or lut.dtype not in (torch.float32, torch.bfloat16) or src.dim() != 1 or B == 0
-            or tuple(desc.shape) != (B, 8) or tuple(taps.shape) != (B, 9 * (Ho + Wo)) or tuple(lut.shape) != (3, 256)
-            or not all(t.is_contiguous() for t in (src, desc, taps, lut))):
-        raise NassegError("augment: bad packed batch")
+    B = _packed_batch("augment", src, desc, taps, lut, Ho, Wo)
     image = torch.empty((B, 3, Ho, Wo), device=src.device, dtype=lut.dtype, memory_format=torch.channels_last)
     mask = torch.empty((B, Ho, Wo), device=src.device, dtype=torch.uint8)
     lib.call(_k("nasseg_augment", lut), ptr(src), src.numel(), ptr(desc), ptr(taps), ptr(lut), ptr(image),
@@ -3396,17 +3404,48 @@ def augment_depth(src, desc, taps, lut, params, depth_scale, Ho, Wo):
     count * depth_scale / zoom in correctly rounded fp32, or the fill undivided); one nasseg_augment_depth launch
     (include/nasseg.h)."""
     require_device(src, desc, taps, lut, params)
-    B = desc.shape[0] if desc.dim() == 2 else 0
-    if (src.dtype != torch.uint8 or desc.dtype != torch.int64 or taps.dtype != torch.int32
-            or lut.dtype not in (torch.float32, torch.bfloat16) or src.dim() != 1 or B == 0
-            or tuple(desc.shape) != (B, 8) or tuple(taps.shape) != (B, 9 * (Ho + Wo)) or tuple(lut.shape) != (3, 256)
-            or params.dtype != torch.float32 or tuple(params.shape) != (B, 2)
-            or not all(t.is_contiguous() for t in (src, desc, taps, lut, params))):
-        raise NassegError("augment_depth: bad packed batch")
+    B = _packed_batch("augment_depth", src, desc, taps, lut, Ho, Wo, params)
     image = torch.empty((B, 3, Ho, Wo), device=src.device, dtype=lut.dtype, memory_format=torch.channels_last)
     target = torch.empty((B, Ho, Wo), device=src.device, dtype=torch.float32)
     lib.call(_k("nasseg_augment_depth", lut), ptr(src), src.numel(), ptr(desc), ptr(taps), ptr(lut), ptr(params),
              float(depth_scale), ptr(image), ptr(target), B, Ho, Wo, current_stream())
+    return image, target
+
+
+def _require_colour(what, B, colour, ctab):
+    """the two per-sample tables of the colour launches: int32 [B][12], uint8 [B][3][256], contiguous"""
+    if (colour.dtype != torch.int32 or tuple(colour.shape) != (B, 12) or not colour.is_contiguous()
+            or ctab.dtype != torch.uint8 or tuple(ctab.shape) != (B, 3, 256) or not ctab.is_contiguous()
+            or ctab.data_ptr() % 4 != 0):
+        raise NassegError("{}: colour must be contiguous int32 [B][12] and ctab contiguous uint8 [B][3][256]".format(
+            what))
+
+
+def augment_colour(src, desc, taps, colour, ctab, lut, Ho, Wo):
+    """``augment`` with a ColourJitter (data/datasets.py) between the resampling and ``lut``: int32 ``colour``
+    [B][12] (the sample's 12-bit colour matrix row-major, 1 / 0: apply it, two zeros) and uint8 ``ctab`` [B][3][256]
+    (its point table per channel); fill pixels skip both.  One nasseg_augment_colour launch (include/nasseg.h)."""
+    require_device(src, desc, taps, colour, ctab, lut)
+    B = _packed_batch("augment_colour", src, desc, taps, lut, Ho, Wo)
+    _require_colour("augment_colour", B, colour, ctab)
+    image = torch.empty((B, 3, Ho, Wo), device=src.device, dtype=lut.dtype, memory_format=torch.channels_last)
+    mask = torch.empty((B, Ho, Wo), device=src.device, dtype=torch.uint8)
+    lib.call(_k("nasseg_augment_colour", lut), ptr(src), src.numel(), ptr(desc), ptr(taps), ptr(colour), ptr(ctab),
+             ptr(lut), ptr(image), ptr(mask), B, Ho, Wo, current_stream())
+    return image, mask
+
+
+def augment_depth_colour(src, desc, taps, colour, ctab, lut, params, depth_scale, Ho, Wo):
+    """``augment_depth`` with ``augment_colour``'s jitter of the image; the target is ``augment_depth``'s.  One
+    nasseg_augment_depth_colour launch (include/nasseg.h)."""
+    require_device(src, desc, taps, colour, ctab, lut, params)
+    B = _packed_batch("augment_depth_colour", src, desc, taps, lut, Ho, Wo, params)
+    _require_colour("augment_depth_colour", B, colour, ctab)
+    image = torch.empty((B, 3, Ho, Wo), device=src.device, dtype=lut.dtype, memory_format=torch.channels_last)
+    target = torch.empty((B, Ho, Wo), device=src.device, dtype=torch.float32)
+    lib.call(_k("nasseg_augment_depth_colour", lut), ptr(src), src.numel(), ptr(desc), ptr(taps), ptr(colour),
+             ptr(ctab), ptr(lut), ptr(params), float(depth_scale), ptr(image), ptr(target), B, Ho, Wo,
+             current_stream())
     return image, target
 
 

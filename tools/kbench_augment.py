@@ -13,8 +13,13 @@
            create_depth_loaders against create_device_depth_loaders on synthetic 640 x 480 RGB + 16-bit depth PNG
            pairs written to a temporary directory (batch 32, 16 workers, first batch not counted).
 
-usage (GPU box): python tools/kbench_augment.py [kernel|loader|all] [--depth]   (KBENCH_BATCHES: loader batches,
-default 24).  One JSON line per measurement on stdout."""
+  --colour the ColourJitter launches (nasseg_augment_colour, with --depth nasseg_augment_depth_colour).  kernel: us per
+           batch of the colour launch beside the plain launch ON THE SAME PACKED BATCH (WACV search training shape; the
+           --depth shape), every sample jittered (matrix and table): 9 rounds alternating the two, 200 launches each,
+           median and min / max over the rounds.  loader: the two loaders with args.colour_jitter set.
+
+usage (GPU box): python tools/kbench_augment.py [kernel|loader|all] [--depth] [--colour]   (KBENCH_BATCHES: loader
+batches, default 24).  One JSON line per measurement on stdout."""
 import json
 import os
 import sys
@@ -81,7 +86,84 @@ def time_kernel(n=50):
                               "out_GBps": round(out_bytes / us / 1e3, 1)}), flush=True)
 
 
-def time_loaders(n_batches):
+JITTER = dict(brightness=0.2, contrast=0.3, gamma=0.2, saturation=0.5, hue=0.05)
+
+
+def colour_tables(B):
+    """[B][12] / [B][3][256] on the device: one draw of ColourJitter(**JITTER) per sample, all of them jittered"""
+    op = D.ColourJitter(**JITTER)
+    tabs = [dev.colour_tables(types.SimpleNamespace(colour=op.draw())) for _ in range(B)]
+    return (torch.from_numpy(np.stack([t["colour"] for t in tabs])).to(DEV),
+            torch.from_numpy(np.stack([t["ctab"] for t in tabs])).to(DEV))
+
+
+def alternate(launches, rounds=9, n=200):
+    """{name: [us per launch of each round]}: the launches warmed up, then timed in turn, ``rounds`` times"""
+    for fn in launches.values():
+        for _ in range(10):
+            fn()
+    torch.cuda.synchronize()
+    us = {name: [] for name in launches}
+    for _ in range(rounds):
+        for name, fn in launches.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us[name].append(e0.elapsed_time(e1) / n * 1e3)
+    return us
+
+
+def report_colour(kernel, dtype, B, Ho, Wo, us):
+    med = {k: float(np.median(v)) for k, v in us.items()}
+    print(json.dumps({"kernel": kernel, "dtype": str(dtype)[6:], "B": B, "Ho": Ho, "Wo": Wo,
+                      "plain_us": round(med["plain"], 1), "plain_min_max": [round(min(us["plain"]), 1),
+                                                                            round(max(us["plain"]), 1)],
+                      "colour_us": round(med["colour"], 1), "colour_min_max": [round(min(us["colour"]), 1),
+                                                                               round(max(us["colour"]), 1)],
+                      "colour_over_plain": round(med["colour"] / med["plain"], 3)}), flush=True)
+
+
+def time_colour_kernel():
+    rng = np.random.RandomState(0)
+    sources = [synthetic(rng) for _ in range(4)]
+    pipe, B = pipelines()["wacv_train_b32"]
+    np.random.seed(0)
+    batch = dev.collate([dev.plan_sample(pipe, *sources[i % 4]) for i in range(B)])
+    Ho, Wo = (int(v) for v in batch["size"])
+    up = {k: batch[k].to(DEV) for k in ("src", "desc", "taps")}
+    colour, ctab = colour_tables(B)
+    for dtype in (torch.float32, torch.bfloat16):
+        lut = batch["lut"].to(dtype).to(DEV)
+        us = alternate({"plain": lambda: F.augment(up["src"], up["desc"], up["taps"], lut, Ho, Wo),
+                        "colour": lambda: F.augment_colour(up["src"], up["desc"], up["taps"], colour, ctab, lut, Ho,
+                                                           Wo)})
+        report_colour("wacv_train_b32", dtype, B, Ho, Wo, us)
+
+
+def time_depth_colour_kernel():
+    rng = np.random.RandomState(0)
+    sources = [synthetic_depth(rng) for _ in range(4)]
+    pipe = D.Compose([D.DepthResizeScale(320, 0.7, 1.4), D.RandomMirror(), D.RandomCrop(320), D.Normalise(*NORM),
+                      D.ToTensor()])
+    B = 32
+    np.random.seed(0)
+    batch = dev.collate_depth([dev.plan_depth_sample(pipe, *sources[i % 4]) for i in range(B)])
+    Ho, Wo = (int(v) for v in batch["size"])
+    up = {k: batch[k].to(DEV) for k in ("src", "desc", "taps", "params")}
+    colour, ctab = colour_tables(B)
+    for dtype in (torch.float32, torch.bfloat16):
+        lut = batch["lut"].to(dtype).to(DEV)
+        us = alternate({"plain": lambda: F.augment_depth(up["src"], up["desc"], up["taps"], lut, up["params"], 1e-3,
+                                                         Ho, Wo),
+                        "colour": lambda: F.augment_depth_colour(up["src"], up["desc"], up["taps"], colour, ctab, lut,
+                                                                 up["params"], 1e-3, Ho, Wo)})
+        report_colour("depth_train_b32", dtype, B, Ho, Wo, us)
+
+
+def time_loaders(n_batches, colour=False):
     from nas_segm_amd.data import create_loaders
     from nas_segm_amd.engine.trainer import _labels, _to_device_image
 
@@ -102,7 +184,7 @@ def time_loaders(n_batches):
             train_dir=tmp, val_dir=tmp, train_list=lst, val_list=lst + ".val", meta_train_prct=80,
             resize_side=[1024], low_scale=0.7, high_scale=1.4, resize_longer_side=True, crop_size=[321],
             val_resize_side=1024, val_crop_size=512, normalise_params=list(NORM), batch_size=[B], val_batch_size=B,
-            num_workers=16)
+            num_workers=16, colour_jitter=JITTER if colour else None)
         with open(args.val_list, "w") as fh:
             fh.write("i0.png\tm0.png\n")
         results = {}
@@ -125,8 +207,8 @@ def time_loaders(n_batches):
                     seen += image.shape[0]
             dt = time.perf_counter() - t0
             results[name] = seen / dt
-            print(json.dumps({"loader": name, "workers": 16, "batch": B, "images": seen, "s": round(dt, 2),
-                              "images_per_s": round(seen / dt, 1), "image": list(image.shape),
+            print(json.dumps({"loader": name, "colour": colour, "workers": 16, "batch": B, "images": seen,
+                              "s": round(dt, 2), "images_per_s": round(seen / dt, 1), "image": list(image.shape),
                               "dtype": str(image.dtype)[6:]}), flush=True)
         print(json.dumps({"loader": "device_over_host", "ratio": round(results["device"] / results["host"], 2)}))
 
@@ -178,7 +260,7 @@ def time_depth_kernel(n=50):
                           "out_GBps": round(out_bytes / us / 1e3, 1)}), flush=True)
 
 
-def time_depth_loaders(n_batches):
+def time_depth_loaders(n_batches, colour=False):
     from nas_segm_amd.data import create_depth_loaders
     from nas_segm_amd.engine.trainer import _depth_target, _to_device_image
 
@@ -196,6 +278,7 @@ def time_depth_loaders(n_batches):
         with open(lst, "w") as fh:
             fh.write("".join("i{0}.png\td{0}.png\n".format(i % n_files) for i in range((n_batches + 1) * B)))
         args = depth_args(tmp, lst, B, 16)
+        args.colour_jitter = JITTER if colour else None
         with open(args.val_list, "w") as fh:
             fh.write("i0.png\td0.png\n")
         results = {}
@@ -219,7 +302,7 @@ def time_depth_loaders(n_batches):
                     seen += image.shape[0]
             dt = time.perf_counter() - t0
             results[name] = seen / dt
-            print(json.dumps({"depth_loader": name, "workers": 16, "batch": B, "images": seen, "s": round(dt, 2),
+            print(json.dumps({"depth_loader": name, "colour": colour, "workers": 16, "batch": B, "images": seen, "s": round(dt, 2),
                               "images_per_s": round(seen / dt, 1), "image": list(image.shape),
                               "dtype": str(image.dtype)[6:], "target": str(target.dtype)[6:]}), flush=True)
         print(json.dumps({"depth_loader": "device_over_host",
@@ -227,10 +310,13 @@ def time_depth_loaders(n_batches):
 
 
 if __name__ == "__main__":
-    argv = [a for a in sys.argv[1:] if a != "--depth"]
-    depth = "--depth" in sys.argv[1:]
+    argv = [a for a in sys.argv[1:] if a not in ("--depth", "--colour")]
+    depth, colour = "--depth" in sys.argv[1:], "--colour" in sys.argv[1:]
     what = argv[0] if argv else "all"
     if what in ("kernel", "all"):
-        (time_depth_kernel if depth else time_kernel)()
+        if colour:
+            (time_depth_colour_kernel if depth else time_colour_kernel)()
+        else:
+            (time_depth_kernel if depth else time_kernel)()
     if what in ("loader", "all"):
-        (time_depth_loaders if depth else time_loaders)(int(os.environ.get("KBENCH_BATCHES", "24")))
+        (time_depth_loaders if depth else time_loaders)(int(os.environ.get("KBENCH_BATCHES", "24")), colour)
