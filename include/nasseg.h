@@ -941,7 +941,9 @@ int nasseg_graph_run(int n_ops, const int64_t* ops, void* stream);
  * [B][9 (Ho + Wo)] = rows [Ho][4 indices, 4 coefficients], columns [Wo][4, 4] (OpenCV's 11-bit INTER_CUBIC
  * coefficients; index -1: a fill pixel), mask rows [Ho], mask columns [Wo] (nearest index, -1: fill), indices
  * into the window; lut [3][256]: output value of channel c for the uint8 result v.  Writes image [B][Ho][Wo][3]
- * (NHWC) and mask uint8 [B][Ho][Wo] (mask null: no mask is written). */
+ * (NHWC) and mask uint8 [B][Ho][Wo] (mask null: no mask is written).  A window - image, mask or counts, of e bytes
+ * per element - lies inside src when h > 0, w > 0, 0 <= offset <= src_bytes, e w <= stride <= src_bytes and offset +
+ * (h - 1) stride + e w <= src_bytes, so a single-row window whose stride exceeds src_bytes is read as fill too. */
 int nasseg_augment(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int* taps, const float* lut,
                    float* image, uint8_t* mask, int B, int Ho, int Wo, void* stream);
 /* The same launch for a metric depth target instead of a label map (data/device.py: run_depth_batch).  The image

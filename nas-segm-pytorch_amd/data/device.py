@@ -30,15 +30,20 @@ the sample carries the integer colour matrix and the byte table (``colour_tables
 these batches are the host's bit for bit too.  Batches of pipelines without the operation are packed and launched as
 before.
 """
+import collections
+import os
+
 import numpy as np
 import torch
-from torch.utils.data import DataLoader, random_split
 
 from . import datasets as D
 from . import loaders as L
 
 _IDENTITY_COEF = np.array([0, D._COEF_SCALE, 0, 0], np.int64)  # (2048 * 2048 * v + 2^21) >> 22 == v
-DESC_FIELDS = 8  # csrc/augment.hip: offsets, window height / width, row strides, fills
+# a sample's descriptor, int64 [DESC_FIELDS]: offsets, window height / width, row strides (bytes), fills, in the order
+# of the enum in csrc/augment.hip, which defines it
+Desc = collections.namedtuple("Desc", "img_off msk_off h w img_ld msk_ld img_fill msk_fill")
+DESC_FIELDS = len(Desc._fields)
 
 
 # ---------------------------------------------------------------------------
@@ -292,21 +297,31 @@ def tables(p):
 # ---------------------------------------------------------------------------
 # dataset, batches, loader
 # ---------------------------------------------------------------------------
+def _check_pipelines(*pipelines):
+    for pipeline in pipelines:
+        if pipeline is not None:
+            check_pipeline(pipeline)
+
+
+def _stage_pipeline(dataset):
+    """the pipeline of the dataset's current stage, or ValueError"""
+    pipeline = getattr(dataset, dataset._PIPELINE_OF_STAGE.get(dataset.stage, ""), None)
+    if pipeline is None:
+        raise ValueError("device pipeline: stage {!r} has no pipeline".format(dataset.stage))
+    return pipeline
+
+
 class DeviceDepthDataset(D.DepthDataset):
     """DepthDataset whose samples are plans (``plan_depth_sample``): the workers decode the image and the 16-bit
     depth file - the counts stay integers; the metres are made on the GPU - and plan the stage's pipeline."""
 
     def __init__(self, data_file, data_dir, transform_trn=None, transform_val=None, depth_scale=1e-3):
-        for pipeline in (transform_trn, transform_val):
-            if pipeline is not None:
-                check_pipeline(pipeline)
+        _check_pipelines(transform_trn, transform_val)
         super(DeviceDepthDataset, self).__init__(data_file, data_dir, transform_trn, transform_val, depth_scale)
 
     def __getitem__(self, idx):
         image_file, depth_file = self._files(idx)
-        pipeline = getattr(self, self._PIPELINE_OF_STAGE.get(self.stage, ""), None)
-        if pipeline is None:
-            raise ValueError("device pipeline: stage {!r} has no pipeline".format(self.stage))
+        pipeline = _stage_pipeline(self)
         return plan_depth_sample(pipeline, D._load_rgb(image_file), D._load_depth_counts(depth_file))
 
 
@@ -316,32 +331,33 @@ class DevicePascalDataset(D.PascalCustomDataset):
     "fill", "lut", "size"}; ``collate`` packs a batch, ``DeviceLoader`` runs it on the GPU."""
 
     def __init__(self, data_file, data_dir, transform_trn=None, transform_val=None):
-        for pipeline in (transform_trn, transform_val):
-            if pipeline is not None:
-                check_pipeline(pipeline)
+        _check_pipelines(transform_trn, transform_val)
         super(DevicePascalDataset, self).__init__(data_file, data_dir, transform_trn, transform_val)
 
     def __getitem__(self, idx):
-        import os
-
         image_file, mask_file = (os.path.join(self.root_dir, name) for name in self.datalist[idx])
         image = D._load_rgb(image_file)
         mask = D._load_mask(mask_file, image_file != mask_file)
-        pipeline = getattr(self, self._PIPELINE_OF_STAGE.get(self.stage, ""), None)
-        if pipeline is None:
-            raise ValueError("device pipeline: stage {!r} has no pipeline".format(self.stage))
-        return plan_sample(pipeline, image, mask)
+        return plan_sample(_stage_pipeline(self), image, mask)
+
+
+def _planned(pipeline, image):
+    """-> (the plan, the window of the source it reaches as (row slice, column slice), the image's packed fill, the
+    image half of the device sample) of a checked image under ``pipeline``; the caller adds "mask", "fill" and what
+    else its target needs"""
+    p = plan(pipeline, image.shape[0], image.shape[1])
+    (r0, r1), (c0, c1), taps = tables(p)
+    window = (slice(r0, r1), slice(c0, c1))
+    img_fill = int(p.img_fill[0]) | int(p.img_fill[1]) << 8 | int(p.img_fill[2]) << 16
+    return p, window, img_fill, {"image": np.ascontiguousarray(image[window]), "taps": taps, "lut": p.lut,
+                                 "size": p.shape, **colour_tables(p)}
 
 
 def plan_sample(pipeline, image, mask):
     """the device sample of (image, mask) under ``pipeline``"""
     check_sample(image, mask)
-    p = plan(pipeline, image.shape[0], image.shape[1])
-    (r0, r1), (c0, c1), taps = tables(p)
-    return {"image": np.ascontiguousarray(image[r0:r1, c0:c1]), "mask": np.ascontiguousarray(mask[r0:r1, c0:c1]),
-            "taps": taps, "fill": (int(p.img_fill[0]) | int(p.img_fill[1]) << 8 | int(p.img_fill[2]) << 16,
-                                   p.msk_fill),
-            "lut": p.lut, "size": p.shape, **colour_tables(p)}
+    p, window, img_fill, sample = _planned(pipeline, image)
+    return dict(sample, mask=np.ascontiguousarray(mask[window]), fill=(img_fill, p.msk_fill))
 
 
 def plan_depth_sample(pipeline, image, counts):
@@ -355,13 +371,9 @@ def plan_depth_sample(pipeline, image, counts):
     if counts.shape != image.shape[:2]:
         raise ValueError("device pipeline: the depth target must be HxW of its image (got {} for {})".format(
             counts.shape, image.shape))
-    p = plan(pipeline, image.shape[0], image.shape[1])
-    (r0, r1), (c0, c1), taps = tables(p)
-    return {"image": np.ascontiguousarray(image[r0:r1, c0:c1]),
-            "mask": np.ascontiguousarray(counts[r0:r1, c0:c1], dtype="<u2"), "taps": taps,
-            "fill": (int(p.img_fill[0]) | int(p.img_fill[1]) << 8 | int(p.img_fill[2]) << 16, 0),
-            "params": np.array([p.zoom, p.depth_fill], np.float32), "lut": p.lut, "size": p.shape,
-            **colour_tables(p)}
+    p, window, img_fill, sample = _planned(pipeline, image)
+    return dict(sample, mask=np.ascontiguousarray(counts[window], dtype="<u2"), fill=(img_fill, 0),
+                params=np.array([p.zoom, p.depth_fill], np.float32))
 
 
 def collate(samples):
@@ -383,7 +395,8 @@ def collate(samples):
         img, msk = s["image"], s["mask"]
         h, w = msk.shape
         # (row strides in bytes: uint8 label maps, or the little-endian uint16 counts of a depth sample)
-        desc[i] = (off, off + img.nbytes, h, w, 3 * w, msk.itemsize * w, s["fill"][0], s["fill"][1])
+        desc[i] = Desc(img_off=off, msk_off=off + img.nbytes, h=h, w=w, img_ld=3 * w, msk_ld=msk.itemsize * w,
+                       img_fill=s["fill"][0], msk_fill=s["fill"][1])
         chunks += [img.reshape(-1), msk.reshape(-1).view(np.uint8)]
         off += img.nbytes + msk.nbytes
     batch = {"src": torch.from_numpy(np.concatenate(chunks)), "desc": torch.from_numpy(desc),
@@ -412,33 +425,38 @@ def run_batch(batch, device, dtype):
     a ColourJitter)"""
     from .. import functional as F
 
-    Ho, Wo = (int(v) for v in batch["size"])
-    lut = batch["lut"].to(dtype)  # (on the host: the cast of torch.from_numpy(host image).to(dtype))
-    up = {k: batch[k].to(device, non_blocking=True) for k in ("src", "desc", "taps", "colour", "ctab") if k in batch}
+    Ho, Wo, up = _uploaded(batch, device, dtype, ("src", "desc", "taps", "colour", "ctab"))
     if "colour" in up:
-        image, mask = F.augment_colour(up["src"], up["desc"], up["taps"], up["colour"], up["ctab"],
-                                       lut.to(device, non_blocking=True), Ho, Wo)
+        image, mask = F.augment_colour(up["src"], up["desc"], up["taps"], up["colour"], up["ctab"], up["lut"], Ho, Wo)
     else:
-        image, mask = F.augment(up["src"], up["desc"], up["taps"], lut.to(device, non_blocking=True), Ho, Wo)
+        image, mask = F.augment(up["src"], up["desc"], up["taps"], up["lut"], Ho, Wo)
     return {"image": image, "mask": mask}
 
 
 def run_depth_batch(batch, device, dtype, depth_scale):
     """one packed depth batch -> {"image": B x 3 x Ho x Wo channels_last ``dtype``, "mask": B x Ho x Wo float32
-    metres} on ``device`` (uploads on the current stream, one augment_depth launch)"""
+    metres} on ``device`` (uploads on the current stream, one augment_depth launch: augment_depth_colour for the
+    batches of a pipeline with a ColourJitter)"""
     from .. import functional as F
 
-    Ho, Wo = (int(v) for v in batch["size"])
-    lut = batch["lut"].to(dtype)
-    up = {k: batch[k].to(device, non_blocking=True) for k in ("src", "desc", "taps", "params", "colour", "ctab")
-          if k in batch}
+    Ho, Wo, up = _uploaded(batch, device, dtype, ("src", "desc", "taps", "params", "colour", "ctab"))
     if "colour" in up:
         image, target = F.augment_depth_colour(up["src"], up["desc"], up["taps"], up["colour"], up["ctab"],
-                                               lut.to(device, non_blocking=True), up["params"], depth_scale, Ho, Wo)
+                                               up["lut"], up["params"], depth_scale, Ho, Wo)
     else:
-        image, target = F.augment_depth(up["src"], up["desc"], up["taps"], lut.to(device, non_blocking=True),
-                                        up["params"], depth_scale, Ho, Wo)
+        image, target = F.augment_depth(up["src"], up["desc"], up["taps"], up["lut"], up["params"], depth_scale,
+                                        Ho, Wo)
     return {"image": image, "mask": target}
+
+
+def _uploaded(batch, device, dtype, keys):
+    """-> (Ho, Wo, those of ``keys`` the packed batch has, on ``device``, and its "lut" as ``dtype`` there): the
+    uploads of the two functions above, on the current stream"""
+    Ho, Wo = (int(v) for v in batch["size"])
+    lut = batch["lut"].to(dtype)  # (on the host: the cast of torch.from_numpy(host image).to(dtype))
+    up = {k: batch[k].to(device, non_blocking=True) for k in keys if k in batch}
+    up["lut"] = lut.to(device, non_blocking=True)
+    return Ho, Wo, up
 
 
 class DeviceLoader(object):
@@ -480,56 +498,26 @@ class DeviceDepthLoader(DeviceLoader):
         return run_depth_batch(batch, device, self.dtype, self.depth_scale)
 
 
-def _data_loader(dataset, batch_size, shuffle, args, collate_fn):
-    return DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, num_workers=args.num_workers,
-                      pin_memory=True, drop_last=True, collate_fn=collate_fn)
-
-
-def _loader(dataset, batch_size, shuffle, args, device, dtype):
-    return DeviceLoader(_data_loader(dataset, batch_size, shuffle, args, collate), device, dtype)
-
-
 def create_device_loaders(args, device=None, dtype=torch.float32):
     """create_loaders(args) (loaders.py) with the augmentation on the GPU: the same ``args`` fields, search-mode
     split, shuffling and drop_last, the same batches (``image`` as ``dtype`` on ``device``, channels_last)
     -> (train_loader, val_loader, do_search)."""
-    val_ops = L._pipeline(L._VAL_OPS, args)
-    full = DevicePascalDataset(args.train_list, args.train_dir, L._train_pipeline(args), val_ops)
-    do_search = args.train_list == args.val_list
-    if do_search:
-        n_train = int(len(full) * args.meta_train_prct / 100.0)
-        train_part, val_part = random_split(full, [n_train, len(full) - n_train])
-    else:
-        train_part = full
-        val_part = DevicePascalDataset(args.val_list, args.val_dir, None, val_ops)
-    L.log.info("data (device augmentation): %d training / %d validation samples (%s)", len(train_part),
-               len(val_part), "search split" if do_search else "separate lists")
-    return (_loader(train_part, args.batch_size[0], True, args, device, dtype),
-            _loader(val_part, args.val_batch_size, False, args, device, dtype), do_search)
+    def loader(part, batch_size, shuffle, args):
+        return DeviceLoader(L._loader(part, batch_size, shuffle, args, collate), device, dtype)
+
+    return L._split_loaders(args, DevicePascalDataset, L._train_pipeline, loader, "data (device augmentation)")
 
 
 def create_device_depth_loaders(args, device=None, dtype=torch.float32, depth_scale=1e-3, zoom_depth=True):
     """create_depth_loaders(args, depth_scale, zoom_depth) (loaders.py) with the augmentation on the GPU: the same
     ``args`` fields, search-mode split, shuffling and drop_last, the same batches (``image`` as ``dtype`` on
     ``device``, channels_last; ``mask`` float32 metres on ``device``) -> (train_loader, val_loader, do_search)."""
-    val_ops = L._pipeline(L._VAL_OPS, args)
-    full = DeviceDepthDataset(args.train_list, args.train_dir, L._depth_train_pipeline(args, zoom_depth), val_ops,
-                              depth_scale)
-    do_search = args.train_list == args.val_list
-    if do_search:
-        n_train = int(len(full) * args.meta_train_prct / 100.0)
-        train_part, val_part = random_split(full, [n_train, len(full) - n_train])
-    else:
-        train_part = full
-        val_part = DeviceDepthDataset(args.val_list, args.val_dir, None, val_ops, depth_scale)
-    L.log.info("depth data (device augmentation): %d training / %d validation samples (%s)", len(train_part),
-               len(val_part), "search split" if do_search else "separate lists")
+    def loader(part, batch_size, shuffle, args):
+        return DeviceDepthLoader(L._loader(part, batch_size, shuffle, args, collate_depth), device, dtype, depth_scale)
 
-    def loader(part, batch_size, shuffle):
-        return DeviceDepthLoader(_data_loader(part, batch_size, shuffle, args, collate_depth), device, dtype,
-                                 depth_scale)
-
-    return loader(train_part, args.batch_size[0], True), loader(val_part, args.val_batch_size, False), do_search
+    return L._split_loaders(args, lambda *files_and_pipelines: DeviceDepthDataset(*files_and_pipelines, depth_scale),
+                            lambda a: L._depth_train_pipeline(a, zoom_depth), loader,
+                            "depth data (device augmentation)")
 
 
 def create_loaders(args):

@@ -40,9 +40,29 @@ def _train_pipeline(args):
     return pipeline
 
 
-def _loader(dataset, batch_size, shuffle, args):
+def _loader(dataset, batch_size, shuffle, args, collate_fn=None):
     return DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, num_workers=args.num_workers,
-                      pin_memory=True, drop_last=True)
+                      pin_memory=True, drop_last=True, collate_fn=collate_fn)
+
+
+def _split_loaders(args, dataset, train_pipeline, loader, word):
+    """The body of every create_*loaders, here and in device.py -> (train_loader, val_loader, do_search).
+    ``dataset(list file, directory, training pipeline or None, validation pipeline)`` makes a dataset,
+    ``train_pipeline(args)`` the training pipeline, ``loader(dataset, batch_size, shuffle, args)`` a loader; ``word``
+    starts the log line."""
+    val_ops = _pipeline(_VAL_OPS, args)
+    full = dataset(args.train_list, args.train_dir, train_pipeline(args), val_ops)
+    do_search = args.train_list == args.val_list
+    if do_search:
+        n_train = int(len(full) * args.meta_train_prct / 100.0)
+        train_part, val_part = random_split(full, [n_train, len(full) - n_train])
+    else:
+        train_part = full
+        val_part = dataset(args.val_list, args.val_dir, None, val_ops)
+    log.info(word + ": %d training / %d validation samples (%s)", len(train_part), len(val_part),
+             "search split" if do_search else "separate lists")
+    return (loader(train_part, args.batch_size[0], True, args), loader(val_part, args.val_batch_size, False, args),
+            do_search)
 
 
 def create_loaders(args):
@@ -54,20 +74,7 @@ def create_loaders(args):
     candidates and the rest scores them (one ``random_split`` draw from torch's global generator); both halves
     share the dataset object, whose stage the engine switches.  Otherwise the validation list is its own dataset.
     Both loaders drop the last incomplete batch; only the training loader shuffles."""
-    val_ops = _pipeline(_VAL_OPS, args)
-    full = D.PascalCustomDataset(args.train_list, args.train_dir, _train_pipeline(args), val_ops)
-    do_search = args.train_list == args.val_list
-    if do_search:
-        n_train = int(len(full) * args.meta_train_prct / 100.0)
-        train_part, val_part = random_split(full, [n_train, len(full) - n_train])
-    else:
-        train_part = full
-        val_part = D.PascalCustomDataset(args.val_list, args.val_dir, None, val_ops)
-    log.info("data: %d training / %d validation samples (%s)", len(train_part), len(val_part),
-             "search split" if do_search else "separate lists")
-    return (_loader(train_part, args.batch_size[0], True, args),
-            _loader(val_part, args.val_batch_size, False, args), do_search)
-
+    return _split_loaders(args, D.PascalCustomDataset, _train_pipeline, _loader, "data")
 
 
 def _depth_train_pipeline(args, zoom_depth):
@@ -86,17 +93,5 @@ def create_depth_loaders(args, depth_scale=1e-3, zoom_depth=True):
     nn.BerHuLoss and ``validate_depth`` take.  The same ``args`` fields, search-mode split (one ``random_split``
     draw), shuffling and drop_last.  ``zoom_depth``: the training pipeline's random zoom divides the target by its
     factor (DepthResizeScale); the validation pipeline never does - its scores are in true metres."""
-    val_ops = _pipeline(_VAL_OPS, args)
-    full = D.DepthDataset(args.train_list, args.train_dir, _depth_train_pipeline(args, zoom_depth), val_ops,
-                          depth_scale)
-    do_search = args.train_list == args.val_list
-    if do_search:
-        n_train = int(len(full) * args.meta_train_prct / 100.0)
-        train_part, val_part = random_split(full, [n_train, len(full) - n_train])
-    else:
-        train_part = full
-        val_part = D.DepthDataset(args.val_list, args.val_dir, None, val_ops, depth_scale)
-    log.info("depth data: %d training / %d validation samples (%s)", len(train_part), len(val_part),
-             "search split" if do_search else "separate lists")
-    return (_loader(train_part, args.batch_size[0], True, args),
-            _loader(val_part, args.val_batch_size, False, args), do_search)
+    return _split_loaders(args, lambda *files_and_pipelines: D.DepthDataset(*files_and_pipelines, depth_scale),
+                          lambda a: _depth_train_pipeline(a, zoom_depth), _loader, "depth data")

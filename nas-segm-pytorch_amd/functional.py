@@ -3370,17 +3370,35 @@ def gather_rows(src, idx, out=None):
     return out
 
 
-def _packed_batch(what, src, desc, taps, lut, Ho, Wo, params=None):
-    """B of a packed batch of data/device.py (``params``: a depth batch's), or NassegError"""
+def _augment(who, src, desc, taps, lut, Ho, Wo, colour=None, depth=None):
+    """The body of the four functions below (``who``: the one that called, for its errors).  ``colour``: (colour, ctab)
+    of a batch with a ColourJitter; ``depth``: (params, depth_scale) of a depth batch.  The packed batch of
+    data/device.py is checked, the image and the target - uint8 labels, fp32 metres for a depth batch - are allocated
+    and the entry point of colour x depth is launched once, its arguments in include/nasseg.h's order."""
+    jitter, ctab = colour or (None, None)
+    params, depth_scale = depth or (None, None)
+    require_device(src, desc, taps, jitter, ctab, lut, params)
     B = desc.shape[0] if desc.dim() == 2 else 0
     if (src.dtype != torch.uint8 or desc.dtype != torch.int64 or taps.dtype != torch.int32
             or lut.dtype not in (torch.float32, torch.bfloat16) or src.dim() != 1 or B == 0
             or tuple(desc.shape) != (B, 8) or tuple(taps.shape) != (B, 9 * (Ho + Wo)) or tuple(lut.shape) != (3, 256)
             or not all(t.is_contiguous() for t in (src, desc, taps, lut))
-            or (params is not None and (params.dtype != torch.float32 or tuple(params.shape) != (B, 2)
-                                        or not params.is_contiguous()))):
-        raise NassegError("{}: bad packed batch".format(what))
-    return B
+            or (depth and (params.dtype != torch.float32 or tuple(params.shape) != (B, 2)
+                           or not params.is_contiguous()))):
+        raise NassegError("{}: bad packed batch".format(who))
+    if colour and (jitter.dtype != torch.int32 or tuple(jitter.shape) != (B, 12) or not jitter.is_contiguous()
+                   or ctab.dtype != torch.uint8 or tuple(ctab.shape) != (B, 3, 256) or not ctab.is_contiguous()
+                   or ctab.data_ptr() % 4 != 0):
+        raise NassegError("{}: colour must be contiguous int32 [B][12] and ctab contiguous uint8 [B][3][256]".format(
+            who))
+    image = torch.empty((B, 3, Ho, Wo), device=src.device, dtype=lut.dtype, memory_format=torch.channels_last)
+    target = torch.empty((B, Ho, Wo), device=src.device, dtype=torch.float32 if depth else torch.uint8)
+    name = "nasseg_augment" + ("_depth" if depth else "") + ("_colour" if colour else "")
+    lib.call(_k(name, lut), ptr(src), src.numel(), ptr(desc), ptr(taps),
+             *((ptr(jitter), ptr(ctab)) if colour else ()), ptr(lut),
+             *((ptr(params), float(depth_scale)) if depth else ()), ptr(image), ptr(target), B, Ho, Wo,
+             current_stream())
+    return image, target
 
 
 def augment(src, desc, taps, lut, Ho, Wo):
@@ -3388,13 +3406,7 @@ def augment(src, desc, taps, lut, Ho, Wo):
     ``src`` (the source windows), int64 ``desc`` [B][8], int32 ``taps`` [B][9 (Ho + Wo)] and the Normalise table
     ``lut`` [3][256] of the output dtype (fp32 or bf16) -> (image B x 3 x Ho x Wo channels_last, mask uint8
     B x Ho x Wo); one nasseg_augment launch (include/nasseg.h)."""
-    require_device(src, desc, taps, lut)
-    B = _packed_batch("augment", src, desc, taps, lut, Ho, Wo)
-    image = torch.empty((B, 3, Ho, Wo), device=src.device, dtype=lut.dtype, memory_format=torch.channels_last)
-    mask = torch.empty((B, Ho, Wo), device=src.device, dtype=torch.uint8)
-    lib.call(_k("nasseg_augment", lut), ptr(src), src.numel(), ptr(desc), ptr(taps), ptr(lut), ptr(image),
-             ptr(mask), B, Ho, Wo, current_stream())
-    return image, mask
+    return _augment("augment", src, desc, taps, lut, Ho, Wo)
 
 
 def augment_depth(src, desc, taps, lut, params, depth_scale, Ho, Wo):
@@ -3403,50 +3415,21 @@ def augment_depth(src, desc, taps, lut, params, depth_scale, Ho, Wo):
     B x 3 x Ho x Wo channels_last of the table's dtype - ``augment``'s, bit for bit -, target fp32 B x Ho x Wo =
     count * depth_scale / zoom in correctly rounded fp32, or the fill undivided); one nasseg_augment_depth launch
     (include/nasseg.h)."""
-    require_device(src, desc, taps, lut, params)
-    B = _packed_batch("augment_depth", src, desc, taps, lut, Ho, Wo, params)
-    image = torch.empty((B, 3, Ho, Wo), device=src.device, dtype=lut.dtype, memory_format=torch.channels_last)
-    target = torch.empty((B, Ho, Wo), device=src.device, dtype=torch.float32)
-    lib.call(_k("nasseg_augment_depth", lut), ptr(src), src.numel(), ptr(desc), ptr(taps), ptr(lut), ptr(params),
-             float(depth_scale), ptr(image), ptr(target), B, Ho, Wo, current_stream())
-    return image, target
-
-
-def _require_colour(what, B, colour, ctab):
-    """the two per-sample tables of the colour launches: int32 [B][12], uint8 [B][3][256], contiguous"""
-    if (colour.dtype != torch.int32 or tuple(colour.shape) != (B, 12) or not colour.is_contiguous()
-            or ctab.dtype != torch.uint8 or tuple(ctab.shape) != (B, 3, 256) or not ctab.is_contiguous()
-            or ctab.data_ptr() % 4 != 0):
-        raise NassegError("{}: colour must be contiguous int32 [B][12] and ctab contiguous uint8 [B][3][256]".format(
-            what))
+    return _augment("augment_depth", src, desc, taps, lut, Ho, Wo, depth=(params, depth_scale))
 
 
 def augment_colour(src, desc, taps, colour, ctab, lut, Ho, Wo):
     """``augment`` with a ColourJitter (data/datasets.py) between the resampling and ``lut``: int32 ``colour``
     [B][12] (the sample's 12-bit colour matrix row-major, 1 / 0: apply it, two zeros) and uint8 ``ctab`` [B][3][256]
     (its point table per channel); fill pixels skip both.  One nasseg_augment_colour launch (include/nasseg.h)."""
-    require_device(src, desc, taps, colour, ctab, lut)
-    B = _packed_batch("augment_colour", src, desc, taps, lut, Ho, Wo)
-    _require_colour("augment_colour", B, colour, ctab)
-    image = torch.empty((B, 3, Ho, Wo), device=src.device, dtype=lut.dtype, memory_format=torch.channels_last)
-    mask = torch.empty((B, Ho, Wo), device=src.device, dtype=torch.uint8)
-    lib.call(_k("nasseg_augment_colour", lut), ptr(src), src.numel(), ptr(desc), ptr(taps), ptr(colour), ptr(ctab),
-             ptr(lut), ptr(image), ptr(mask), B, Ho, Wo, current_stream())
-    return image, mask
+    return _augment("augment_colour", src, desc, taps, lut, Ho, Wo, colour=(colour, ctab))
 
 
 def augment_depth_colour(src, desc, taps, colour, ctab, lut, params, depth_scale, Ho, Wo):
     """``augment_depth`` with ``augment_colour``'s jitter of the image; the target is ``augment_depth``'s.  One
     nasseg_augment_depth_colour launch (include/nasseg.h)."""
-    require_device(src, desc, taps, colour, ctab, lut, params)
-    B = _packed_batch("augment_depth_colour", src, desc, taps, lut, Ho, Wo, params)
-    _require_colour("augment_depth_colour", B, colour, ctab)
-    image = torch.empty((B, 3, Ho, Wo), device=src.device, dtype=lut.dtype, memory_format=torch.channels_last)
-    target = torch.empty((B, Ho, Wo), device=src.device, dtype=torch.float32)
-    lib.call(_k("nasseg_augment_depth_colour", lut), ptr(src), src.numel(), ptr(desc), ptr(taps), ptr(colour),
-             ptr(ctab), ptr(lut), ptr(params), float(depth_scale), ptr(image), ptr(target), B, Ho, Wo,
-             current_stream())
-    return image, target
+    return _augment("augment_depth_colour", src, desc, taps, lut, Ho, Wo, colour=(colour, ctab),
+                    depth=(params, depth_scale))
 
 
 def argmax_confusion(logits, gt, n_classes, cm=None, out_size=None, return_preds=False):
@@ -3768,8 +3751,8 @@ def prepare_plan(device, B, H, W, dtype=torch.float32):
         (ty, my), (tx, mx) = axes
         taps = np.concatenate([ty.ravel(), tx.ravel(), my, mx]).astype(np.int32)
         desc = np.zeros((B, ddev.DESC_FIELDS), np.int64)
-        desc[:, 0] = np.arange(B, dtype=np.int64) * (H * W * 3)
-        desc[:, 2:6] = (H, W, 3 * W, W)
+        desc[:] = ddev.Desc(img_off=0, msk_off=0, h=H, w=W, img_ld=3 * W, msk_ld=W, img_fill=0, msk_fill=0)
+        desc[:, ddev.Desc._fields.index("img_off")] = np.arange(B, dtype=np.int64) * (H * W * 3)
         lut = torch.from_numpy(ddev.prepare_img_table()).float().to(dtype)
         return (torch.from_numpy(desc).to(device), torch.from_numpy(np.tile(taps, (B, 1))).to(device),
                 lut.to(device))

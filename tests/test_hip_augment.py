@@ -213,3 +213,71 @@ def test_one_epoch_and_validation_from_either_loader(tmp_path, monkeypatch):
     assert len(h_losses) == len(h_trn) > 0 and h_losses == d_losses
     assert all(torch.equal(h_sd[k], d_sd[k]) for k in h_sd)
     assert h_reward == d_reward
+
+
+@pytest.mark.parametrize("kind", ["label", "depth"])
+def test_a_window_outside_src_is_read_as_fill(kind):
+    """Whatever the descriptor holds, no load leaves ``src``: a window that does not lie inside it is read as fill.
+    Three 17 x 19 samples (323 pixels: a full block of 256 threads and a ragged one), identity taps, every pixel
+    live; one field of sample 1's descriptor - its windows lie in the middle of ``src`` - is changed at a time.  The
+    half of sample 1 whose window it is becomes that half's fill, exactly (lut[c][fill byte c]; the mask fill;
+    params[1][1] NOT divided by the zoom); everything else is the unmodified launch's, bit for bit.  ``src`` is a
+    slice of a larger buffer with 4096 bytes on either side that hold a value no fill has, so a wrong read would be
+    a wrong value and never an access out of bounds."""
+    from nas_segm_amd import functional as F
+
+    D, dev = mods()
+    Ho, Wo, guard, elem = 17, 19, 4096, 1 if kind == "label" else 2
+    img_fill, msk_fill, depth_fill, guard_byte = (11, 22, 33), 200, 7.5, 238
+    pipe = D.Compose([D.Normalise(1.0 / 255, MEAN, STD), D.ToTensor()])
+    rng = np.random.RandomState(0)
+    images = [(rng.rand(Ho, Wo, 3) * 255).astype(np.uint8) for _ in range(3)]
+    if kind == "label":  # labels below 21, counts of at most 4.5 m after the zoom: no live value is a fill
+        batch = dev.collate([dev.plan_sample(pipe, img, (rng.rand(Ho, Wo) * 21).astype(np.uint8)) for img in images])
+    else:
+        batch = dev.collate_depth([dev.plan_depth_sample(pipe, img, rng.randint(1, 9000, (Ho, Wo)).astype(np.uint16))
+                                   for img in images])
+        params = torch.tensor([[2.0, depth_fill]] * 3, dtype=torch.float32, device=DEV)
+    assert tuple(batch["size"]) == (Ho, Wo) and bool((batch["taps"] >= 0).all())
+    field = {name: i for i, name in enumerate(dev.Desc._fields)}
+    desc = batch["desc"].clone()
+    desc[:, field["img_fill"]] = img_fill[0] | img_fill[1] << 8 | img_fill[2] << 16
+    desc[:, field["msk_fill"]] = msk_fill
+    n = batch["src"].numel()
+    img_bytes, msk_bytes = 3 * Ho * Wo, elem * Ho * Wo
+    assert n == 3 * (img_bytes + msk_bytes)
+    assert desc[1].tolist()[:6] == [img_bytes + msk_bytes, 2 * img_bytes + msk_bytes, Ho, Wo, 3 * Wo, elem * Wo]
+    big = torch.full((guard + n + guard,), guard_byte, dtype=torch.uint8, device=DEV)
+    src = big[guard: guard + n]
+    src.copy_(batch["src"])
+    taps = batch["taps"].to(DEV)
+    IMAGE, TARGET = 0, 1
+    changes = [("msk_off", -1, {TARGET}), ("msk_off", n - msk_bytes + elem, {TARGET}),
+               ("msk_ld", elem * Wo - 1, {TARGET}),
+               ("img_off", -1, {IMAGE}), ("img_off", n - img_bytes + 3, {IMAGE}), ("img_ld", 3 * Wo - 1, {IMAGE}),
+               ("h", 0, {IMAGE, TARGET})]
+
+    for dtype in DTYPES:
+        lut = batch["lut"].to(dtype).to(DEV)
+
+        def launch(d):
+            if kind == "label":
+                return F.augment(src, d.to(DEV), taps, lut, Ho, Wo)
+            return F.augment_depth(src, d.to(DEV), taps, lut, params, 1e-3, Ho, Wo)
+
+        fills = (torch.stack([lut[c, v] for c, v in enumerate(img_fill)]).view(3, 1, 1).expand(3, Ho, Wo),
+                 torch.full((Ho, Wo), msk_fill, dtype=torch.uint8) if kind == "label"
+                 else torch.full((Ho, Wo), depth_fill, dtype=torch.float32))
+        base = launch(desc)
+        for half in (IMAGE, TARGET):  # (the unmodified launch holds no fill pixel)
+            assert not bool((base[half][1].cpu() == fills[half].cpu()).all(dim=0).any() if half == IMAGE
+                            else (base[half][1].cpu() == fills[half]).any())
+        for name, value, filled in changes:
+            d = desc.clone()
+            d[1, field[name]] = value
+            got = launch(d)
+            for half in (IMAGE, TARGET):
+                for b in range(3):
+                    want = fills[half] if b == 1 and half in filled else base[half][b]
+                    assert equal(got[half][b], want), (kind, dtype, name, value, half, b)
+    assert bool((big[:guard] == guard_byte).all()) and bool((big[guard + n:] == guard_byte).all())
