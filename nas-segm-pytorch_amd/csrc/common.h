@@ -175,6 +175,8 @@ __device__ __forceinline__ float4 mul4(float4 a, float4 b) {
   return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
 }
 
+#include "lane_math.h"  // the per-lane algebra of the fused kernels, in terms of the helpers above
+
 // ---------------------------------------------------------------------------
 // Second stage of every deterministic two-stage reduction: sum partial[b][e]
 // over b = 0..nblk-1 for NASSEG_RP_ELEMS consecutive elements per workgroup.

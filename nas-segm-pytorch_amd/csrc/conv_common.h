@@ -1,5 +1,5 @@
 // Shared pieces of the dense-convolution kernels (conv_fwd.hip, conv_wgrad.hip):
-// implicit-GEMM geometry and the fp32 MFMA wrapper.
+// implicit-GEMM geometry (the fp32 MFMA wrapper mfma16 and keep_if are lane_math.h's).
 //
 // Code-generation rules learned on gfx950 / hipcc 7.2 and followed throughout:
 //  * never put a global load under a data-dependent branch: the compiler closes every
@@ -9,10 +9,6 @@
 //    parameters or hoist them out of the loop.
 #pragma once
 #include "common.h"
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 struct ConvGeom {
   int B, Hs, Ws;  // source (tensor being read) dims
@@ -43,16 +39,4 @@ __device__ __forceinline__ int src_pixel(const ConvGeom& g, int b, int oy, int o
     if (iy >= g.Hs || ix >= g.Ws) return -1;
   }
   return (b * g.Hs + iy) * g.Ws + ix;
-}
-
-__device__ __forceinline__ float keep_if(float v, bool ok) {
-  return __uint_as_float(__float_as_uint(v) & (0u - (unsigned)ok));
-}
-__device__ __forceinline__ float4 keep_if(float4 v, bool ok) {
-  const unsigned m = 0u - (unsigned)ok;
-  v.x = __uint_as_float(__float_as_uint(v.x) & m);
-  v.y = __uint_as_float(__float_as_uint(v.y) & m);
-  v.z = __uint_as_float(__float_as_uint(v.z) & m);
-  v.w = __uint_as_float(__float_as_uint(v.w) & m);
-  return v;
 }

@@ -225,11 +225,8 @@ __global__ __launch_bounds__(256) void conv_pw_bwd_kernel(PwArgs a) {
                            g2.z * act_mask(y.z, a.bn_act), g2.w * act_mask(y.w, a.bn_act));
         }
         float4 dz = fma4(g2, va, fma4(z2, vb, vd));
-#ifdef NASSEG_BF16
         // (what the two-kernel form stores and reads back)
-        dz = make_float4(bf16_to_f32(f32_to_bf16(dz.x)), bf16_to_f32(f32_to_bf16(dz.y)),
-                         bf16_to_f32(f32_to_bf16(dz.z)), bf16_to_f32(f32_to_bf16(dz.w)));
-#endif
+        dz = as_stored4(dz);
         *reinterpret_cast<float4*>(&dzt[px * LSN + n]) = keep_if(dz, ok);
       }
     }
@@ -308,11 +305,8 @@ __global__ __launch_bounds__(256) void conv_pw_bwd_kernel(PwArgs a) {
           float* slot = &dzt[(wave * 16 + j) * LSN + n];
           float4 g2 = *reinterpret_cast<const float4*>(slot);
           float4 z2 = make_float4(zc[q][0], zc[q][1], zc[q][2], zc[q][3]);
-#ifdef NASSEG_BF16
           // (the value the forward stored and every other consumer of z reads)
-          z2 = make_float4(bf16_to_f32(f32_to_bf16(z2.x)), bf16_to_f32(f32_to_bf16(z2.y)), bf16_to_f32(f32_to_bf16(z2.z)),
-                           bf16_to_f32(f32_to_bf16(z2.w)));
-#endif
+          z2 = as_stored4(z2);
           const float4 va = ld4(ca + n), vb = ld4(cb + n), vd = ld4(cd + n);
           if (a.bn_act) {
             const float4 y = fma4(z2, va, ld4(cs + n));
@@ -320,10 +314,7 @@ __global__ __launch_bounds__(256) void conv_pw_bwd_kernel(PwArgs a) {
                              g2.z * act_mask(y.z, a.bn_act), g2.w * act_mask(y.w, a.bn_act));
           }
           float4 dz = fma4(g2, va, fma4(z2, vb, vd));
-#ifdef NASSEG_BF16
-          dz = make_float4(bf16_to_f32(f32_to_bf16(dz.x)), bf16_to_f32(f32_to_bf16(dz.y)),
-                           bf16_to_f32(f32_to_bf16(dz.z)), bf16_to_f32(f32_to_bf16(dz.w)));
-#endif
+          dz = as_stored4(dz);
           *reinterpret_cast<float4*>(slot) = keep_if(dz, pok && n < N);
         }
         __builtin_amdgcn_sched_barrier(0);  // (one group at a time: keeps the next group's operands out of this one's registers)
@@ -379,13 +370,9 @@ __global__ __launch_bounds__(256) void conv_pw_bwd_kernel(PwArgs a) {
           //  value when the BatchNorm's weight is zero, and a global re-load here would queue up behind the
           //  next tile's loads that were just issued)
           const float4 zr = *reinterpret_cast<const float4*>(&xraw[(wave * 16 + j) * LSK + k]);
-#ifdef NASSEG_BF16
-          o = make_float4(bf16_to_f32(f32_to_bf16(o.x)), bf16_to_f32(f32_to_bf16(o.y)), bf16_to_f32(f32_to_bf16(o.z)),
-                          bf16_to_f32(f32_to_bf16(o.w)));  // (what a separate pass would read back)
-#endif
+          o = as_stored4(o);  // (what a separate pass would read back)
           const float4 gm = keep_if(o, ok);
-          const float4 xh = make_float4((zr.x - smu[kt].x) * sis[kt].x, (zr.y - smu[kt].y) * sis[kt].y,
-                                        (zr.z - smu[kt].z) * sis[kt].z, (zr.w - smu[kt].w) * sis[kt].w);
+          const float4 xh = xhat4(zr, smu[kt], sis[kt]);
           sx[kt] = add4(sx[kt], gm);
           sq[kt] = fma4(gm, xh, sq[kt]);
         }
@@ -561,10 +548,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_bwd_wide_kernel(PwArgs a) {
                          (y.z > m_lo && y.z < m_hi) ? gv.z : 0.f, (y.w > m_lo && y.w < m_hi) ? gv.w : 0.f);
       }
       float4 dz = fma4(gv, va, fma4(zv, vb, vd));
-#ifdef NASSEG_BF16
-      dz = make_float4(bf16_to_f32(f32_to_bf16(dz.x)), bf16_to_f32(f32_to_bf16(dz.y)),
-                       bf16_to_f32(f32_to_bf16(dz.z)), bf16_to_f32(f32_to_bf16(dz.w)));
-#endif
+      dz = as_stored4(dz);
       *reinterpret_cast<float4*>(&dzt[px * LS + icol]) = keep_if(dz, ok);
     }
   };

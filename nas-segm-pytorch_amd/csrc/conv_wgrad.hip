@@ -197,11 +197,7 @@ __device__ __forceinline__ void wgrad_tile(const WgArgs& a, const int bx, const 
         for (int c = 0; c < VN; ++c) {
           float gm = dv[u][c];
           if (a.bn_act) gm *= act_mask(fmaf(zv[c], ca[c], cs[c]), a.bn_act);
-          float v = fmaf(gm, ca[c], fmaf(zv[c], cb[c], cd[c]));
-#ifdef NASSEG_BF16
-          v = bf16_to_f32(f32_to_bf16(v));  // (the value the backward-data kernel will read)
-#endif
-          dv[u][c] = v;
+          dv[u][c] = as_stored(fmaf(gm, ca[c], fmaf(zv[c], cb[c], cd[c])));  // (the value the backward-data kernel will read)
         }
         if (wr && pok) store_vec<VN, ALN>(a.dz + (int64_t)pc * a.lddz, n0, a.N, dv[u]);
       }

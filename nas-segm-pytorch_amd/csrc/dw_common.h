@@ -8,17 +8,6 @@
 
 namespace {
 
-// keep v where ok, +0.0 elsewhere, without a select the compiler could turn back into
-// a branch around the producing load (mask = all ones / all zeros)
-__device__ __forceinline__ float4 keep_if(float4 v, bool ok) {
-  const unsigned m = 0u - (unsigned)ok;
-  v.x = __uint_as_float(__float_as_uint(v.x) & m);
-  v.y = __uint_as_float(__float_as_uint(v.y) & m);
-  v.z = __uint_as_float(__float_as_uint(v.z) & m);
-  v.w = __uint_as_float(__float_as_uint(v.w) & m);
-  return v;
-}
-
 // Pin a value at this program point: LLVM otherwise sinks the whole FMA chain of an
 // accumulator into the (conditional) block that finally stores it, which keeps every
 // loaded operand alive until the end of the kernel.

@@ -98,8 +98,7 @@ __device__ __forceinline__ void bnbwd_accumulate(float4& g, float4 z, const BnBw
   g.z *= act_mask(yv.z, act);
   g.w *= act_mask(yv.w, act);
   const float4 v = keep_if(g, ok);
-  const float4 xh = make_float4((z.x - l.mu.x) * l.is.x, (z.y - l.mu.y) * l.is.y,
-                                (z.z - l.mu.z) * l.is.z, (z.w - l.mu.w) * l.is.w);
+  const float4 xh = xhat4(z, l.mu, l.is);
   ssum[0] = add4(ssum[0], v);
   ssum[1] = fma4(v, xh, ssum[1]);
 }
@@ -515,10 +514,7 @@ __device__ __forceinline__ void dw_wgrad_tile(const DwWgArgs& q, const int bx, c
                            gv.z * act_mask(y.z, q.bn_act), gv.w * act_mask(y.w, q.bn_act));
         }
         gv = fma4(gv, ca, fma4(zv, cb, cd));
-#ifdef NASSEG_BF16
-        gv = make_float4(bf16_to_f32(f32_to_bf16(gv.x)), bf16_to_f32(f32_to_bf16(gv.y)),
-                         bf16_to_f32(f32_to_bf16(gv.z)), bf16_to_f32(f32_to_bf16(gv.w)));
-#endif
+        gv = as_stored4(gv);
         if (pok) sta4(q.dz + off, gv);  // (every dy element is loaded by exactly one lane)
       }
       d[j][i] = keep_if(gv, pok);
@@ -742,10 +738,7 @@ __global__ __launch_bounds__(256, 2) void dw_wgrad_lds_kernel(DwWlArgs w) {
                               g.z * act_mask(y.z, q.bn_act), g.w * act_mask(y.w, q.bn_act));
             }
             g = fma4(g, ca, fma4(zv[i], cb, cd));
-#ifdef NASSEG_BF16
-            g = make_float4(bf16_to_f32(f32_to_bf16(g.x)), bf16_to_f32(f32_to_bf16(g.y)),
-                            bf16_to_f32(f32_to_bf16(g.z)), bf16_to_f32(f32_to_bf16(g.w)));
-#endif
+            g = as_stored4(g);
             if (go[i]) sta4(q.dz + ib + goff[i], g);
           }
           if (p < npx_d) ds[p * PS + sc_] = keep_if(g, go[i]);
@@ -888,34 +881,9 @@ struct DwBwdArgs {
   int flip;  // wt is the 180-degree rotated packing (what a stride-1 chain keeps for backward-data)
 };
 
-struct DzConst {
-  float4 ca, cb, cd, cs;
-};
-__device__ __forceinline__ DzConst dz_const(const DwBwdArgs& q, int c4) {
-  DzConst k;
-  const int C = q.C4 * 4;
-  k.ca = lda4(q.bn_scale + c4 * 4);
-  k.cs = q.bn_act ? lda4(q.bn_shift + c4 * 4) : f4zero();
-  k.cb = f4zero();
-  k.cd = f4zero();
-  if (q.bn_train) {
-    const float4 is = lda4(q.bn_invstd + c4 * 4), mu = lda4(q.bn_mean + c4 * 4);
-    const float4 s0 = lda4(q.bn_sums + c4 * 4), s1 = lda4(q.bn_sums + C + c4 * 4);
-    const float m = q.invM;
-    k.cb = make_float4(-k.ca.x * is.x * (s1.x * m), -k.ca.y * is.y * (s1.y * m), -k.ca.z * is.z * (s1.z * m),
-                       -k.ca.w * is.w * (s1.w * m));
-    k.cd = make_float4(k.ca.x * (mu.x * is.x * (s1.x * m) - s0.x * m), k.ca.y * (mu.y * is.y * (s1.y * m) - s0.y * m),
-                       k.ca.z * (mu.z * is.z * (s1.z * m) - s0.z * m), k.ca.w * (mu.w * is.w * (s1.w * m) - s0.w * m));
-  }
-  return k;
-}
 // dz at output pixel (oy, ox) of image b (zero outside the map) in two halves, so that the loads of
 // the next row can be issued before the arithmetic of the current one: dz_load (unconditional loads
 // from a clamped address) and dz_make
-struct DzRaw {
-  float4 g, z;
-  bool ok;
-};
 __device__ __forceinline__ DzRaw dz_load(const DwBwdArgs& q, int b, int oy, int ox, int c4) {
   DzRaw r;
   r.ok = oy >= 0 && oy < q.Ho && ox >= 0 && ox < q.Wo;
@@ -925,7 +893,7 @@ __device__ __forceinline__ DzRaw dz_load(const DwBwdArgs& q, int b, int oy, int 
   r.z = lda4(q.z + off);
   return r;
 }
-__device__ __forceinline__ float4 dz_make(const DwBwdArgs& q, const DzConst& k, const DzRaw& r) {
+__device__ __forceinline__ float4 dz_make(const DwBwdArgs& q, const BnCoef& k, const DzRaw& r) {
   float4 gv = r.g;
   if (q.bn_act) {
     const float4 y = fma4(r.z, k.ca, k.cs);
@@ -933,13 +901,10 @@ __device__ __forceinline__ float4 dz_make(const DwBwdArgs& q, const DzConst& k, 
                      gv.w * act_mask(y.w, q.bn_act));
   }
   float4 v = fma4(gv, k.ca, fma4(r.z, k.cb, k.cd));
-#ifdef NASSEG_BF16
-  v = make_float4(bf16_to_f32(f32_to_bf16(v.x)), bf16_to_f32(f32_to_bf16(v.y)), bf16_to_f32(f32_to_bf16(v.z)),
-                  bf16_to_f32(f32_to_bf16(v.w)));  // (what the two-kernel form stores and reads back)
-#endif
+  v = as_stored4(v);  // (what the two-kernel form stores and reads back)
   return keep_if(v, r.ok);
 }
-__device__ __forceinline__ float4 dz_at(const DwBwdArgs& q, const DzConst& k, int b, int oy, int ox, int c4) {
+__device__ __forceinline__ float4 dz_at(const DwBwdArgs& q, const BnCoef& k, int b, int oy, int ox, int c4) {
   return dz_make(q, k, dz_load(q, b, oy, ox, c4));
 }
 
@@ -965,7 +930,8 @@ __global__ __launch_bounds__(256, NASSEG_DWBWD_MINB) void dw3x3_bwd_bn_kernel(Dw
   const bool live = idx < Wq * C4;
   const int xq = live ? idx / C4 : 0;
   const int c4 = live ? idx - xq * C4 : 0;
-  const DzConst kc = dz_const(q, c4);
+  const BnCoef kc = bn_coef(q.bn_scale, q.bn_shift, q.bn_mean, q.bn_invstd, q.bn_sums, C, q.invM, q.bn_train, q.bn_act,
+                              c4);
   BnBwd bn = {q.xz, q.in_scale, q.in_shift, q.in_mean, q.in_invstd, q.in_act};
   const BnBwdLane bl = bnbwd_lane(bn, c4);
   Prologue pro;  // (scale / shift shared with bl)

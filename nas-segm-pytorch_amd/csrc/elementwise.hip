@@ -77,10 +77,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
       const float4 is = lda4(invstd + c4 * 4);
       const float4 s0 = lda4(sums + c4 * 4);
       const float4 s1 = lda4(sums + C + c4 * 4);
-      g.x = g.x - s0.x * invM - (v.x - mu.x) * is.x * s1.x * invM;
-      g.y = g.y - s0.y * invM - (v.y - mu.y) * is.y * s1.y * invM;
-      g.z = g.z - s0.z * invM - (v.z - mu.z) * is.z * s1.z * invM;
-      g.w = g.w - s0.w * invM - (v.w - mu.w) * is.w * s1.w * invM;
+      g = bn_dx4(g, v, mu, is, s0, s1, invM);
     }
     sta4(dx + i * 4, mul4(g, s));
   }
@@ -148,10 +145,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rows_kernel(
       const float4 is = lda4(invstd + c4 * 4);
       const float4 s0 = *reinterpret_cast<const float4*>(fin + c4 * 4);
       const float4 s1 = *reinterpret_cast<const float4*>(fin + C + c4 * 4);
-      g.x = g.x - s0.x * invM - (v.x - mu.x) * is.x * s1.x * invM;
-      g.y = g.y - s0.y * invM - (v.y - mu.y) * is.y * s1.y * invM;
-      g.z = g.z - s0.z * invM - (v.z - mu.z) * is.z * s1.z * invM;
-      g.w = g.w - s0.w * invM - (v.w - mu.w) * is.w * s1.w * invM;
+      g = bn_dx4(g, v, mu, is, s0, s1, invM);
     }
     sta4(dx + i * 4, mul4(g, s));
   }

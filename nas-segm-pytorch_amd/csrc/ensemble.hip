@@ -280,7 +280,7 @@ __global__ __launch_bounds__(256) void view_image_kernel(const act_t* __restrict
     const float v01 = lda1(xb + ((int64_t)ly.i0 * Wi + lx.i1) * C);
     const float v10 = lda1(xb + ((int64_t)ly.i1 * Wi + lx.i0) * C);
     const float v11 = lda1(xb + ((int64_t)ly.i1 * Wi + lx.i1) * C);
-    sta1(y + i, ly.l0 * (lx.l0 * v00 + lx.l1 * v01) + ly.l1 * (lx.l0 * v10 + lx.l1 * v11));
+    sta1(y + i, bilerp(v00, v01, v10, v11, ly, lx));
   }
 }
 

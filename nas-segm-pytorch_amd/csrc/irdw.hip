@@ -41,10 +41,6 @@ namespace {
 constexpr int kIrMaxTiles = 12;  // C <= 192
 constexpr int kIrMaxWaves = 4;   // waves (channel tiles) per workgroup
 
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {  // (conv_common.h's wrapper)
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 template <int CTRL>
 __device__ __forceinline__ float dpp_shift0(float v) {  // (bound_ctrl: a lane without a source reads 0 - no "old" move)
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
@@ -54,14 +50,6 @@ __device__ __forceinline__ float4 from_left(float4 v) {  // lane j <- lane j - 1
 }
 __device__ __forceinline__ float4 from_right(float4 v) {  // lane j <- lane j + 1 (0 at j = 15)
   return make_float4(dpp_shift0<0x101>(v.x), dpp_shift0<0x101>(v.y), dpp_shift0<0x101>(v.z), dpp_shift0<0x101>(v.w));
-}
-__device__ __forceinline__ float4 round_like_storage(float4 v) {
-#ifdef NASSEG_BF16
-  // (the value the expansion would have stored and every consumer of z1 would have read)
-  v = make_float4(bf16_to_f32(f32_to_bf16(v.x)), bf16_to_f32(f32_to_bf16(v.y)), bf16_to_f32(f32_to_bf16(v.z)),
-                  bf16_to_f32(f32_to_bf16(v.w)));
-#endif
-  return v;
 }
 
 struct IrCommon {
@@ -135,7 +123,8 @@ __device__ __forceinline__ float4 ir_mma(const IrLane<KT, PRO>& l, const IrRawX<
     acc = mfma16(l.aw[kb][2], v.z, acc);
     acc = mfma16(l.aw[kb][3], v.w, acc);
   }
-  return round_like_storage(make_float4(acc[0], acc[1], acc[2], acc[3]));
+  // (the value the expansion would have stored and every consumer of z1 would have read)
+  return as_stored4(make_float4(acc[0], acc[1], acc[2], acc[3]));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -303,34 +292,9 @@ struct IrBwdArgs {
   float invM;
 };
 
-struct IrDz {
-  float4 ca, cb, cd, cs;
-};
-__device__ __forceinline__ IrDz ir_dz_const(const IrBwdArgs& a, int c4) {
-  // dz = ca*g' + cb*z + cd  ==  scale*(g' - sum(g')/M - xhat*sum(g'*xhat)/M); g' = g * act2'(scale*z + shift)
-  IrDz k;
-  const int C = a.c.C;
-  k.ca = ld4(a.sc2 + c4 * 4);
-  k.cs = a.act2 ? ld4(a.sh2 + c4 * 4) : f4zero();
-  k.cb = f4zero();
-  k.cd = f4zero();
-  if (a.train2) {
-    const float4 is = ld4(a.is2 + c4 * 4), mu = ld4(a.mu2 + c4 * 4);
-    const float4 s0 = ld4(a.sums2 + c4 * 4), s1 = ld4(a.sums2 + C + c4 * 4);
-    const float m = a.invM;
-    k.cb = make_float4(-k.ca.x * is.x * (s1.x * m), -k.ca.y * is.y * (s1.y * m), -k.ca.z * is.z * (s1.z * m),
-                       -k.ca.w * is.w * (s1.w * m));
-    k.cd = make_float4(k.ca.x * (mu.x * is.x * (s1.x * m) - s0.x * m), k.ca.y * (mu.y * is.y * (s1.y * m) - s0.y * m),
-                       k.ca.z * (mu.z * is.z * (s1.z * m) - s0.z * m), k.ca.w * (mu.w * is.w * (s1.w * m) - s0.w * m));
-  }
-  return k;
-}
-struct IrRaw {
-  float4 g, z;
-  bool ok;
-};
-__device__ __forceinline__ IrRaw ir_dz_load(const IrBwdArgs& a, int b, int oy, int ox, int c4) {
-  IrRaw r;
+// dz2 at an output pixel (zero outside the map) in two halves: the loads, from a clamped address, and the arithmetic
+__device__ __forceinline__ DzRaw ir_dz_load(const IrBwdArgs& a, int b, int oy, int ox, int c4) {
+  DzRaw r;
   const int Ho = a.c.Ho, Wo = a.c.Wo;
   r.ok = oy >= 0 && oy < Ho && ox >= 0 && ox < Wo;
   const int oyc = oy < 0 ? 0 : (oy >= Ho ? Ho - 1 : oy), oxc = ox < 0 ? 0 : (ox >= Wo ? Wo - 1 : ox);
@@ -340,11 +304,8 @@ __device__ __forceinline__ IrRaw ir_dz_load(const IrBwdArgs& a, int b, int oy, i
   return r;
 }
 // (the activations as loop-invariant scalars: a run-time `act` inside the row loop is a branch per component)
-__device__ __forceinline__ float4 ir_dz_make(const ActSel& act2, const IrDz& k, const IrRaw& r) {
-  const float4 y = fma4(r.z, k.ca, k.cs);
-  const float4 gv = make_float4(r.g.x * act_mask(y.x, act2), r.g.y * act_mask(y.y, act2), r.g.z * act_mask(y.z, act2),
-                                r.g.w * act_mask(y.w, act2));
-  return keep_if(round_like_storage(fma4(gv, k.ca, fma4(r.z, k.cb, k.cd))), r.ok);
+__device__ __forceinline__ float4 ir_dz_make(const ActSel& act2, const BnCoef& k, const DzRaw& r) {
+  return keep_if(bn_coef_apply(r.g, r.z, k, act2), r.ok);
 }
 
 template <int STRIDE, int KT, bool PRO>
@@ -358,7 +319,7 @@ __global__ __launch_bounds__(64 * kIrMaxWaves, NASSEG_IR_BWD_MINB) void irdw_bwd
   const float4 sc1 = ld4(q.sc1 + 4 * c4), sh1 = ld4(q.sh1 + 4 * c4);
   const float4 mu1 = ld4(a.mu1 + 4 * c4), is1 = ld4(a.is1 + 4 * c4);
   const float lo1 = q.act1 ? 0.f : -INFINITY, hi1 = q.act1 == NASSEG_ACT_RELU6 ? 6.f : INFINITY;
-  const IrDz kc = ir_dz_const(a, c4);
+  const BnCoef kc = bn_coef(a.sc2, a.sh2, a.mu2, a.is2, a.sums2, C, a.invM, a.train2, a.act2, c4);
   const ActSel sel1 = act_sel(q.act1), sel2 = act_sel(a.act2);
   float4 lw[9];
 #pragma unroll
@@ -370,13 +331,9 @@ __global__ __launch_bounds__(64 * kIrMaxWaves, NASSEG_IR_BWD_MINB) void irdw_bwd
   // ge of one input pixel: masked with act1'(sc1 z1 + sh1); its sums against xhat1
   auto finish = [&](float4& o, float4 z1, bool ok) {
     const float4 y = fma4(z1, sc1, sh1);
-    o.x *= act_mask(y.x, sel1);
-    o.y *= act_mask(y.y, sel1);
-    o.z *= act_mask(y.z, sel1);
-    o.w *= act_mask(y.w, sel1);
+    o = mask4(o, y, sel1);
     const float4 v = keep_if(o, ok);
-    const float4 xh = make_float4((z1.x - mu1.x) * is1.x, (z1.y - mu1.y) * is1.y, (z1.z - mu1.z) * is1.z,
-                                  (z1.w - mu1.w) * is1.w);
+    const float4 xh = xhat4(z1, mu1, is1);
     ssum[0] = add4(ssum[0], v);
     ssum[1] = fma4(v, xh, ssum[1]);
   };
@@ -407,8 +364,8 @@ __global__ __launch_bounds__(64 * kIrMaxWaves, NASSEG_IR_BWD_MINB) void irdw_bwd
       const act_t* xcol = q.x + ((size_t)b * H * W + xc) * K;
       // window rows: dz[iy - 1], dz[iy], dz[iy + 1] with their left / right neighbours
       float4 dl[3], dm[3], dr[3];
-      auto make_dz = [&](const IrRaw& raw, float4& L, float4& M, float4& R) {
-        IrRaw r = raw;
+      auto make_dz = [&](const DzRaw& raw, float4& L, float4& M, float4& R) {
+        DzRaw r = raw;
         r.ok = r.ok && colok;
         M = ir_dz_make(sel2, kc, r);
         L = from_left(M);
@@ -416,11 +373,11 @@ __global__ __launch_bounds__(64 * kIrMaxWaves, NASSEG_IR_BWD_MINB) void irdw_bwd
       };
       make_dz(ir_dz_load(a, b, r0 - 1, xc, c4), dl[1], dm[1], dr[1]);
       make_dz(ir_dz_load(a, b, r0, xc, c4), dl[2], dm[2], dr[2]);
-      IrRaw nxt = ir_dz_load(a, b, r0 + 1, xc, c4), nxt2 = ir_dz_load(a, b, r0 + 2, xc, c4);
+      DzRaw nxt = ir_dz_load(a, b, r0 + 1, xc, c4), nxt2 = ir_dz_load(a, b, r0 + 2, xc, c4);
       IrRawX<KT, PRO> xnxt = ir_load<KT, PRO>(ln, xcol + (size_t)r0 * W * K);
       IrRawX<KT, PRO> xnxt2 = ir_load<KT, PRO>(ln, xcol + (size_t)(r0 + 1 < H ? r0 + 1 : H - 1) * W * K);
       for (int iy = r0; iy < r1; ++iy) {
-        const IrRaw cur = nxt;
+        const DzRaw cur = nxt;
         const IrRawX<KT, PRO> xcur = xnxt;
         nxt = nxt2;
         xnxt = xnxt2;
@@ -457,7 +414,7 @@ __global__ __launch_bounds__(64 * kIrMaxWaves, NASSEG_IR_BWD_MINB) void irdw_bwd
       const bool live = j <= 14 && xq < Wq;
       const int xqc = xq < Wq ? xq : Wq - 1;
       float4 d[2][2];  // [ry][rx]
-      auto make_dz = [&](const IrRaw& raw, float4& M, float4& R) {
+      auto make_dz = [&](const DzRaw& raw, float4& M, float4& R) {
         M = ir_dz_make(sel2, kc, raw);
         R = from_right(M);
       };
@@ -472,11 +429,11 @@ __global__ __launch_bounds__(64 * kIrMaxWaves, NASSEG_IR_BWD_MINB) void irdw_bwd
       };
       // (a column beyond the map's last output column reads as 0: ir_dz_load checks the UNclamped column)
       make_dz(ir_dz_load(a, b, r0, xq, c4), d[1][0], d[1][1]);
-      IrRaw nxt = ir_dz_load(a, b, r0 + 1, xq, c4);
+      DzRaw nxt = ir_dz_load(a, b, r0 + 1, xq, c4);
       IrRawX<KT, PRO> xnxt[2][2];
       fetch_quad(r0, xnxt);
       for (int aq = r0; aq < r1; ++aq) {
-        const IrRaw cur = nxt;
+        const DzRaw cur = nxt;
         IrRawX<KT, PRO> xcur[2][2];
 #pragma unroll
         for (int py = 0; py < 2; ++py)

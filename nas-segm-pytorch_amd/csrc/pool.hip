@@ -290,14 +290,10 @@ __global__ __launch_bounds__(256) void maxpool3_bn_bwd_kernel(const act_t* __res
       acc.w += (ok[t] && w[t].w == t) ? d[t].w : 0.f;
     }
     if (live) sta4(g + off, acc);
-#ifdef NASSEG_BF16
-    acc = make_float4(bf16_to_f32(f32_to_bf16(acc.x)), bf16_to_f32(f32_to_bf16(acc.y)),
-                      bf16_to_f32(f32_to_bf16(acc.z)), bf16_to_f32(f32_to_bf16(acc.w)));  // (what a reduction pass would read)
-#endif
+    acc = as_stored4(acc);  // (what a reduction pass would read)
     const float4 gm = keep_if(acc, live);
     ssum[0] = add4(ssum[0], gm);
-    ssum[1] = fma4(gm, make_float4((zv.x - mu.x) * is.x, (zv.y - mu.y) * is.y, (zv.z - mu.z) * is.z,
-                                   (zv.w - mu.w) * is.w), ssum[1]);
+    ssum[1] = fma4(gm, xhat4(zv, mu, is), ssum[1]);
   }
   const int blk = blockIdx.y * gridDim.x + blockIdx.x;
   block_reduce_groups<2, 2>(ssum, sred, stats + (size_t)blk * 2 * C, base, C4);
@@ -448,14 +444,10 @@ __global__ __launch_bounds__(256) void maxpool3_bn_bwd_strip_kernel(const act_t*
       }
       const bool rowok = live && iy0 + j < H;
       if (rowok) sta4(g + (((int64_t)b * H + iy0 + j) * W + ix) * C + c4 * 4, acc);
-#ifdef NASSEG_BF16
-      acc = make_float4(bf16_to_f32(f32_to_bf16(acc.x)), bf16_to_f32(f32_to_bf16(acc.y)),
-                        bf16_to_f32(f32_to_bf16(acc.z)), bf16_to_f32(f32_to_bf16(acc.w)));  // (what a reduction pass would read)
-#endif
+      acc = as_stored4(acc);  // (what a reduction pass would read)
       const float4 gm = keep_if(acc, rowok);
       ssum[0] = add4(ssum[0], gm);
-      ssum[1] = fma4(gm, make_float4((zv[j].x - mu.x) * is.x, (zv[j].y - mu.y) * is.y, (zv[j].z - mu.z) * is.z,
-                                     (zv[j].w - mu.w) * is.w), ssum[1]);
+      ssum[1] = fma4(gm, xhat4(zv[j], mu, is), ssum[1]);
     }
   }
   const int blk = blockIdx.y * gridDim.x + blockIdx.x;

@@ -53,10 +53,7 @@ struct Vt<4> {
     return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
   }
   static __device__ __forceinline__ T fma(T a, T b, T c) { return fma4(a, b, c); }
-  static __device__ __forceinline__ T mask(T z, int act) {
-    return make_float4(act_mask(z.x, act), act_mask(z.y, act), act_mask(z.z, act),
-                       act_mask(z.w, act));
-  }
+  static __device__ __forceinline__ T mask(T z, int act) { return act_mask4(z, act); }
 };
 template <>
 struct Vt<1> {

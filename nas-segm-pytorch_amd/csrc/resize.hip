@@ -92,17 +92,8 @@ __global__ __launch_bounds__(256) void bilinear_fwd_scalar_kernel(const act_t* _
     const float v01 = lda1(xb + ((int64_t)ly.i0 * Wi + lx.i1) * C);
     const float v10 = lda1(xb + ((int64_t)ly.i1 * Wi + lx.i0) * C);
     const float v11 = lda1(xb + ((int64_t)ly.i1 * Wi + lx.i1) * C);
-    sta1(y + i, ly.l0 * (lx.l0 * v00 + lx.l1 * v01) + ly.l1 * (lx.l0 * v10 + lx.l1 * v11));
+    sta1(y + i, bilerp(v00, v01, v10, v11, ly, lx));
   }
-}
-
-__device__ __forceinline__ float4 keep_if4(float4 v, bool ok) {
-  const unsigned m = 0u - (unsigned)ok;
-  v.x = __uint_as_float(__float_as_uint(v.x) & m);
-  v.y = __uint_as_float(__float_as_uint(v.y) & m);
-  v.z = __uint_as_float(__float_as_uint(v.z) & m);
-  v.w = __uint_as_float(__float_as_uint(v.w) & m);
-  return v;
 }
 
 // One input of a channel concatenation, written into its slice [yoff, yoff + C) of the slab y (row stride
@@ -142,19 +133,13 @@ __global__ __launch_bounds__(256) void cat_src_fwd_kernel(const act_t* __restric
       const float4 v01 = act_apply4(fma4(lda4(xb + ((int64_t)ly.i0 * Wi + lx.i1) * C), sc, sf), act);
       const float4 v10 = act_apply4(fma4(lda4(xb + ((int64_t)ly.i1 * Wi + lx.i0) * C), sc, sf), act);
       const float4 v11 = act_apply4(fma4(lda4(xb + ((int64_t)ly.i1 * Wi + lx.i1) * C), sc, sf), act);
-      o.x = ly.l0 * (lx.l0 * v00.x + lx.l1 * v01.x) + ly.l1 * (lx.l0 * v10.x + lx.l1 * v11.x);
-      o.y = ly.l0 * (lx.l0 * v00.y + lx.l1 * v01.y) + ly.l1 * (lx.l0 * v10.y + lx.l1 * v11.y);
-      o.z = ly.l0 * (lx.l0 * v00.z + lx.l1 * v01.z) + ly.l1 * (lx.l0 * v10.z + lx.l1 * v11.z);
-      o.w = ly.l0 * (lx.l0 * v00.w + lx.l1 * v01.w) + ly.l1 * (lx.l0 * v10.w + lx.l1 * v11.w);
+      o = bilerp4(v00, v01, v10, v11, ly, lx);
     } else {
       o = act_apply4(fma4(lda4(x + ((int64_t)r * Wo + ox) * C + c4 * 4), sc, sf), act);
     }
     if (live) sta4(y + ((int64_t)r * Wo + ox) * ldy + yoff + c4 * 4, o);
-#ifdef NASSEG_BF16
-    o = make_float4(bf16_to_f32(f32_to_bf16(o.x)), bf16_to_f32(f32_to_bf16(o.y)), bf16_to_f32(f32_to_bf16(o.z)),
-                    bf16_to_f32(f32_to_bf16(o.w)));  // (the statistics of what a pass over the slab would read)
-#endif
-    o = keep_if4(o, live);
+    o = as_stored4(o);  // (the statistics of what a pass over the slab would read)
+    o = keep_if(o, live);
     ssum[0] = add4(ssum[0], o);
     ssum[1] = fma4(o, o, ssum[1]);
   }
@@ -217,17 +202,11 @@ __global__ __launch_bounds__(256) void cat_src_bwd_kernel(
       float4 x;
       if (ZSAME) {
         x = act_apply4(ts, act);  // (the expression nasseg_cat_src_fwd stored)
-#ifdef NASSEG_BF16
-        x = make_float4(bf16_to_f32(f32_to_bf16(x.x)), bf16_to_f32(f32_to_bf16(x.y)), bf16_to_f32(f32_to_bf16(x.z)),
-                        bf16_to_f32(f32_to_bf16(x.w)));
-#endif
+        x = as_stored4(x);
       } else {
         x = lda4(slab + pix * ld + sc);
       }
-      v.x = d.x - s0.x * invM - (x.x - smu.x) * sis.x * s1.x * invM;
-      v.y = d.y - s0.y * invM - (x.y - smu.y) * sis.y * s1.y * invM;
-      v.z = d.z - s0.z * invM - (x.z - smu.z) * sis.z * s1.z * invM;
-      v.w = d.w - s0.w * invM - (x.w - smu.w) * sis.w * s1.w * invM;
+      v = bn_dx4(d, x, smu, sis, s0, s1, invM);
     }
     v = mul4(v, ssc);
     float4 xh = f4zero();
@@ -237,8 +216,7 @@ __global__ __launch_bounds__(256) void cat_src_bwd_kernel(
       const float4 t = ZSAME ? ts : fma4(zv, tsc, tsh);
       v = make_float4(v.x * act_mask(t.x, act), v.y * act_mask(t.y, act), v.z * act_mask(t.z, act),
                       v.w * act_mask(t.w, act));
-      xh = make_float4((zv.x - tmu.x) * tis.x, (zv.y - tmu.y) * tis.y, (zv.z - tmu.z) * tis.z,
-                       (zv.w - tmu.w) * tis.w);
+      xh = xhat4(zv, tmu, tis);
     }
     if (z && RESIZE) {
       // the producer's gradient is g(p) = m(p) * sum_o w(o, p) v(o) (nasseg_bilinear_bwd_act forms it): its sums
@@ -264,11 +242,8 @@ __global__ __launch_bounds__(256) void cat_src_bwd_kernel(
       }
     }
     if (live) sta4(g + pix * C + c4 * 4, v);
-#ifdef NASSEG_BF16
-    v = make_float4(bf16_to_f32(f32_to_bf16(v.x)), bf16_to_f32(f32_to_bf16(v.y)), bf16_to_f32(f32_to_bf16(v.z)),
-                    bf16_to_f32(f32_to_bf16(v.w)));  // (what a reduction pass over g would read)
-#endif
-    v = keep_if4(v, live);
+    v = as_stored4(v);  // (what a reduction pass over g would read)
+    v = keep_if(v, live);
     ssum[0] = RESIZE ? fma4(v, ms, ssum[0]) : add4(ssum[0], v);
     ssum[1] = fma4(v, xh, ssum[1]);
   }
@@ -316,22 +291,17 @@ __global__ __launch_bounds__(256) void psum_bwd_kernel(
   float4 sa[2] = {f4zero(), f4zero()}, sb[2] = {f4zero(), f4zero()}, scf[2] = {f4zero(), f4zero()};
   for (int r = blockIdx.y; r < R; r += gridDim.y) {
     const int64_t e = ((int64_t)r * Wo + ox) * C + c4 * 4;
-    const float4 d = keep_if4(lda4(dy + e), live);
+    const float4 d = keep_if(lda4(dy + e), live);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const float4 zv = lda4(zz[s] + e);
       const float4 t = fma4(zv, sc[s], sh[s]);
       scf[s] = fma4(d, act_apply4(t, as[s]), scf[s]);
       float4 g = mul4(d, cf[s]);
-      g = make_float4(g.x * act_mask(t.x, as[s]), g.y * act_mask(t.y, as[s]), g.z * act_mask(t.z, as[s]),
-                      g.w * act_mask(t.w, as[s]));
+      g = mask4(g, t, as[s]);
       if (live && gg[s]) sta4(gg[s] + e, g);
-#ifdef NASSEG_BF16
-      g = make_float4(bf16_to_f32(f32_to_bf16(g.x)), bf16_to_f32(f32_to_bf16(g.y)), bf16_to_f32(f32_to_bf16(g.z)),
-                      bf16_to_f32(f32_to_bf16(g.w)));  // (what a reduction pass over g would read)
-#endif
-      const float4 xh = make_float4((zv.x - mu[s].x) * is[s].x, (zv.y - mu[s].y) * is[s].y, (zv.z - mu[s].z) * is[s].z,
-                                    (zv.w - mu[s].w) * is[s].w);
+      g = as_stored4(g);  // (what a reduction pass over g would read)
+      const float4 xh = xhat4(zv, mu[s], is[s]);
       float4(&acc)[2] = s == 0 ? sa : sb;
       acc[0] = add4(acc[0], g);
       acc[1] = fma4(g, xh, acc[1]);
@@ -391,15 +361,12 @@ __global__ __launch_bounds__(256) void grad_junction_kernel(JunctionSrc src, con
     for (int i = 1; i < NG; ++i) g = add4(g, gv[i]);
     if (ts) {
       const float4 t = fma4(zv, sc, sh);
-      g = make_float4(g.x * act_mask(t.x, as), g.y * act_mask(t.y, as), g.z * act_mask(t.z, as), g.w * act_mask(t.w, as));
+      g = mask4(g, t, as);
     }
-    g = keep_if4(g, live);
+    g = keep_if(g, live);
     if (live) sta4(out + e, g);
     if (part) {
-#ifdef NASSEG_BF16
-      g = make_float4(bf16_to_f32(f32_to_bf16(g.x)), bf16_to_f32(f32_to_bf16(g.y)), bf16_to_f32(f32_to_bf16(g.z)),
-                      bf16_to_f32(f32_to_bf16(g.w)));  // (what a reduction pass over the stored gradient would read)
-#endif
+      g = as_stored4(g);  // (what a reduction pass over the stored gradient would read)
       const float4 xh = make_float4((zv.x - mu.x) * is.x, (zv.y - mu.y) * is.y, (zv.z - mu.z) * is.z,
                                     (zv.w - mu.w) * is.w);
       acc[0] = add4(acc[0], g);
@@ -564,7 +531,7 @@ __global__ __launch_bounds__(256) void bilinear_bwd_win_kernel(const act_t* __re
 #pragma unroll
       for (int tx = 0; tx < NW; ++tx) {
         const float w = wy[ty] * wx[tx];
-        const float4 v = keep_if4(d[ty][tx], w != 0.f);
+        const float4 v = keep_if(d[ty][tx], w != 0.f);
         g.x = fmaf(w, v.x, g.x);
         g.y = fmaf(w, v.y, g.y);
         g.z = fmaf(w, v.z, g.z);
@@ -623,7 +590,7 @@ __global__ __launch_bounds__(256) void bilinear_bwd_axis_kernel(const TS* __rest
     for (int o = lo; o <= hi; ++o) {
       const float w = lin_weight(o, idx, scale, n_in, n_out);
       const int64_t pix = AXIS == 1 ? ((int64_t)b * H + y) * Wsrc + o : ((int64_t)b * H + o) * Wsrc + x;
-      const float4 d = keep_if4(lda4(src + pix * lds + soff + c4 * 4), w != 0.f);
+      const float4 d = keep_if(lda4(src + pix * lds + soff + c4 * 4), w != 0.f);
       g.x = fmaf(w, d.x, g.x);
       g.y = fmaf(w, d.y, g.y);
       g.z = fmaf(w, d.z, g.z);

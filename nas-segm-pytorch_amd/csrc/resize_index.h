@@ -31,6 +31,19 @@ __device__ __forceinline__ Lin lin_coeff(int dst, float scale, int in_size, int 
   return r;
 }
 
+// The resize itself: the four taps blended with contraction left to the compiler (resize.hip, ensemble.hip)
+__device__ __forceinline__ float bilerp(float v00, float v01, float v10, float v11, const Lin& ly, const Lin& lx) {
+  return ly.l0 * (lx.l0 * v00 + lx.l1 * v01) + ly.l1 * (lx.l0 * v10 + lx.l1 * v11);
+}
+__device__ __forceinline__ float4 bilerp4(float4 v00, float4 v01, float4 v10, float4 v11, const Lin& ly, const Lin& lx) {
+  float4 o;
+  o.x = bilerp(v00.x, v01.x, v10.x, v11.x, ly, lx);
+  o.y = bilerp(v00.y, v01.y, v10.y, v11.y, ly, lx);
+  o.z = bilerp(v00.z, v01.z, v10.z, v11.z, ly, lx);
+  o.w = bilerp(v00.w, v01.w, v10.w, v11.w, ly, lx);
+  return o;
+}
+
 // The fused up-sampling criteria (loss_up.hip, depth.hip): the value, and the two halves of its transpose.
 // v = ly.l0 * (lx.l0 * x00 + lx.l1 * x01) + ly.l1 * (lx.l0 * x10 + lx.l1 * x11), every product and sum rounded on
 // its own (csrc/miou.hip: argmax_cm_kernel; csrc/depth_eval.hip: depth_metrics_kernel)

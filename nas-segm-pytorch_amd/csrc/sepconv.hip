@@ -21,11 +21,6 @@
 
 namespace {
 
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float4 keep4(float4 v, bool ok) { return keep_if(v, ok); }
-
 constexpr int kSepP = 4;      // output rows per strip
 constexpr int kSepMaxPix = kSepP * 48;
 
@@ -126,7 +121,7 @@ __global__ __launch_bounds__(256) void sepconv_fwd_kernel(SepArgs a) {
         for (int t = 0; t < KX; ++t) {
           float4 u = lda4(xr + xoff[t]);
           if (PRO) u = apply_prologue(u, pro);
-          v[t] = keep4(u, yok && xok[t]);
+          v[t] = keep_if(u, yok && xok[t]);
         }
       };
       float4 vcur[KX], vnext[KX];
@@ -162,14 +157,11 @@ __global__ __launch_bounds__(256) void sepconv_fwd_kernel(SepArgs a) {
         for (int c = 0; c < 2; ++c) {
           const bool ok = ox + c < Wo && oy < Ho;
           float4 o = acc[j][c];
-#ifdef NASSEG_BF16
-          o = make_float4(bf16_to_f32(f32_to_bf16(o.x)), bf16_to_f32(f32_to_bf16(o.y)),
-                          bf16_to_f32(f32_to_bf16(o.z)), bf16_to_f32(f32_to_bf16(o.w)));
-#endif
+          o = as_stored4(o);
           if (WRZ) {
             if (ok) sta4(a.zdw + (((size_t)b * Ho + oy) * Wo + ox + c) * C + c4 * 4, o);
           }
-          *reinterpret_cast<float4*>(&zt[(j * a.Wt + xl + c) * LS + c4 * 4]) = keep4(o, ok);
+          *reinterpret_cast<float4*>(&zt[(j * a.Wt + xl + c) * LS + c4 * 4]) = keep_if(o, ok);
         }
       }
     }
@@ -208,7 +200,7 @@ __global__ __launch_bounds__(256) void sepconv_fwd_kernel(SepArgs a) {
       for (int tx = 0; tx < K; ++tx) {
         float4 t = lda4(xr + xoff[tx]);
         if (PRO) t = apply_prologue(t, pro);
-        v[tx] = keep4(t, yok && xok[tx]);
+        v[tx] = keep_if(t, yok && xok[tx]);
       }
     };
     float4 vcur[K], vnext[K];
@@ -236,15 +228,12 @@ __global__ __launch_bounds__(256) void sepconv_fwd_kernel(SepArgs a) {
       const int oy = oy0 + j * a.g;
       const bool ok = colok && oy < Ho;
       float4 o = acc[j];
-#ifdef NASSEG_BF16
       // the value a separate pointwise kernel (and the backward pass) would read back
-      o = make_float4(bf16_to_f32(f32_to_bf16(o.x)), bf16_to_f32(f32_to_bf16(o.y)),
-                      bf16_to_f32(f32_to_bf16(o.z)), bf16_to_f32(f32_to_bf16(o.w)));
-#endif
+      o = as_stored4(o);
       if (WRZ) {
         if (ok) sta4(a.zdw + (((size_t)b * Ho + oy) * Wo + ox) * C + c4 * 4, o);
       }
-      *reinterpret_cast<float4*>(&zt[(j * a.Wt + xl) * LS + c4 * 4]) = keep4(o, ok);
+      *reinterpret_cast<float4*>(&zt[(j * a.Wt + xl) * LS + c4 * 4]) = keep_if(o, ok);
     }
   }
   __syncthreads();
@@ -283,7 +272,7 @@ __global__ __launch_bounds__(256) void sepconv_fwd_kernel(SepArgs a) {
     for (int mt = 0; mt < MT; ++mt) bv[mt] = *reinterpret_cast<const float4*>(&zt[zoff[mt] + k]);
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
-      av[nt] = keep4(ld4(a.wpw + (size_t)wn[nt] * C + (kok ? k : 0)), wok[nt] && kok);
+      av[nt] = keep_if(ld4(a.wpw + (size_t)wn[nt] * C + (kok ? k : 0)), wok[nt] && kok);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       if (wave + mt * 4 < nsub) {  // (wave-uniform)
@@ -320,7 +309,7 @@ __global__ __launch_bounds__(256) void sepconv_fwd_kernel(SepArgs a) {
       const f32x4 c = acc2[mt][nt];
       float4 o = make_float4(c[0], c[1], c[2], c[3]);
       if (STATS) {
-        const float4 v = keep4(o, ok);
+        const float4 v = keep_if(o, ok);
         sx[nt][0] += v.x; sx[nt][1] += v.y; sx[nt][2] += v.z; sx[nt][3] += v.w;
         sq[nt][0] = fmaf(v.x, v.x, sq[nt][0]); sq[nt][1] = fmaf(v.y, v.y, sq[nt][1]);
         sq[nt][2] = fmaf(v.z, v.z, sq[nt][2]); sq[nt][3] = fmaf(v.w, v.w, sq[nt][3]);
